@@ -12,13 +12,21 @@ posttrans Linear(12F->F) + BatchNorm(eval) + ReLU + residual), eval mode, inputs
 With N > 1 the graph has N x the nodes/edges (weak scaling), is sharded by destination range, and each
 step includes the RCCL halo all-to-all of source rows.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, ms_per_step, higher_is_better, dtype) and `config`.  A plain
+call does only what that line needs: set-up, the untimed pre-conditioning, W warm-up steps, K timed steps.
+
+    --dump-outputs DIR   after the timed steps, a fixed, seeded sample of the rows the LAST timed step returned, float32, as
+                         DIR/y_rows.npy (N > 1: DIR/y_rows_rank<r>.npy); at most DUMP_BYTES in all.  Same arguments -> same inputs,
+                         so two builds can be compared output for output.
+    --full               everything else the line has carried, measured after the timed steps (all legs skip on their own flags):
   roofline     -- the step's dominant kernel vs the 8 TB/s HBM roofline on ALGORITHMIC bytes / its measured mean
                   duration (HIP events): the one-kernel layer pna_fused_degree_f32 (gather + aggregators + scalers + posttrans; the
                   4F aggregate is never written: E_g (4F+4) + V_g (8F+4) bytes) where it runs, else the standalone segment-reduce
                   (E (4F+4) + 4 (V+1) + V 16F); `read_only_frac` = the gather's reads alone (the north star's 60 % target)
   cpu_baseline -- the oracle's C port (oracle/pna_oracle.c, OpenMP) + torch CPU Linear/BN of the same
                   layer, timed on this box's host cores on a bounded sample (rank 0, N=1 only)
+  and the per-graph set-up times, the sampled parity check against the oracle, the cold-cache, contiguous-input, hipGraph and
+  other-arithmetic legs, the per-kernel timings and power probe, and (N = 1, default workload) the configs[4]-shape child leg.
 """
 import argparse
 import gc
@@ -50,6 +58,8 @@ ARITH_TEXT = {
               "accumulate; error vs float64 at the exact-f32 kernel's level (tests/test_gpu_posttrans_x3.py)",
 }
 MFMA_BF16_PEAK = 2.5e15    # FLOP/s, dense bf16 MFMA; the bf16x3 contraction spends 6 bf16 products per fp32 multiply
+DUMP_BYTES = 32 << 20      # --dump-outputs: bytes of sampled output rows over all ranks
+DUMP_SEED = 2024
 
 
 def parse():
@@ -76,7 +86,14 @@ def parse():
     p.add_argument("--layers", type=int, default=1, help="> 1: a step = this many stacked layers (N > 1: inter-layer halo exchange cut into row "
                    "blocks, pna_amd.shard.BlockPipeline); a reduced JSON line, the default line describes ONE layer")
     p.add_argument("--blocks", type=int, default=4, help="--layers > 1, N > 1: row blocks per layer of the pipelined exchange")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="after the timed steps also run every diagnostic leg (set-up times, parity check, "
+                   "cold / contiguous / hipGraph / arithmetic legs, per-kernel rooflines, power probe, CPU baselines, configs[4]-shape leg)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed, seeded sample of the last timed step's output "
+                   "rows to DIR/*.npy (float32)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
 
 
 def power_probe(fn, seconds=1.5):
@@ -273,6 +290,56 @@ def F_of(layer_sd):
     return layer_sd["posttrans.fully_connected.0.linear.weight"].shape[1] // 12
 
 
+def dump_outputs(out_dir, y, rank, world):
+    """--dump-outputs: the rows of `y` (what the last timed step returned) at a fixed, seeded sample of row indices -- all rows when
+    they fit in DUMP_BYTES / world -- in ascending order, float32, as out_dir/y_rows.npy (N > 1: y_rows_rank<r>.npy)."""
+    import numpy as np
+    n_rows, width = y.shape
+    n = min(n_rows, max(1, DUMP_BYTES // world // (4 * width)))
+    rows = torch.randperm(n_rows, generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+    sample = y[rows.to(y.device)].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y_rows.npy" if world == 1 else f"y_rows_rank{rank}.npy"), sample)
+
+
+def one_kernel_arith(layer, g, h):
+    """The contraction arithmetic's name (pna_amd._lib.FD_ARITH_NAMES) when the step runs the group rows as the one-kernel layer, else
+    None: the path test of the --full per-kernel section, without its timing."""
+    from pna_amd import _lib, degree_groups as DG
+    with torch.no_grad():
+        if not (hasattr(layer, "_degree_grouped_path") and layer._degree_grouped_path(g, h) and DG.fused_applies(g, g.source_features(h), F, F)):
+            return None
+    return _lib.FD_ARITH_NAMES[DG.fused_arith()]
+
+
+def headline(args, world, V, E, g, n_local, e_local, value, ms_per_step, prewarm, arith, fused_arith, guard_info=None):
+    """The line's headline fields and `config`, plain and --full calls alike.  fused_arith: the one-kernel layer's contraction (None when
+    the step took the two-kernel path, whose contraction is `arith`)."""
+    wl = ("BASELINE.json configs[2]: synthetic power-law graph |V|=1M |E|=10M per GPU, F=75, " if args.workload == "c3" else
+          "BASELINE.json configs[4]: synthetic power-law graph |V|=2M |E|=20M per GPU (16M / 160M over 8 GPUs), F=128, ")
+    return {
+        "metric": f"PNA-layer fwd edges/sec (F={F}, 4 aggr x 3 scalers)", "value": value, "unit": "edges/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" + (f" (fp32 in / out / accumulation; posttrans contraction: {fused_arith}, see config.posttrans_arith)" if fused_arith else ""),
+        "data": "synthetic",
+        "prewarm_steps_untimed": prewarm,
+        "config": {"workload": wl + f"single PNA (simple) layer fwd: 4 aggregators x 3 scalers + posttrans Linear({12 * F}->{F}) + BN + ReLU + residual",
+                   "V": V, "E": E, "F": F, "aggregators": AGGREGATORS, "scalers": SCALERS,
+                   "parallelism": f"dst-range shard x{world}, halo all-to-all" if world > 1 else "single GPU",
+                   "x_row_pitch_floats": max(args.x_pitch, F),
+                   # (the arithmetic of the path the timed step TOOK: the one-kernel layer's for its group rows, the two-kernel path's otherwise)
+                   "posttrans_arith": (ARITH_TEXT[fused_arith] + " -- the group rows of the one-kernel layer; the rest rows (two-kernel path): bf16x3") if fused_arith
+                                      else ARITH_TEXT["bf16x3"] if arith == "bf16x3" else "f32 (v_mfma_f32_16x16x4_f32)",
+                   "guard": guard_info,
+                   "max_in_degree": int(g.csr.max_degree), "halo_rows_rank0": getattr(g, "n_halo", 0),
+                   "interior_rows_rank0": int(g.interior_mask().sum().item()) if world > 1 else None,
+                   "local_rows_rank0": n_local, "local_edges_rank0": e_local, "partition_balance": args.balance if world > 1 else None,
+                   "halo_exchange_in_step": ("every timed step runs the halo all-to-all of the source rows (pack + all_to_all_single over RCCL) before its "
+                                             "kernel, although this benchmark's features do not change between steps: it is the cost a multi-layer net "
+                                             "pays once per layer; nothing is prefetched or reused across steps") if world > 1 else None}}
+
+
 def main():
     args = parse()
     global F
@@ -358,8 +425,9 @@ def main():
     # ---- per-graph / per-weight set-up of the one-kernel layer, timed on its own BEFORE any step (set-up reported
     #      separately).  Once per graph: the degree plan (row order, tile-major id records, descriptors) and the
     #      rest rows' work list; once per (weights, graph): the packed weight images W_D (fp16 x 2 and bf16 x 3).  Neither is part of a step.
+    #      --full only: a plain call leaves these builds to the first untimed step.
     setup = None
-    if world == 1 and hasattr(layer, "_degree_grouped_path"):
+    if args.full and world == 1 and hasattr(layer, "_degree_grouped_path"):
         from pna_amd import degree_groups as _DGs
         with torch.no_grad():
             # (round 6, VERDICT r5 item 6: the FIRST plan of a process used to be what this clock saw -- 440 ms, of which 436 were torch loading
@@ -461,8 +529,9 @@ def main():
             step_l()
         sync()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step_l()
+        y_last = step_l()                                      # (N > 1: the table whose local rows hold the last layer's output)
         sync()
         dt = time.perf_counter() - t0
         gc.enable()
@@ -470,6 +539,8 @@ def main():
             tt = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, y_last[:n_local, :F], rank, world)
         if rank == 0:
             print(json.dumps({"metric": "PNA-layer fwd edges/sec (F=%d, 4 aggr x 3 scalers), %d stacked layers per step" % (F, L),
                               "value": E * L / (dt / args.steps), "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -520,8 +591,9 @@ def main():
             t_ = time.perf_counter(); step(); sync(); ts.append(round((time.perf_counter() - t_) * 1e3, 3))
         print("[bench] per-step ms:", ts, file=sys.stderr, flush=True)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    y_last = step()                                            # (held from the last step only: the K - 1 before it free theirs as always)
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
@@ -531,6 +603,21 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     value = E / (dt / args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y_last, rank, world)
+    del y_last
+
+    # the contraction arithmetic of the two-kernel path (the rest rows; all rows when the one-kernel layer does not apply)
+    from pna_amd import ops as _ops
+    arith = "bf16x3" if (_ops.POSTTRANS_ARITH == "bf16x3" or (_ops.POSTTRANS_ARITH == "auto" and n_local >= _ops.X3_MIN_ROWS)) else "f32"
+    if not args.full:
+        rec = headline(args, world, V, E, g, n_local, e_local, value, ms_per_step, prewarm, arith, one_kernel_arith(layer, g, h))
+        if rank == 0:
+            print(json.dumps(_finite(rec)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the timed kernels did the work: sampled rows of one more step's output against the oracle --------------------
     check = None
@@ -623,8 +710,6 @@ def main():
             ms_per_step_hipgraph = None
 
     # the same step with the contraction forced onto the exact f32-input MFMA (reported beside the headline number)
-    from pna_amd import ops as _ops
-    arith = "bf16x3" if (_ops.POSTTRANS_ARITH == "bf16x3" or (_ops.POSTTRANS_ARITH == "auto" and n_local >= _ops.X3_MIN_ROWS)) else "f32"
     ms_per_step_f32 = ms_per_step
     if arith != "f32":
         keep = _ops.POSTTRANS_ARITH
@@ -887,8 +972,6 @@ def main():
                       "achieved": layer_bytes / (ms_per_step * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                       "frac": layer_bytes / (ms_per_step * 1e-3) / HBM_PEAK,
                       "note": "E(4F+4) + 4(V+1) + 2*V*4F: what a layer that never materialised the 4F aggregate would have to move"}
-    wl = ("BASELINE.json configs[2]: synthetic power-law graph |V|=1M |E|=10M per GPU, F=75, " if args.workload == "c3" else
-          "BASELINE.json configs[4]: synthetic power-law graph |V|=2M |E|=20M per GPU (16M / 160M over 8 GPUs), F=128, ")
     if halo_rate is not None:
         # whole-job speed-up over one GPU running the same per-GPU shape = world x t_1 / t_world; t_world >= max(compute, exchange at link peak)
         # when the exchange is perfectly hidden (and >= their sum when it is not hidden at all).  compute: this rank's kernels without the exchange.
@@ -899,27 +982,8 @@ def main():
                                                   "note": "weak scaling, against one GPU at this rank's compute time; the Chung-Lu generator has no locality -- "
                                                           "every rank references ~70 % of every peer's rows -- so at 8 GPUs the bound sits below the north "
                                                           "star's 6 x (DESIGN.md 7)"}
-    rec = {
-        "metric": f"PNA-layer fwd edges/sec (F={F}, 4 aggr x 3 scalers)", "value": value, "unit": "edges/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" + (f" (fp32 in / out / accumulation; posttrans contraction: {fused['arith']}, see config.posttrans_arith)" if fused else ""),
-        "data": "synthetic",
-        "prewarm_steps_untimed": prewarm,
-        "config": {"workload": wl + f"single PNA (simple) layer fwd: 4 aggregators x 3 scalers + posttrans Linear({12 * F}->{F}) + BN + ReLU + residual",
-                   "V": V, "E": E, "F": F, "aggregators": AGGREGATORS, "scalers": SCALERS,
-                   "parallelism": f"dst-range shard x{world}, halo all-to-all" if world > 1 else "single GPU",
-                   "x_row_pitch_floats": max(args.x_pitch, F),
-                   # (the arithmetic of the path the timed step TOOK: the one-kernel layer's for its group rows, the two-kernel path's otherwise)
-                   "posttrans_arith": (ARITH_TEXT[fused["arith"]] + " -- the group rows of the one-kernel layer; the rest rows (two-kernel path): bf16x3") if fused
-                                      else ARITH_TEXT["bf16x3"] if arith == "bf16x3" else "f32 (v_mfma_f32_16x16x4_f32)",
-                   "guard": guard_info,
-                   "max_in_degree": int(csr.max_degree), "halo_rows_rank0": getattr(g, "n_halo", 0),
-                   "interior_rows_rank0": int(g.interior_mask().sum().item()) if world > 1 else None,
-                   "local_rows_rank0": n_local, "local_edges_rank0": e_local, "partition_balance": args.balance if world > 1 else None,
-                   "halo_exchange_in_step": ("every timed step runs the halo all-to-all of the source rows (pack + all_to_all_single over RCCL) before its "
-                                             "kernel, although this benchmark's features do not change between steps: it is the cost a multi-layer net "
-                                             "pays once per layer; nothing is prefetched or reused across steps") if world > 1 else None},
+    rec = headline(args, world, V, E, g, n_local, e_local, value, ms_per_step, prewarm, arith, fused["arith"] if fused else None, guard_info)
+    rec.update({
         "roofline": roofline, "roofline_segreduce_standalone": roofline_segreduce, "roofline_posttrans": roofline_post, "roofline_layer": roofline_layer,
         "power_probe": power,
         "ms_per_step_cold": ms_per_step_cold, "value_cold": (E / (ms_per_step_cold * 1e-3)) if ms_per_step_cold else None,
@@ -940,7 +1004,7 @@ def main():
                               "takes_the_one_kernel_layer": contig_one_kernel, "output_bits_equal_the_aligned_step": contig_same_bits,
                               "value": E / (ms_per_step_contig * 1e-3), "ratio_to_headline": ms_per_step_contig / ms_per_step}
                              if ms_per_step_contig else None),
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             rec["cpu_baseline"] = cpu_baseline(src, dst, V, h_all, layer_sd, avg_log, args.cpu_sample_rows)
@@ -956,8 +1020,8 @@ def main():
     if (rank == 0 and world == 1 and args.workload == "c3" and not args.no_c5_leg and args.layers == 1
             and args.nodes_per_gpu == V_PER_GPU and args.edges_per_gpu == E_PER_GPU):
         # BASELINE configs[4] (V = 16 M, E = 160 M, F = 128 over 8 GPUs) is the driver's to launch; its PER-GPU shape on this one GPU
-        # rides along with every default call, so that the number is driver-run too
-        rec["configs4_per_gpu_shape"] = other_workload_leg(["--workload", "c5", "--no-cpu-baseline", "--no-cold", "--no-power-probe",
+        # rides along with every --full call of the default workload, so that the number is driver-run too
+        rec["configs4_per_gpu_shape"] = other_workload_leg(["--workload", "c5", "--full", "--no-cpu-baseline", "--no-cold", "--no-power-probe",
                                                             "--steps", "10", "--warmup", "3"])
     if rank == 0:
         rec["diagnostics_error"] = diag_error

@@ -24,7 +24,7 @@ def test_bench_two_ranks_on_one_gpu_prints_the_contract_line(cuda_device, worklo
     V, E = 150_000, 1_500_000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--nodes-per-gpu", str(V), "--edges-per-gpu", str(E),
-           "--no-cpu-baseline", "--kernel-iters", "2", "--workload", workload]
+           "--full", "--no-cpu-baseline", "--kernel-iters", "2", "--workload", workload]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-500:], out.stderr[-1500:])

@@ -283,16 +283,21 @@ def test_avg_d_producers_match_the_reference_formulas():
     assert b["log"].item() == pytest.approx((math.log(2) + (math.log(3) + 2 * math.log(2)) / 3) / 2, rel=1e-6)
 
 
-def test_bench_child_leg_never_sinks_the_line(monkeypatch):
-    """bench.py's default call runs BASELINE configs[4]'s per-GPU shape in a child process (`configs4_per_gpu_shape`): a child that
-    fails, prints nothing or times out costs that field only; a child's line is cut down to the fields a reader compares."""
+def _bench_module():
     import importlib.util
-    import json
-    import subprocess
-    import types
     spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_child_leg_never_sinks_the_line(monkeypatch):
+    """bench.py's default call runs BASELINE configs[4]'s per-GPU shape in a child process (`configs4_per_gpu_shape`): a child that
+    fails, prints nothing or times out costs that field only; a child's line is cut down to the fields a reader compares."""
+    import json
+    import subprocess
+    import types
+    bench = _bench_module()
     line = open(os.path.join(ROOT, "profiles", "r03_bench_c5_shard_shape_n1.json")).read().strip()
     monkeypatch.setattr(subprocess, "run", lambda *a, **k: types.SimpleNamespace(returncode=0, stdout="a warning\n" + line + "\n"))
     r = bench.other_workload_leg(["--workload", "c5"])
@@ -305,6 +310,41 @@ def test_bench_child_leg_never_sinks_the_line(monkeypatch):
         raise subprocess.TimeoutExpired(cmd="bench.py", timeout=1)
     monkeypatch.setattr(subprocess, "run", boom)
     assert "TimeoutExpired" in bench.other_workload_leg(["--workload", "c5"])["error"]
+
+
+def test_bench_options_plain_full_and_dump(monkeypatch):
+    """A plain bench.py call runs no diagnostic leg (--full is off by default); --steps is the number of timed steps and must be >= 1."""
+    import sys
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out_dir"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_budget(tmp_path):
+    """--dump-outputs: the same seeded rows every time, ascending, float32, values untouched; all rows when they fit; <= DUMP_BYTES over
+    the ranks (one file per rank when N > 1)."""
+    bench = _bench_module()
+    gen = torch.Generator().manual_seed(5)
+    big = torch.randn(300_000, 75, generator=gen)[:, :75]
+    bench.dump_outputs(str(tmp_path / "a"), big, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), big, 0, 1)
+    a, b = np.load(tmp_path / "a" / "y_rows.npy"), np.load(tmp_path / "b" / "y_rows.npy")
+    assert a.dtype == np.float32 and a.shape[1] == 75 and np.array_equal(a, b)
+    assert 0 < a.nbytes <= bench.DUMP_BYTES and a.nbytes > bench.DUMP_BYTES - 75 * 4
+    rows = torch.randperm(big.shape[0], generator=torch.Generator().manual_seed(bench.DUMP_SEED))[:a.shape[0]].sort().values
+    assert np.array_equal(a, big[rows].numpy())
+    small = torch.randn(1000, 80, generator=gen)[:, :75]                  # (a pitched view, like the layer's output)
+    bench.dump_outputs(str(tmp_path / "c"), small, 1, 2)
+    assert np.array_equal(np.load(tmp_path / "c" / "y_rows_rank1.npy"), small.numpy())
+    bench.dump_outputs(str(tmp_path / "d"), big, 1, 4)
+    assert np.load(tmp_path / "d" / "y_rows_rank1.npy").nbytes <= bench.DUMP_BYTES // 4
 
 
 def test_registered_edge_types_answer_without_a_search(monkeypatch):

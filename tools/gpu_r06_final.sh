@@ -10,12 +10,12 @@ rm -rf $O; mkdir -p $O
 cd $P
 timeout 700 python -m pytest tests -m gpu -q --timeout 300 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed" $O/pytest_gpu.log | tail -8
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
 grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*' $O/bench_n1.json | head -4
-timeout 300 python bench.py --workload c5 --no-cpu-baseline --no-cold > $O/bench_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?"
+timeout 300 python bench.py --workload c5 --full --no-cpu-baseline --no-cold > $O/bench_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?"
 timeout 200 python bench.py --layers 4 --steps 10 --warmup 3 > $O/bench_layers4.json 2> $O/bench_layers4.err; echo "layers rc=$?"
 cd /tmp; rm -rf $O/trace
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $P/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cold --no-power-probe --no-c5-leg > $O/trace.log 2>&1; echo "trace rc=$?"
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $P/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-cold --no-power-probe --no-c5-leg > $O/trace.log 2>&1; echo "trace rc=$?"
 find $O/trace -name "bench_kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 head -5 $O/bench_kernel_stats.csv | cut -c1-220
 rm -rf $O/trace
