@@ -13,7 +13,7 @@
  *   - stream-ordered and asynchronous: nothing here synchronises the device;
  *   - re-entrant: no global mutable state except the per-thread last-error string;
  *   - return value 0 = success, negative = error (see PNA_E_*); pna_last_error() gives the text;
- *   - all data is fp32 and all arithmetic is fp32 (pna_posttrans_x3_f32 evaluates each fp32 product as six exact
+ *   - all data is fp32 and all arithmetic is fp32, except the two bf16 entry points of ABI 22 (bf16 data, fp32 accumulation) (pna_posttrans_x3_f32 evaluates each fp32 product as six exact
  *     bf16 partial products accumulated in fp32 -- fp32-level accuracy, see there); indices are int32; row strides
  *     (ld*) are in floats.
  */
@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 21 /* 21: the GUARDED fp16 x 2 contraction of the one-kernel layer (round 6): + pna_fused_degree_args.{w_img_x3,
+#define PNA_ABI_VERSION 22 /* 22: + pna_segreduce_fwd_bf16 / pna_segreduce_bf16_partials_bytes, pna_posttrans_bf16 / pna_posttrans_bf16_tiles
+                                  (bf16 inference of PNASimpleLayer; pna_segreduce_bf16_args, pna_posttrans_bf16_args).
+                              21: the GUARDED fp16 x 2 contraction of the one-kernel layer (round 6): + pna_fused_degree_args.{w_img_x3,
                                   image_stride_x3, guard_ws, guard_ws_bytes, arith}, PNA_FD_ARITH_*, pna_fused_image_bytes, pna_fused_pack_f32,
                                   pna_fused_degree_guard_bytes; the fp16 x 2 images carry a 1024-byte tail (column scales + the guard's column
                                   thresholds); image_stride must EQUAL pna_fused_image_bytes; row scale bound in [2^14, 2^15).
@@ -966,6 +968,90 @@ typedef struct pna_bn_tail_args {
 int64_t pna_bn_tail_workspace_bytes(int64_t M, int32_t N);
 int pna_bn_tail_fwd_f32(const pna_bn_tail_args* args, pna_stream_t stream);
 int pna_bn_tail_bwd_f32(const pna_bn_tail_args* args, pna_stream_t stream);
+
+/* ---- bf16 inference of PNASimpleLayer (ABI 22) ------------------------------------------------------------------------------
+ *
+ * Two entry points for a layer whose features and parameters are bf16 (pna_amd.functional.simple_layer_bf16); together they
+ * replace PNASimpleLayer.reduce_func + forward, models/dgl/pna_layer.py:189-216, with the aggregators of models/dgl/aggregators.py.  Data pointers typed
+ * `void*` below hold bf16 values (the upper 16 bits of an IEEE fp32); row strides (ld*) are in ELEMENTS of the pointed-to type.
+ *
+ * pna_segreduce_fwd_bf16 -- replaces reduce_func of PNASimpleLayer, models/dgl/pna_layer.py:189-194 (copy_u message + update_all,
+ * :202), with the aggregators of models/dgl/aggregators.py:6-26,50-51 (mean, sum, max, min, std, var; identity scaler only):
+ *     out[v * ldo + a * block_stride + f] = bf16( aggr[a]( x[col[k]][f] : k in [rowptr[v], rowptr[v+1]) ) )
+ * Every statistic is accumulated in fp32 in CSR edge order (hub rows: per heavy segment, then over segments in segment order) with
+ * the formulas of pna_segreduce_fwd_f32 (mean = s / D correctly rounded; var = relu(E[x^2] - E[x]^2); std = sqrt(var + 1e-5)),
+ * then rounded to bf16 ONCE.  Rows with no in-edges give 0.  No atomics: repeated calls give identical bits.
+ * With block_stride a multiple of 8, columns [F, round8(F)) of every block are written as 0 and the stores are 16 bytes wide;
+ * otherwise only the F columns of each block are written.  x: any pitch ldx >= F; with ldx a multiple of 8 and a 16-byte aligned
+ * x, rows are gathered in 16-byte pieces when F is a multiple of 8 or x_tail_readable = 1 (columns [F, round8(F)) of every row of
+ * x may be read; their values are ignored).  Hub rows: the Graph's heavy-row schedule (pna_segreduce_args "Heavy rows"), with
+ * `partials` = pna_segreduce_bf16_partials_bytes(n_seg, F) bytes of fp32 workspace.  F <= 512. */
+typedef struct pna_segreduce_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_segreduce_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* rowptr;   /* [V+1] */
+  const int32_t* col;      /* [E] source row of each CSR edge */
+  int32_t V;
+  int32_t F;
+  const void* x;           /* bf16 (x_rows, ldx) */
+  int64_t ldx;
+  int32_t x_tail_readable; /* 1 = columns [F, round8(F)) of every row of x may be read */
+  int32_t n_aggr;
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_VAR */
+  void* out;               /* bf16 (V, ldo), 16-byte aligned, ldo a multiple of 8 and >= (n_aggr - 1) * block_stride + F */
+  int64_t ldo;
+  int32_t block_stride;    /* columns between aggregator blocks (>= F); 0 = F */
+  int32_t heavy_threshold; /* rows with more in-edges are reduced through the heavy schedule (when n_heavy > 0) */
+  int32_t seg_len;
+  int32_t n_heavy;
+  int32_t n_seg;
+  int32_t _pad0;
+  const int32_t* heavy_rows;   /* [n_heavy] */
+  const int32_t* heavy_segptr; /* [n_heavy+1] */
+  const int32_t* seg_heavy;    /* [n_seg] */
+  float* partials;             /* workspace */
+} pna_segreduce_bf16_args;
+
+int pna_segreduce_fwd_bf16(const pna_segreduce_bf16_args* args, pna_stream_t stream);
+int64_t pna_segreduce_bf16_partials_bytes(int32_t n_seg, int32_t F);
+
+/* pna_posttrans_bf16 -- replaces the posttrans nn.Linear and, with `epilogue`, the eval-mode tail of PNASimpleLayer,
+ * models/dgl/pna_layer.py:206-213 (BatchNorm with running statistics :209-210, ReLU :211, residual :212-213):
+ *     z[v] = sum_s row_scale[s][v] * (W_s . a[v]) + bias
+ *     y[v] = bf16( epilogue ? residual[v] + relu(z[v] * col_scale + col_shift) : z[v] )
+ * `a` is the (M, K) bf16 aggregate of pna_segreduce_fwd_bf16 (K a multiple of 8; every one of its K columns must be finite where
+ * the weight is zero), W_s the column block of the reference weight that multiplies scaler s (models/dgl/pna_layer.py:48-49).
+ * The products are single bf16 x bf16 products on v_mfma_f32_16x16x32_bf16, accumulated in fp32 per scaler block; the row scalers
+ * (fp32, models/dgl/scalers.py:7-19 -- Graph.degree_scalers) multiply those fp32 sums, so the (M, S K) scaled operand is never
+ * formed.  y is rounded to bf16 once.  w_img: bf16 (n_scaler, 16 T, round32(K)) row-major, T = pna_posttrans_bf16_tiles(N),
+ * element [s][n][k] = W_s[n][k], zero outside n < N, k < K.  bias (bf16 [N]), row_scale[s] (fp32 [M]; NULL = identity),
+ * col_scale / col_shift (fp32 [N], the folded BatchNorm; NULL = none) and residual (bf16 (M, ld_res)) are optional; relu and the
+ * three after the bias apply only with epilogue = 1.  1 <= N <= 128, n_scaler <= 3. */
+typedef struct pna_posttrans_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_posttrans_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const void* a;           /* bf16 (M, lda), 16-byte aligned, lda a multiple of 8 */
+  int64_t lda;
+  int32_t M;
+  int32_t K;
+  int32_t N;
+  int32_t n_scaler;
+  const float* row_scale[PNA_MAX_SCALER];
+  const void* w_img;       /* bf16 image, 16-byte aligned */
+  const void* bias;        /* bf16 [N], nullable */
+  int32_t epilogue;        /* 1 = BatchNorm fold / ReLU / residual after the bias; 0 = y = z */
+  int32_t relu;
+  const float* col_scale;  /* nullable [N]: gamma / sqrt(running_var + eps) */
+  const float* col_shift;  /* nullable [N]: beta - running_mean * col_scale */
+  const void* residual;    /* bf16 (M, ld_res), nullable */
+  int64_t ld_res;
+  void* y;                 /* bf16 (M, ldy) */
+  int64_t ldy;
+} pna_posttrans_bf16_args;
+
+int pna_posttrans_bf16(const pna_posttrans_bf16_args* args, pna_stream_t stream);
+/* Column tiles of 16 the weight image of an N-column contraction has (2, 4, 5 or 8); -1 when N is outside 1..128. */
+int pna_posttrans_bf16_tiles(int32_t N);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

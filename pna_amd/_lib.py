@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PNA_AMD_LIB_PATH: another build of the same ABI -- tools/build_variant.sh, the -DPNA_AMD_EXPERIMENTS build -- for same-box A/B runs)
 LIB_PATH = os.environ.get("PNA_AMD_LIB_PATH") or os.path.join(_HERE, "lib", "libpna_amd.so")
 
-PNA_ABI_VERSION = 21
+PNA_ABI_VERSION = 22
 PNA_MAX_AGGR = 8
 PNA_MAX_SCALER = 8
 
@@ -213,6 +213,31 @@ class PnaTowerLayerArgs(_Args):
     ]
 
 
+class PnaSegreduceBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("V", ctypes.c_int32), ("F", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("x_tail_readable", ctypes.c_int32), ("n_aggr", ctypes.c_int32),
+        ("aggr", ctypes.c_int32 * PNA_MAX_AGGR),
+        ("out", ctypes.c_void_p), ("ldo", ctypes.c_int64), ("block_stride", ctypes.c_int32),
+        ("heavy_threshold", ctypes.c_int32), ("seg_len", ctypes.c_int32), ("n_heavy", ctypes.c_int32), ("n_seg", ctypes.c_int32),
+        ("_pad0", ctypes.c_int32),
+        ("heavy_rows", ctypes.c_void_p), ("heavy_segptr", ctypes.c_void_p), ("seg_heavy", ctypes.c_void_p), ("partials", ctypes.c_void_p),
+    ]
+
+
+class PnaPosttransBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("a", ctypes.c_void_p), ("lda", ctypes.c_int64), ("M", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("N", ctypes.c_int32), ("n_scaler", ctypes.c_int32),
+        ("row_scale", ctypes.c_void_p * PNA_MAX_SCALER),
+        ("w_img", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("epilogue", ctypes.c_int32), ("relu", ctypes.c_int32),
+        ("col_scale", ctypes.c_void_p), ("col_shift", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("ld_res", ctypes.c_int64),
+        ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -327,6 +352,14 @@ def lib():
         L.pna_tower_post_pack_f32.restype = ctypes.c_int
         L.pna_tower_layer_f32.argtypes = [ctypes.POINTER(PnaTowerLayerArgs), ctypes.c_void_p]
         L.pna_tower_layer_f32.restype = ctypes.c_int
+        L.pna_segreduce_fwd_bf16.argtypes = [ctypes.POINTER(PnaSegreduceBf16Args), ctypes.c_void_p]
+        L.pna_segreduce_fwd_bf16.restype = ctypes.c_int
+        L.pna_segreduce_bf16_partials_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        L.pna_segreduce_bf16_partials_bytes.restype = ctypes.c_int64
+        L.pna_posttrans_bf16.argtypes = [ctypes.POINTER(PnaPosttransBf16Args), ctypes.c_void_p]
+        L.pna_posttrans_bf16.restype = ctypes.c_int
+        L.pna_posttrans_bf16_tiles.argtypes = [ctypes.c_int32]
+        L.pna_posttrans_bf16_tiles.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

@@ -476,8 +476,20 @@ class PNASimpleLayer(nn.Module):
             return False
         return not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters())))
 
+    def _bf16_path(self, graph, h):
+        """Whether this call is served by the bf16 inference kernels (functional.simple_layer_bf16): bf16 features and every
+        floating-point parameter and buffer bf16, inference (eval mode, no gradient required), features on the GPU and a whole
+        Graph.  Every other call -- fp32, bf16 training, sharded graphs -- takes the fp32 code below."""
+        if h.dtype != torch.bfloat16 or self.training or not h.is_cuda or type(graph) is not Graph:
+            return False
+        if any(t.dtype != torch.bfloat16 for t in list(self.parameters()) + list(self.buffers()) if t.is_floating_point()):
+            return False
+        return not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters())))
+
     def forward(self, g, h):
         graph = as_graph(g)
+        if self._bf16_path(graph, h):
+            return PF.simple_layer_bf16(self, graph, h)
         if self._small_batch_path(graph, h):
             return PF.simple_layer_small(self, graph, h, _row_scales(graph, self.scalers, self.avg_d, h.device))
         h_in = h

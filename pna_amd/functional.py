@@ -1339,3 +1339,56 @@ class SimpleLayerRows:
             cs, ct, _ = _layer_tail_operands(layer, x)
             ops.posttrans(self.agg[r0:r1, :K], K, lin.weight, [None if r is None else r[r0:r1] for r in scales], lin.bias, out=out[:, :layer.out_dim],
                           col_scale=cs, col_shift=ct, relu=True, residual=x[r0:r1] if layer.residual else None)
+
+
+def _fold_batchnorm_f32(bn):
+    """_fold_batchnorm of a bf16 BatchNorm1d, folded in fp32 from the bf16 parameters and running statistics (the bf16 epilogue
+    of pna_posttrans_bf16 takes fp32 column constants); cached on the module like _fold_batchnorm."""
+    ts = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+    key = tuple((id(t), t._version, t.data_ptr(), str(t.device)) for t in ts) + (bn.eps,)
+    hit = bn.__dict__.get("_pna_amd_fold_f32")
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            cs = (bn.weight.float() if bn.weight is not None else 1.0) * torch.rsqrt(bn.running_var.float() + bn.eps)
+            ct = (bn.bias.float() if bn.bias is not None else 0.0) - bn.running_mean.float() * cs
+        hit = (key, cs.contiguous(), ct.contiguous(), ts)
+        bn.__dict__["_pna_amd_fold_f32"] = hit
+    return hit[1], hit[2]
+
+
+def simple_layer_bf16(layer, graph, h):
+    """PNASimpleLayer.forward (models/dgl/pna_layer.py:197-216) in inference on bf16 features and parameters: the bf16 aggregate of
+    pna_segreduce_fwd_bf16 (blocks round8(F) columns apart, fp32 statistics), then pna_posttrans_bf16 with the degree scalers,
+    bias, folded BatchNorm, ReLU and residual in its epilogue.  A deeper posttrans MLP runs its first Linear on the kernel (no
+    epilogue) and the rest -- its later layers, BatchNorm, ReLU, residual -- as the module's own bf16 torch ops."""
+    from .dgl.pna_layer import _row_scales
+    F = layer.in_dim
+    if h.dim() != 2 or h.shape[1] != F:
+        raise ValueError(f"expected features of shape (V, {F}), got {tuple(h.shape)}")
+    if h.stride(-1) != 1:
+        h = h.contiguous()
+    A = len(layer.aggregators)
+    Fb = (F + 7) // 8 * 8
+    csr = graph.csr
+    agg = ops.segreduce_bf16(csr.rowptr, csr.col, h, F, layer.aggregators, block_stride=Fb, heavy=graph.heavy_schedule(),
+                             workspace=graph.workspace)
+    scales = _row_scales(graph, layer.scalers, layer.avg_d, h.device)
+    lin = layer.posttrans.fully_connected[0].linear
+    w_img = ops.pack_posttrans_weight_bf16(lin.weight, len(scales), A, F, Fb)
+    if layer.posttrans.is_affine:
+        if layer.residual and h.shape[1] != layer.out_dim:
+            raise RuntimeError(f"The size of tensor a ({h.shape[1]}) must match the size of tensor b "
+                               f"({layer.out_dim}) at non-singleton dimension 1")   # same failure as the reference (:213)
+        cs = ct = None
+        if layer.batch_norm:
+            cs, ct = _fold_batchnorm_f32(layer.batchnorm_h)
+        return ops.posttrans_bf16(agg, A * Fb, w_img, lin.out_features, scales, lin.bias, epilogue=True, relu=True,
+                                  col_scale=cs, col_shift=ct, residual=h if layer.residual else None)
+    y = ops.posttrans_bf16(agg, A * Fb, w_img, lin.out_features, scales, lin.bias)
+    y = layer.posttrans.tail(y)
+    if layer.batch_norm:
+        y = layer.batchnorm_h(y)
+    y = torch.relu(y)
+    if layer.residual:
+        y = h + y
+    return y

@@ -639,3 +639,110 @@ def tower_layer(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *, n_t
     rc = _lib.lib().pna_tower_layer_f32(ctypes.byref(g), _lib.stream_ptr(dev))
     _lib.check(rc, "pna_tower_layer_f32")
     return out
+
+
+# ---- bf16 inference of PNASimpleLayer (pna_bf16.hip) -------------------------------------------------------------------------
+_BF16_AGGS = ("mean", "sum", "max", "min", "std", "var")
+
+
+def segreduce_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
+                   block_stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                   heavy: Optional[HeavySchedule] = None, workspace=None):
+    """bf16 (V, A * bs) aggregate (bs = block_stride, default F) of the bf16 source rows x (any pitch >= F) through
+    pna_segreduce_fwd_bf16: fp32 statistics rounded to bf16 once, identity scaler.  The returned tensor's pitch is a multiple of
+    8 elements.  block_stride a multiple of 8: the columns [F, round8(F)) of every block hold zeros."""
+    V = rowptr.numel() - 1
+    A = len(aggregators)
+    bs = F if block_stride is None else int(block_stride)
+    dev = x.device
+    if out is None:
+        width = (A - 1) * bs + F
+        out = torch.empty(V, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)[:, :width]
+    a = _lib.PnaSegreduceBf16Args()
+    a.rowptr = _lib.dev_ptr(rowptr, torch.int32, "rowptr")
+    a.col = _lib.dev_ptr(col, torch.int32, "col")
+    a.V, a.F = V, F
+    a.x, a.ldx = _lib.dev_ptr(x, torch.bfloat16, "x"), _ld(x)
+    if F % 8 and x.shape[0] > 0:
+        # the 16-byte gather reads up to round8(F) columns of every row: allowed when the storage holds them
+        last = x.storage_offset() + (x.shape[0] - 1) * _ld(x) + (F + 7) // 8 * 8
+        a.x_tail_readable = int(last * x.element_size() <= x.untyped_storage().nbytes())
+    a.n_aggr = A
+    for i, name in enumerate(aggregators):
+        if name not in _BF16_AGGS:
+            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
+        a.aggr[i] = _lib.AGG_CODES[name]
+    a.out, a.ldo, a.block_stride = _lib.dev_ptr(out, torch.bfloat16, "out"), _ld(out), bs
+    keep = None
+    if heavy is not None and heavy.n_heavy > 0:
+        a.heavy_threshold, a.seg_len, a.n_heavy, a.n_seg = heavy.threshold, heavy.seg_len, heavy.n_heavy, heavy.n_seg
+        a.heavy_rows = _lib.dev_ptr(heavy.heavy_rows, torch.int32, "heavy_rows")
+        a.heavy_segptr = _lib.dev_ptr(heavy.heavy_segptr, torch.int32, "heavy_segptr")
+        a.seg_heavy = _lib.dev_ptr(heavy.seg_heavy, torch.int32, "seg_heavy")
+        nbytes = _lib.lib().pna_segreduce_bf16_partials_bytes(heavy.n_seg, F)
+        keep = workspace(nbytes) if workspace is not None else torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        a.partials = _lib.dev_ptr(keep, torch.float32, "partials")
+    rc = _lib.lib().pna_segreduce_fwd_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
+    _lib.check(rc, "pna_segreduce_fwd_bf16")
+    if keep is not None and workspace is None:
+        keep.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def pack_posttrans_weight_bf16(weight: torch.Tensor, n_scaler: int, A: int, F: int, Fb: int):
+    """bf16 image (n_scaler, 16 T, round32(A * Fb)) of a reference-layout posttrans weight (N, n_scaler * A * F) for an aggregate
+    whose A blocks sit Fb >= F columns apart (include/pna_amd.h, pna_posttrans_bf16_args.w_img): zero columns at the padding of
+    every block, zero rows beyond N.  Cached on the weight tensor like pack_posttrans_weight."""
+    key = (weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), weight.stride(0), n_scaler, A, F, Fb)
+    hit = getattr(weight, "_pna_amd_pack_bf16", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    N = weight.shape[0]
+    if weight.dtype != torch.bfloat16 or weight.shape[1] != n_scaler * A * F:
+        raise ValueError(f"posttrans weight must be bf16 (N, {n_scaler * A * F}), got {weight.dtype} {tuple(weight.shape)}")
+    T = _lib.lib().pna_posttrans_bf16_tiles(N)
+    if T < 0:
+        raise ValueError(f"pna_posttrans_bf16: out_dim {N} outside 1..128")
+    K = A * Fb
+    Kp = (K + 31) // 32 * 32
+    with torch.no_grad():
+        img = torch.zeros(n_scaler, 16 * T, Kp, dtype=torch.bfloat16, device=weight.device)
+        w = weight.reshape(N, n_scaler, A, F).permute(1, 0, 2, 3)                      # (S, N, A, F)
+        img[:, :N, :K].view(n_scaler, N, A, Fb)[..., :F] = w
+    try:
+        weight._pna_amd_pack_bf16 = (key, img)
+    except AttributeError:
+        pass
+    return img
+
+
+def posttrans_bf16(agg: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_scales: Sequence[Optional[torch.Tensor]],
+                   bias: Optional[torch.Tensor] = None, *, epilogue: bool = False, relu: bool = False,
+                   col_scale: Optional[torch.Tensor] = None, col_shift: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """y = [residual +] [relu](( sum_s row_scales[s] * (W_s agg[:, :K]) + bias ) [* col_scale + col_shift]) through pna_posttrans_bf16
+    (bf16 operands, fp32 accumulation, bf16 result): see include/pna_amd.h.  w_img from pack_posttrans_weight_bf16; the tail after
+    the bias applies only with epilogue=True."""
+    M = agg.shape[0]
+    S = len(row_scales)
+    dev = agg.device
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+    a = _lib.PnaPosttransBf16Args()
+    a.a, a.lda, a.M, a.K, a.N, a.n_scaler = _lib.dev_ptr(agg, torch.bfloat16, "agg"), _ld(agg), M, K, N, S
+    for i, rs in enumerate(row_scales):
+        if rs is not None:
+            if rs.numel() != M:
+                raise ValueError("row scale must have one entry per row")
+            a.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+    a.w_img = _lib.dev_ptr(w_img, torch.bfloat16, "w_img")
+    a.bias = _lib.dev_ptr(bias, torch.bfloat16, "bias")
+    a.epilogue, a.relu = int(epilogue), int(relu)
+    a.col_scale = _lib.dev_ptr(col_scale, torch.float32, "col_scale")
+    a.col_shift = _lib.dev_ptr(col_shift, torch.float32, "col_shift")
+    if residual is not None:
+        a.residual, a.ld_res = _lib.dev_ptr(residual, torch.bfloat16, "residual"), _ld(residual)
+    a.y, a.ldy = _lib.dev_ptr(out, torch.bfloat16, "y"), _ld(out)
+    rc = _lib.lib().pna_posttrans_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
+    _lib.check(rc, "pna_posttrans_bf16")
+    return out
