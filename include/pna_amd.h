@@ -13,7 +13,7 @@
  *   - stream-ordered and asynchronous: nothing here synchronises the device;
  *   - re-entrant: no global mutable state except the per-thread last-error string;
  *   - return value 0 = success, negative = error (see PNA_E_*); pna_last_error() gives the text;
- *   - all data is fp32 and all arithmetic is fp32, except the two bf16 entry points of ABI 22 (bf16 data, fp32 accumulation) (pna_posttrans_x3_f32 evaluates each fp32 product as six exact
+ *   - all data is fp32 and all arithmetic is fp32, except the bf16 entry points of ABI 22 / 23 (bf16 data, fp32 accumulation) (pna_posttrans_x3_f32 evaluates each fp32 product as six exact
  *     bf16 partial products accumulated in fp32 -- fp32-level accuracy, see there); indices are int32; row strides
  *     (ld*) are in floats.
  */
@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 22 /* 22: + pna_segreduce_fwd_bf16 / pna_segreduce_bf16_partials_bytes, pna_posttrans_bf16 / pna_posttrans_bf16_tiles
+#define PNA_ABI_VERSION 23 /* 23: + pna_gather_bf16 / pna_contract_bf16 / pna_contract_bf16_tiles (bf16 inference of PNALayer / PNATower and the nets;
+                                  pna_gather_bf16_args, pna_contract_bf16_args).
+                              22: + pna_segreduce_fwd_bf16 / pna_segreduce_bf16_partials_bytes, pna_posttrans_bf16 / pna_posttrans_bf16_tiles
                                   (bf16 inference of PNASimpleLayer; pna_segreduce_bf16_args, pna_posttrans_bf16_args).
                               21: the GUARDED fp16 x 2 contraction of the one-kernel layer (round 6): + pna_fused_degree_args.{w_img_x3,
                                   image_stride_x3, guard_ws, guard_ws_bytes, arith}, PNA_FD_ARITH_*, pna_fused_image_bytes, pna_fused_pack_f32,
@@ -1052,6 +1054,103 @@ typedef struct pna_posttrans_bf16_args {
 int pna_posttrans_bf16(const pna_posttrans_bf16_args* args, pna_stream_t stream);
 /* Column tiles of 16 the weight image of an N-column contraction has (2, 4, 5 or 8); -1 when N is outside 1..128. */
 int pna_posttrans_bf16_tiles(int32_t N);
+
+/* ---- bf16 inference of PNALayer / PNATower (ABI 23) ------------------------------------------------------------------------------
+ *
+ * Two entry points for the tower layer on bf16 features and parameters (pna_amd.functional.tower_layer_bf16); with the node-level
+ * projections of the factorised 1-layer pretrans they replace PNATower.forward and PNALayer.forward, models/dgl/pna_layer.py:35-76,
+ * :130-145.  `void*` data pointers hold bf16 values; row strides (ld*) are in ELEMENTS of the pointed-to type.
+ *
+ * pna_gather_bf16 -- replaces pretrans_edges + reduce_func of PNATower, models/dgl/pna_layer.py:35-50 (update_all, :64), for a
+ * pretrans that is one Linear, with the aggregators of models/dgl/aggregators.py:6-26,50-51:
+ *     m(k)  = x[col[k]][f] + dst_term[v][f] + edge_term(k)[f]                 fp32, in registers, never rounded or stored
+ *     out[v * ldo + a * block_stride + f] = bf16( aggr[a]( m(k) : k in [rowptr[v], rowptr[v+1]) ) )
+ * x = W_a h, dst_term = W_b h + b (one row per destination, added once per edge; NULL = no term), edge_term(k) = row
+ * edge_type[k] of edge_rows (W_e ef of every edge type) or, with edge_type NULL, row k of edge_rows (W_e ef of CSR edge k);
+ * edge_rows NULL = no term.  All towers of a layer go through one call as rows of width F = towers * in_dim (the aggregators
+ * are per feature).  Statistics, hub rows, rounding, empty rows (0) and the layout of `out`: exactly pna_segreduce_fwd_bf16.
+ * Rows are read in 16-byte pieces when x, dst_term and edge_rows are all 16-byte aligned with pitches that are multiples of 8
+ * and F is a multiple of 8 or tails_readable = 1 (columns [F, round8(F)) of every row of the three may be read; their values
+ * are ignored); in 2-byte pieces otherwise.  F <= 512. */
+typedef struct pna_gather_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_gather_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* rowptr;   /* [V+1] */
+  const int32_t* col;      /* [E] source row of each CSR edge */
+  int32_t V;
+  int32_t F;
+  const void* x;           /* bf16 (x_rows, ldx): the source-side term */
+  int64_t ldx;
+  const void* dst_term;    /* bf16 (V, ld_dst), nullable */
+  int64_t ld_dst;
+  const void* edge_rows;   /* bf16 (n_types or E, ld_edge), nullable */
+  int64_t ld_edge;
+  const int32_t* edge_type; /* [E] in CSR order, values in [0, n_edge_rows); NULL = edge_rows has one row per CSR edge */
+  int32_t n_edge_rows;     /* rows of edge_rows */
+  int32_t tails_readable;  /* 1 = columns [F, round8(F)) of every row of x, dst_term and edge_rows may be read */
+  int32_t n_aggr;
+  int32_t block_stride;    /* columns between aggregator blocks (>= F); 0 = F */
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_VAR */
+  void* out;               /* bf16 (V, ldo), 16-byte aligned, ldo a multiple of 8 and >= (n_aggr - 1) * block_stride + F */
+  int64_t ldo;
+  int32_t heavy_threshold; /* the heavy-row schedule of pna_segreduce_bf16_args */
+  int32_t seg_len;
+  int32_t n_heavy;
+  int32_t n_seg;
+  const int32_t* heavy_rows;   /* [n_heavy] */
+  const int32_t* heavy_segptr; /* [n_heavy+1] */
+  const int32_t* seg_heavy;    /* [n_seg] */
+  float* partials;             /* pna_segreduce_bf16_partials_bytes(n_seg, F) bytes */
+} pna_gather_bf16_args;
+
+int pna_gather_bf16(const pna_gather_bf16_args* args, pna_stream_t stream);
+
+/* pna_contract_bf16 -- one contraction for the three dense stages of the bf16 tower layer: the node-level projections of the
+ * pretrans (models/dgl/pna_layer.py:35-40 -- no scaler, no epilogue), the posttrans Linear of all towers with graph norm and
+ * eval-mode BatchNorm (:65-74) and the mixing network (:128, :141-144):
+ *     z[v] = sum_s row_scale[s][v] * (W_s . a[v]) + W_h . h_self[v] + bias
+ *     y[v] = bf16( residual[v] + act( (z[v] * row_post[v]) * col_scale + col_shift ) ),   act(t) = t < 0 ? slope * t : t
+ * Single bf16 x bf16 products on v_mfma_f32_16x16x32_bf16, fp32 accumulators per scaler block; the fp32 row scalers multiply the fp32
+ * sums; y is rounded once.  h_self (bf16 (M, Kh), nullable) is the unscaled operand: when row_scale[0] is NULL (an identity
+ * scaler first) it shares that block's accumulators, else it gets a set of its own.  a: (M, K); the 16-byte loads need a 16-byte
+ * aligned base, lda a multiple of 8 and K a multiple of 8 (likewise h_self / ld_self / Kh), other operands are read in 2-byte pieces
+ * with columns >= K taken as 0.  w_img: bf16 (n_scaler, R, round32(K)) row-major with R = 16 T ceil(N / (16 T)) rows,
+ * T = pna_contract_bf16_tiles(N); element [s][n][k] = W_s[n][k], zero elsewhere.  w_self: bf16 (R, round32(Kh)) likewise.
+ * bias (bf16 [N]), row_scale[s] (fp32 [M]; NULL = 1), row_post (fp32 [M]), col_scale / col_shift (fp32 [N], both or neither) and
+ * residual (bf16 (M, ld_res)) are optional; slope 1 = no activation, 0 = ReLU, 0.01 = LeakyReLU.  n_scaler <= 3; N <= 128 with more
+ * than one scaler block or with h_self, N <= 4096 otherwise (column slabs of 128). */
+typedef struct pna_contract_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_contract_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const void* a;           /* bf16 (M, lda) */
+  int64_t lda;
+  int32_t M;
+  int32_t K;
+  int32_t N;
+  int32_t n_scaler;
+  const float* row_scale[PNA_MAX_SCALER];
+  const void* w_img;       /* bf16 image, 16-byte aligned */
+  const void* h_self;      /* bf16 (M, ld_self), nullable */
+  int64_t ld_self;
+  int32_t Kh;
+  int32_t _pad0;
+  const void* w_self;      /* bf16 image, 16-byte aligned; required with h_self */
+  const void* bias;        /* bf16 [N], nullable */
+  const float* row_post;   /* nullable [M] */
+  const float* col_scale;  /* nullable [N] */
+  const float* col_shift;  /* nullable [N] */
+  float slope;             /* 1 = none, 0 = ReLU, 0.01 = LeakyReLU */
+  int32_t _pad1;
+  const void* residual;    /* bf16 (M, ld_res), nullable */
+  int64_t ld_res;
+  void* y;                 /* bf16 (M, ldy) */
+  int64_t ldy;
+} pna_contract_bf16_args;
+
+int pna_contract_bf16(const pna_contract_bf16_args* args, pna_stream_t stream);
+/* Column tiles of 16 per workgroup the weight images of an N-column contraction are laid out for (2, 4, 5 or 8; 8 for N > 128);
+ * -1 when N is outside 1..4096. */
+int pna_contract_bf16_tiles(int32_t N);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

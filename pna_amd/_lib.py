@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PNA_AMD_LIB_PATH: another build of the same ABI -- tools/build_variant.sh, the -DPNA_AMD_EXPERIMENTS build -- for same-box A/B runs)
 LIB_PATH = os.environ.get("PNA_AMD_LIB_PATH") or os.path.join(_HERE, "lib", "libpna_amd.so")
 
-PNA_ABI_VERSION = 22
+PNA_ABI_VERSION = 23
 PNA_MAX_AGGR = 8
 PNA_MAX_SCALER = 8
 
@@ -238,6 +238,33 @@ class PnaPosttransBf16Args(_Args):
     ]
 
 
+class PnaGatherBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("V", ctypes.c_int32), ("F", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("dst_term", ctypes.c_void_p), ("ld_dst", ctypes.c_int64),
+        ("edge_rows", ctypes.c_void_p), ("ld_edge", ctypes.c_int64), ("edge_type", ctypes.c_void_p),
+        ("n_edge_rows", ctypes.c_int32), ("tails_readable", ctypes.c_int32), ("n_aggr", ctypes.c_int32), ("block_stride", ctypes.c_int32),
+        ("aggr", ctypes.c_int32 * PNA_MAX_AGGR),
+        ("out", ctypes.c_void_p), ("ldo", ctypes.c_int64),
+        ("heavy_threshold", ctypes.c_int32), ("seg_len", ctypes.c_int32), ("n_heavy", ctypes.c_int32), ("n_seg", ctypes.c_int32),
+        ("heavy_rows", ctypes.c_void_p), ("heavy_segptr", ctypes.c_void_p), ("seg_heavy", ctypes.c_void_p), ("partials", ctypes.c_void_p),
+    ]
+
+
+class PnaContractBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("a", ctypes.c_void_p), ("lda", ctypes.c_int64), ("M", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("N", ctypes.c_int32), ("n_scaler", ctypes.c_int32),
+        ("row_scale", ctypes.c_void_p * PNA_MAX_SCALER),
+        ("w_img", ctypes.c_void_p), ("h_self", ctypes.c_void_p), ("ld_self", ctypes.c_int64), ("Kh", ctypes.c_int32),
+        ("_pad0", ctypes.c_int32), ("w_self", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("row_post", ctypes.c_void_p),
+        ("col_scale", ctypes.c_void_p), ("col_shift", ctypes.c_void_p), ("slope", ctypes.c_float), ("_pad1", ctypes.c_int32),
+        ("residual", ctypes.c_void_p), ("ld_res", ctypes.c_int64), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -360,6 +387,12 @@ def lib():
         L.pna_posttrans_bf16.restype = ctypes.c_int
         L.pna_posttrans_bf16_tiles.argtypes = [ctypes.c_int32]
         L.pna_posttrans_bf16_tiles.restype = ctypes.c_int
+        L.pna_gather_bf16.argtypes = [ctypes.POINTER(PnaGatherBf16Args), ctypes.c_void_p]
+        L.pna_gather_bf16.restype = ctypes.c_int
+        L.pna_contract_bf16.argtypes = [ctypes.POINTER(PnaContractBf16Args), ctypes.c_void_p]
+        L.pna_contract_bf16.restype = ctypes.c_int
+        L.pna_contract_bf16_tiles.argtypes = [ctypes.c_int32]
+        L.pna_contract_bf16_tiles.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

@@ -86,6 +86,31 @@ def _row_scales(graph, scalers, avg_d, device):
     return [{"identity": None, "amplification": amp, "attenuation": att}[s] for s in scalers]
 
 
+def _bf16_towers_path(module, towers, mix, graph, h, e, out_dim):
+    """Whether a PNATower / PNALayer call is served by the bf16 inference kernels (functional.towers_bf16 / tower_layer_bf16): the
+    predicate of PNASimpleLayer._bf16_path -- bf16 features, every floating-point parameter and buffer bf16, inference (eval mode, no
+    gradient required), features on the GPU, exactly a Graph -- and: a 1-layer (affine) pretrans, bf16 edge features on the GPU
+    when the towers read them, at most 128 output columns, aggregators and scalers the kernels know (mean / sum / max / min / std /
+    var, at most 3 scalers), a mixing network that is Linear + (Leaky)ReLU, and no stream capture in progress.  Every other call
+    takes the fp32 code and fails there as before."""
+    if h.dtype != torch.bfloat16 or module.training or not h.is_cuda or type(graph) is not Graph:
+        return False
+    if any(t.dtype != torch.bfloat16 for t in list(module.parameters()) + list(module.buffers()) if t.is_floating_point()):
+        return False
+    t0 = towers[0]
+    if any(t.training or not t.pretrans.is_affine for t in towers) or out_dim > 128:
+        return False
+    if t0.edge_features and (e is None or e.dtype != torch.bfloat16 or not e.is_cuda or e.requires_grad):
+        return False
+    if any(a not in ops._BF16_AGGS for a in t0.aggregators) or len(t0.scalers) > 3:
+        return False
+    if mix is not None and (mix.b_norm is not None or not (mix.activation is None or isinstance(mix.activation, (nn.LeakyReLU, nn.ReLU)))):
+        return False
+    if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in module.parameters())):
+        return False
+    return not (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing())
+
+
 class PNATower(nn.Module):
     def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, avg_d,
                  pretrans_layers, posttrans_layers, edge_features, edge_dim):
@@ -117,8 +142,14 @@ class PNATower(nn.Module):
             y = self.batchnorm_h(y)
         return F.dropout(y, self.dropout, training=self.training)
 
+    def _bf16_path(self, graph, h, e=None):
+        return _bf16_towers_path(self, [self], None, graph, h, e, self.out_dim)
+
     def forward(self, g, h, e, snorm_n):
-        return _towers_forward([self], as_graph(g), h, e, snorm_n, divide_input=False)
+        graph = as_graph(g)
+        if self._bf16_path(graph, h, e):
+            return PF.towers_bf16([self], graph, h, e, snorm_n, divide_input=False).contiguous()
+        return _towers_forward([self], graph, h, e, snorm_n, divide_input=False)
 
 
 def _projection_cache(towers, Fi):
@@ -353,8 +384,14 @@ class PNALayer(nn.Module):
             return False
         return not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters())))
 
+    def _bf16_path(self, graph, h, e=None):
+        """Whether this call is served by the bf16 inference kernels: see _bf16_towers_path."""
+        return _bf16_towers_path(self, list(self.towers), self.mixing_network, graph, h, e, self.out_dim)
+
     def forward(self, g, h, e, snorm_n):
         graph = as_graph(g)
+        if self._bf16_path(graph, h, e):
+            return PF.tower_layer_bf16(self, graph, h, e, snorm_n)
         if self._small_batch_path(graph, h):
             t0 = self.towers[0]
             etab = None

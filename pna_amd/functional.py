@@ -1392,3 +1392,135 @@ def simple_layer_bf16(layer, graph, h):
     if layer.residual:
         y = h + y
     return y
+
+
+def _tensor_key(ts):
+    return tuple((id(t), t._version, t.data_ptr(), str(t.device), t.dtype, tuple(t.shape)) for t in ts)
+
+
+def _tower_images_bf16(towers, divide_input):
+    """The weight images of the bf16 tower layer (ops.contract_image_bf16), built once per version of EVERY tensor they are made
+    from -- the pretrans and first posttrans Linear and the BatchNorm tensors of every tower -- and cached on the first tower.
+    With T towers of input width Fi, output width No, P = round8(T * Fi), A aggregators and S scalers:
+      proj  (1, 2P, Kin)   rows [t Fi, (t+1) Fi): W_a of tower t, rows P + the same: W_b; bias [0 | b]   (x_src | x_dst, 16-byte halves)
+      edge  (1, P, ed)     rows [t Fi, (t+1) Fi): W_e of tower t
+      post  (S, T No, A P) row t No + n, column a P + t Fi + f of block s: the posttrans weight of tower t on aggregator a, scaler s;
+                           zero where a tower does not read a column.  Blocks are ordered identity scaler first (`perm`)
+      self  (1, T No, Kin) the posttrans weight on the tower's own features
+    Kin = T Fi with divide_input (tower t reads the input slice [t Fi, (t+1) Fi): block-diagonal), else Fi."""
+    t0 = towers[0]
+    pre = [t.pretrans.fully_connected[0].linear for t in towers]
+    post = [t.posttrans.fully_connected[0].linear for t in towers]
+    bns = [t.batchnorm_h for t in towers] if t0.batch_norm and t0.posttrans.is_affine else []
+    ts = [p for l in pre + post for p in (l.weight, l.bias)]
+    ts += [x for bn in bns for x in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if x is not None]
+    key = (_tensor_key(ts), divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns))
+    hit = t0.__dict__.get("_pna_amd_bf16_images")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    T, Fi, ed, No = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
+    A, S = len(t0.aggregators), len(t0.scalers)
+    P = (T * Fi + 7) // 8 * 8
+    Kin = T * Fi if divide_input else Fi
+    dev, bf = pre[0].weight.device, torch.bfloat16
+    perm = sorted(range(S), key=lambda s: t0.scalers[s] != "identity")           # stable: an identity scaler first
+    with torch.no_grad():
+        proj = torch.zeros(1, 2 * P, Kin, dtype=bf, device=dev)
+        pbias = torch.zeros(2 * P, dtype=bf, device=dev)
+        edge = torch.zeros(1, P, max(ed, 1), dtype=bf, device=dev)
+        wpost = torch.zeros(S, T * No, A * P, dtype=bf, device=dev)
+        wself = torch.zeros(1, T * No, Kin, dtype=bf, device=dev)
+        for t in range(T):
+            r = slice(t * Fi, (t + 1) * Fi)
+            c = r if divide_input else slice(0, Fi)
+            W = pre[t].weight
+            proj[0, r, c] = W[:, :Fi]
+            proj[0, P + t * Fi:P + (t + 1) * Fi, c] = W[:, Fi:2 * Fi]
+            pbias[P + t * Fi:P + (t + 1) * Fi] = pre[t].bias
+            if ed:
+                edge[0, r, :ed] = W[:, 2 * Fi:]
+            Wp = post[t].weight                                                    # (No, (S A + 1) Fi): [h | scaler-major aggregates]
+            o = slice(t * No, (t + 1) * No)
+            wself[0, o, c] = Wp[:, :Fi]
+            blocks = Wp[:, Fi:].reshape(No, S, A, Fi)
+            for j, s in enumerate(perm):
+                wpost[j, o].view(No, A, P)[:, :, r] = blocks[:, s]
+        res = {
+            "P": P, "perm": perm,
+            "proj": ops.contract_image_bf16(proj), "proj_bias": pbias,
+            "edge": ops.contract_image_bf16(edge) if ed else None,
+            "post": ops.contract_image_bf16(wpost), "self": ops.contract_image_bf16(wself),
+            "post_bias": torch.cat([l.bias for l in post]).contiguous(),
+            "cs": None, "ct": None,
+        }
+        if bns:
+            folds = [_fold_batchnorm_f32(bn) for bn in bns]
+            res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
+            res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
+    t0.__dict__["_pna_amd_bf16_images"] = (key, res, ts)                           # (ts: the addresses in the key stay taken)
+    return res
+
+
+def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
+    """The concatenated tower outputs h_cat (V, T * out_dim per tower) of PNATower.forward, models/dgl/pna_layer.py:55-76, in inference
+    on bf16 features and parameters with a 1-layer pretrans.  Four launches: the node-level projections x_src = W_a h,
+    x_dst = W_b h + b of all towers (pna_contract_bf16, rounded to bf16), [the edge term W_e ef per edge type or per edge,] the
+    gather of x_src[u] + x_dst[v] + x_edge in fp32 with fp32 statistics (pna_gather_bf16, one row of width T * Fi for all towers)
+    and the posttrans of all towers against one block-structured weight image with the degree scalers, bias, graph norm and the
+    folded BatchNorm in its epilogue.  A deeper posttrans MLP runs its first Linear on the kernel and the rest -- later layers, graph
+    norm, BatchNorm -- as each tower's own bf16 torch ops.  The result's pitch is a multiple of 8 elements."""
+    from .dgl.pna_layer import _row_scales
+    t0 = towers[0]
+    T, Fi, ed, No = len(towers), t0.in_dim, t0.edge_dim, t0.out_dim
+    Kin = T * Fi if divide_input else Fi
+    if h.dim() != 2 or h.shape[1] != Kin:
+        raise ValueError(f"expected features of shape (V, {Kin}), got {tuple(h.shape)}")
+    if h.stride(-1) != 1:
+        h = h.contiguous()
+    V = h.shape[0]
+    im = _tower_images_bf16(towers, divide_input)
+    P, csr = im["P"], graph.csr
+    x_cat = ops.contract_bf16(h, Kin, im["proj"], 2 * P, (None,), im["proj_bias"])
+    edge_rows = edge_type = None
+    if t0.edge_features:
+        if e is None:
+            raise ValueError("edge_features=True but no edge features were given")
+        etab = graph.edge_type_table(e)                  # an embedding of <= 4 edge types: W_e ef once per type
+        if etab is not None:
+            edge_type, ef = etab
+        else:
+            ef = e[csr.eid.long()]                       # per-edge features in CSR (dst-sorted) order
+        edge_rows = ops.contract_bf16(ef.contiguous(), ed, im["edge"], P)
+    agg = ops.gather_bf16(csr.rowptr, csr.col, x_cat[:, :T * Fi], T * Fi, t0.aggregators, dst_term=x_cat[:, P:P + T * Fi],
+                          edge_rows=edge_rows, edge_type=edge_type, block_stride=P, heavy=graph.heavy_schedule(),
+                          workspace=graph.workspace)
+    scales = _row_scales(graph, t0.scalers, t0.avg_d, h.device)
+    scales = [scales[s] for s in im["perm"]]
+    A = len(t0.aggregators)
+    if t0.posttrans.is_affine:
+        post = snorm_n.reshape(-1).float() if t0.graph_norm else None
+        return ops.contract_bf16(agg, A * P, im["post"], T * No, scales, im["post_bias"], h_self=h, w_self=im["self"],
+                                 row_post=post, col_scale=im["cs"], col_shift=im["ct"])
+    y = ops.contract_bf16(agg, A * P, im["post"], T * No, scales, im["post_bias"], h_self=h, w_self=im["self"])
+    sn = snorm_n.to(torch.bfloat16)
+    outs = [tower.tail(y[:, t * No:(t + 1) * No], sn) for t, tower in enumerate(towers)]
+    return torch.cat(outs, dim=1) if T > 1 else outs[0]
+
+
+def tower_layer_bf16(layer, graph, h, e, snorm_n):
+    """PNALayer.forward (models/dgl/pna_layer.py:130-145) in inference on bf16 features and parameters: towers_bf16, then the mixing
+    network -- Linear, LeakyReLU and the residual -- as one more pna_contract_bf16 launch."""
+    h_cat = towers_bf16(list(layer.towers), graph, h, e, snorm_n, layer.divide_input)
+    mix = layer.mixing_network
+    w = mix.linear.weight
+    key = _tensor_key([w])
+    hit = layer.__dict__.get("_pna_amd_bf16_mix")
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = (key, ops.contract_image_bf16(w.unsqueeze(0)), w)
+        layer.__dict__["_pna_amd_bf16_mix"] = hit
+    N = layer.out_dim
+    out = torch.empty(h.shape[0], N, dtype=torch.bfloat16, device=h.device)
+    slope = 1.0 if mix.activation is None else 0.0 if isinstance(mix.activation, torch.nn.ReLU) else mix.activation.negative_slope
+    return ops.contract_bf16(h_cat, N, hit[1], N, (None,), mix.linear.bias, slope=slope,
+                             residual=(h if h.stride(-1) == 1 else h.contiguous()) if layer.residual else None, out=out)

@@ -58,6 +58,12 @@ def readout_nodes(g, h, op):
         owner = torch.repeat_interleave(torch.arange(sizes.numel(), device=h.device), sizes)
         rg = Graph(torch.arange(graph.num_nodes, device=h.device), owner, sizes.numel())   # node v -> its graph
         graph._heavy[key] = rg
+    if h.dtype == torch.bfloat16:
+        # bf16 rows (the bf16 inference path of the layers): fp32 statistics rounded once, pna_segreduce_fwd_bf16
+        if h.stride(-1) != 1:
+            h = h.contiguous()
+        csr = rg.csr
+        return PF.ops.segreduce_bf16(csr.rowptr, csr.col, h, h.shape[1], [op], heavy=rg.heavy_schedule(), workspace=rg.workspace)
     return PF.aggregate(rg, h, h.shape[1], [op], edge_resident=True)
 
 

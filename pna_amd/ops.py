@@ -746,3 +746,140 @@ def posttrans_bf16(agg: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_s
     rc = _lib.lib().pna_posttrans_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
     _lib.check(rc, "pna_posttrans_bf16")
     return out
+
+
+# ---- bf16 inference of PNALayer / PNATower (pna_bf16_tower.hip) --------------------------------------------------------------
+def _tail_readable(t: torch.Tensor, F: int) -> bool:
+    """Whether the columns [F, round8(F)) of every row of the 2-D view t lie inside its storage (16-byte row pieces may read them)."""
+    if F % 8 == 0 or t.shape[0] == 0:
+        return True
+    last = t.storage_offset() + (t.shape[0] - 1) * _ld(t) + (F + 7) // 8 * 8
+    return last * t.element_size() <= t.untyped_storage().nbytes()
+
+
+def gather_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
+                dst_term: Optional[torch.Tensor] = None, edge_rows: Optional[torch.Tensor] = None,
+                edge_type: Optional[torch.Tensor] = None, block_stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                heavy: Optional[HeavySchedule] = None, workspace=None):
+    """segreduce_bf16 over the messages x[col[k]] + dst_term[v] + edge term, formed in fp32 and never stored (pna_gather_bf16).
+    edge term of CSR edge k: edge_rows[edge_type[k]] (a table of <= a few rows; edge_type int32 [E] in CSR order) or edge_rows[k]
+    when edge_type is None.  The result is (V, A * bs) when bs is a multiple of 8 (the padding columns of every block hold zeros: the
+    operand of contract_bf16), else (V, (A - 1) * bs + F)."""
+    V = rowptr.numel() - 1
+    A = len(aggregators)
+    bs = F if block_stride is None else int(block_stride)
+    dev = x.device
+    if out is None:
+        width = A * bs if bs % 8 == 0 else (A - 1) * bs + F
+        out = torch.empty(V, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)[:, :width]
+    a = _lib.PnaGatherBf16Args()
+    a.rowptr = _lib.dev_ptr(rowptr, torch.int32, "rowptr")
+    a.col = _lib.dev_ptr(col, torch.int32, "col")
+    a.V, a.F = V, F
+    a.x, a.ldx = _lib.dev_ptr(x, torch.bfloat16, "x"), _ld(x)
+    tails = _tail_readable(x, F)
+    if dst_term is not None:
+        if dst_term.shape[0] != V or dst_term.shape[1] < F:
+            raise ValueError(f"dst_term must be (V, >= {F}), got {tuple(dst_term.shape)}")
+        a.dst_term, a.ld_dst = _lib.dev_ptr(dst_term, torch.bfloat16, "dst_term"), _ld(dst_term)
+        tails = tails and _tail_readable(dst_term, F)
+    if edge_rows is not None:
+        if edge_rows.shape[1] < F or (edge_type is None and edge_rows.shape[0] != col.numel()):
+            raise ValueError(f"edge_rows must be (E or n_types, >= {F}), got {tuple(edge_rows.shape)}")
+        a.edge_rows, a.ld_edge = _lib.dev_ptr(edge_rows, torch.bfloat16, "edge_rows"), _ld(edge_rows)
+        a.n_edge_rows = edge_rows.shape[0]
+        tails = tails and _tail_readable(edge_rows, F)
+        if edge_type is not None:
+            if edge_type.numel() != col.numel():
+                raise ValueError("edge_type must have one entry per edge")
+            a.edge_type = _lib.dev_ptr(edge_type, torch.int32, "edge_type")
+    elif edge_type is not None:
+        raise ValueError("edge_type without edge_rows")
+    a.tails_readable = int(tails)
+    a.n_aggr = A
+    for i, name in enumerate(aggregators):
+        if name not in _BF16_AGGS:
+            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
+        a.aggr[i] = _lib.AGG_CODES[name]
+    a.out, a.ldo, a.block_stride = _lib.dev_ptr(out, torch.bfloat16, "out"), _ld(out), bs
+    keep = None
+    if heavy is not None and heavy.n_heavy > 0:
+        a.heavy_threshold, a.seg_len, a.n_heavy, a.n_seg = heavy.threshold, heavy.seg_len, heavy.n_heavy, heavy.n_seg
+        a.heavy_rows = _lib.dev_ptr(heavy.heavy_rows, torch.int32, "heavy_rows")
+        a.heavy_segptr = _lib.dev_ptr(heavy.heavy_segptr, torch.int32, "heavy_segptr")
+        a.seg_heavy = _lib.dev_ptr(heavy.seg_heavy, torch.int32, "seg_heavy")
+        nbytes = _lib.lib().pna_segreduce_bf16_partials_bytes(heavy.n_seg, F)
+        keep = workspace(nbytes) if workspace is not None else torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        a.partials = _lib.dev_ptr(keep, torch.float32, "partials")
+    rc = _lib.lib().pna_gather_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
+    _lib.check(rc, "pna_gather_bf16")
+    if keep is not None and workspace is None:
+        keep.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def contract_image_bf16(blocks: torch.Tensor):
+    """bf16 weight image of pna_contract_bf16 from `blocks` (n_blocks, N, K) (dense, zeros where an output does not read a column):
+    (n_blocks, R, round32(K)) with R = N rounded up to the kernel's column slab (include/pna_amd.h, pna_contract_bf16_args.w_img)."""
+    S, N, K = blocks.shape
+    T = _lib.lib().pna_contract_bf16_tiles(N)
+    if T < 0:
+        raise ValueError(f"pna_contract_bf16: {N} output columns outside 1..4096")
+    R = (N + 16 * T - 1) // (16 * T) * (16 * T)
+    img = torch.zeros(S, R, (K + 31) // 32 * 32, dtype=torch.bfloat16, device=blocks.device)
+    img[:, :N, :K] = blocks
+    return img
+
+
+def contract_bf16(a: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_scales: Sequence[Optional[torch.Tensor]] = (None,),
+                  bias: Optional[torch.Tensor] = None, *, h_self: Optional[torch.Tensor] = None, w_self: Optional[torch.Tensor] = None,
+                  row_post: Optional[torch.Tensor] = None, col_scale: Optional[torch.Tensor] = None,
+                  col_shift: Optional[torch.Tensor] = None, slope: float = 1.0, residual: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None):
+    """y = [residual +] act((( sum_s row_scales[s] * (W_s a[:, :K]) + W_h h_self + bias ) * row_post) [* col_scale + col_shift]) through
+    pna_contract_bf16 (bf16 operands, fp32 accumulation, one rounding): see include/pna_amd.h.  w_img / w_self from
+    contract_image_bf16; act(t) = t if t >= 0 else slope * t.  The result's pitch is a multiple of 8 elements."""
+    M = a.shape[0]
+    S = len(row_scales)
+    dev = a.device
+    if out is None:
+        out = torch.empty(M, (N + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)[:, :N]
+    T = _lib.lib().pna_contract_bf16_tiles(N)
+    if T < 0:
+        raise ValueError(f"pna_contract_bf16: {N} output columns outside 1..4096")
+    R = (N + 16 * T - 1) // (16 * T) * (16 * T)
+    if a.shape[1] < K or tuple(w_img.shape) != (S, R, (K + 31) // 32 * 32) or not w_img.is_contiguous():
+        raise ValueError(f"pna_contract_bf16: operand {tuple(a.shape)} / image {tuple(w_img.shape)} do not fit K={K}, N={N}, {S} blocks")
+    g = _lib.PnaContractBf16Args()
+    g.a, g.lda, g.M, g.K, g.N, g.n_scaler = _lib.dev_ptr(a, torch.bfloat16, "a"), _ld(a), M, K, N, S
+    for i, rs in enumerate(row_scales):
+        if rs is not None:
+            if rs.numel() != M:
+                raise ValueError("row scale must have one entry per row")
+            g.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+    g.w_img = _lib.dev_ptr(w_img, torch.bfloat16, "w_img")
+    if h_self is not None:
+        Kh = h_self.shape[1]
+        if h_self.shape[0] != M or w_self is None or tuple(w_self.shape) != (1, R, (Kh + 31) // 32 * 32) or not w_self.is_contiguous():
+            raise ValueError("pna_contract_bf16: h_self needs (M, Kh) rows and a (1, R, round32(Kh)) image")
+        g.h_self, g.ld_self, g.Kh = _lib.dev_ptr(h_self, torch.bfloat16, "h_self"), _ld(h_self), Kh
+        g.w_self = _lib.dev_ptr(w_self, torch.bfloat16, "w_self")
+    g.bias = _lib.dev_ptr(bias, torch.bfloat16, "bias")
+    if bias is not None and bias.numel() != N:
+        raise ValueError("bias must have one entry per output column")
+    for name, t, n in (("row_post", row_post, M), ("col_scale", col_scale, N), ("col_shift", col_shift, N)):
+        if t is not None:
+            if t.numel() != n:
+                raise ValueError(f"{name} must have {n} entries")
+            setattr(g, name, _lib.dev_ptr(t, torch.float32, name))
+    g.slope = float(slope)
+    if residual is not None:
+        if residual.shape[0] != M or residual.shape[1] < N:
+            raise ValueError("residual must be (M, >= N)")
+        g.residual, g.ld_res = _lib.dev_ptr(residual, torch.bfloat16, "residual"), _ld(residual)
+    if out.shape[0] != M or out.shape[1] < N:
+        raise ValueError("out must be (M, >= N)")
+    g.y, g.ldy = _lib.dev_ptr(out, torch.bfloat16, "y"), _ld(out)
+    rc = _lib.lib().pna_contract_bf16(ctypes.byref(g), _lib.stream_ptr(dev))
+    _lib.check(rc, "pna_contract_bf16")
+    return out
