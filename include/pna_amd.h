@@ -28,6 +28,8 @@ extern "C" {
 
 #define PNA_ABI_VERSION 23 /* 23: + pna_gather_bf16 / pna_contract_bf16 / pna_contract_bf16_tiles (bf16 inference of PNALayer / PNATower and the nets;
                                   pna_gather_bf16_args, pna_contract_bf16_args).
+                                  23, additive: + pna_tower_layer_bf16 / pna_tower_layer_bf16_args (the bf16 tower layer of molecule batches
+                                  as one call); no existing struct or entry point changed.
                               22: + pna_segreduce_fwd_bf16 / pna_segreduce_bf16_partials_bytes, pna_posttrans_bf16 / pna_posttrans_bf16_tiles
                                   (bf16 inference of PNASimpleLayer; pna_segreduce_bf16_args, pna_posttrans_bf16_args).
                               21: the GUARDED fp16 x 2 contraction of the one-kernel layer (round 6): + pna_fused_degree_args.{w_img_x3,
@@ -1151,6 +1153,75 @@ int pna_contract_bf16(const pna_contract_bf16_args* args, pna_stream_t stream);
 /* Column tiles of 16 per workgroup the weight images of an N-column contraction are laid out for (2, 4, 5 or 8; 8 for N > 128);
  * -1 when N is outside 1..4096. */
 int pna_contract_bf16_tiles(int32_t N);
+
+/* ---- the bf16 tower layer of molecule-sized batches: one call, at most two launches (ABI 23, additive) ----------------------------
+ *
+ * pna_tower_layer_bf16 is the bf16 counterpart of pna_tower_layer_f32: in eval mode, all of PNALayer.forward
+ * (models/dgl/pna_layer.py:130-148) with 1-layer pretrans / posttrans, PNATower.forward (:55-76, mix_img == NULL) or
+ * PNASimpleLayer.forward (:197-216, no_self_panel) for batches whose rows all have few in-edges.  `void*` data pointers hold bf16
+ * values; row strides (ld*) are in ELEMENTS.  With Fp = round8(Fi), R = round to bf16 once, everything in between fp32:
+ *   launch 1   x_cat[v] = R([ W_a,t h_t[v] ]_t | [ W_b,t h_t[v] + b_t ]_t)      tower t's block at columns t Fp (+ T Fp for the second
+ *              half); pna_contract_bf16 on proj_img.  Skipped with no_self_panel.
+ *   launch 2   per 16 destination rows, never leaving the CU:
+ *              a_t[v]   = R(aggr[i]( x_src,t[u] + x_dst,t[v] + edge_table[edge_type[k]] : in-edges k = (u -> v) ))   fp32 statistics
+ *                         of pna_gather_bf16 (max / min are selections; rows without in-edges give 0)
+ *              z_t[v]   = R(((b_t + W_h,t h_t[v] + sum_s row_scale[s][v] (W_s,t a_t[v])) * row_post[v]) * col_scale + col_shift)
+ *              y[v]     = R(residual[v] + act(W_mix [z_0 .. z_T-1][v] + b_mix)),   act(t) = t < 0 ? mix_slope * t : t
+ *   mix_img == NULL: y[v] = R(residual[v] + act(((...)) * col_scale + col_shift)) of the concatenation, ONE rounding (PNATower on
+ *   its own: mix_slope = 1, residual NULL).  no_self_panel: the messages are the raw rows h[u] (x = h, no destination term, no
+ *   self block, n_tower = 1, no mixing network): two roundings, the aggregate and y = R(h + relu(BN(...))) with mix_slope = 0.
+ * Each tower is contracted against its own weight blocks only (v_mfma_f32_16x16x32_bf16).  No atomics: identical bits on every run.
+ * Rows of any in-degree are served, one lane per 8 features walking the whole row: callers keep hub rows on pna_gather_bf16.
+ *
+ * Weight images (bf16, 16-byte aligned, zero where nothing is named), Fop = round16(Fo), Kp = round32(n_aggr Fp), Khp = round32(Fi):
+ *   proj_img   the pna_contract_bf16 image (1, R, round32(Kin)) of the 2 T Fp projection rows (Kin = T Fi block-diagonal with
+ *              divide_input, else Fi); proj_bias bf16 [2 T Fp] = [0 | b_t at T Fp + t Fp]
+ *   post_img   [T][n_scaler][Fop][Kp]: element [t][s][n][a Fp + f] = posttrans weight of tower t, output n, scaler s, aggregator a,
+ *              feature f; followed (unless no_self_panel) by [T][Fop][Khp]: element [t][n][f] = the weight on the tower's own h_t
+ *   mix_img    [round16(No)][round32(T Fo)]
+ * Returns PNA_E_INVALID when the 16-row tile -- 32 (T Kp + [T or 1] Khp + round32(T Fo) + 24) bytes -- exceeds 160 KiB of LDS. */
+typedef struct pna_tower_layer_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_tower_layer_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* rowptr;   /* [V+1] CSR by destination */
+  const int32_t* col;      /* [E] source node per CSR edge */
+  int32_t V;
+  int32_t n_tower;         /* T */
+  int32_t Fi;              /* per-tower input width (= pretrans output width) */
+  int32_t Fo;              /* per-tower output width */
+  int32_t divide_input;    /* 0: every tower reads all of h (ldh >= Fi); 1: tower t reads columns [t Fi, (t+1) Fi) */
+  int32_t n_scaler;        /* 1..3 */
+  int32_t n_aggr;          /* 1..PNA_MAX_AGGR */
+  int32_t no_self_panel;   /* != 0: the PNASimpleLayer form */
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_VAR */
+  const void* h;           /* bf16 (V, ldh) node features */
+  int64_t ldh;
+  void* x_cat;             /* bf16 (V, ldx) workspace, 2 T Fp columns, 16-byte aligned, ldx a multiple of 8 */
+  int64_t ldx;
+  const void* proj_img;
+  const void* proj_bias;   /* bf16 [2 T Fp], nullable */
+  const float* row_scale[PNA_MAX_SCALER]; /* each fp32 [V] or NULL = identity */
+  const void* post_img;
+  const void* post_bias;   /* bf16 [T Fo], nullable */
+  const float* row_post;   /* nullable fp32 [V]: graph-norm factor */
+  const float* col_scale;  /* nullable fp32 [T Fo]: eval BatchNorm scale of every tower, concatenated */
+  const float* col_shift;  /* nullable fp32 [T Fo] (with col_scale) */
+  const void* mix_img;     /* nullable */
+  const void* mix_bias;    /* bf16 [No], nullable */
+  int32_t No;              /* mixing output width (ignored without mix_img: the output is T Fo wide) */
+  float mix_slope;         /* 1 = no activation, 0 = ReLU, 0.01 = LeakyReLU */
+  const void* residual;    /* bf16 (V, ld_res), nullable: added after the activation */
+  int64_t ld_res;
+  void* y;                 /* bf16 (V, ldy) */
+  int64_t ldy;
+  const int32_t* edge_type;  /* nullable [E]: type of every CSR edge; values outside [0, n_edge_types) read the nearest table row */
+  const void* edge_table;    /* bf16 (n_edge_types, ld_edge_table), 16-byte aligned rows: R(W_e ef) of tower t at columns t Fp */
+  int64_t ld_edge_table;
+  int32_t n_edge_types;      /* 1..4 with edge_type */
+  int32_t h_tail_readable;   /* no_self_panel: 1 = columns [Fi, round8(Fi)) of every row of h may be read (16-byte gathers) */
+} pna_tower_layer_bf16_args;
+
+int pna_tower_layer_bf16(const pna_tower_layer_bf16_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -265,6 +265,24 @@ class PnaContractBf16Args(_Args):
     ]
 
 
+class PnaTowerLayerBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("V", ctypes.c_int32), ("n_tower", ctypes.c_int32),
+        ("Fi", ctypes.c_int32), ("Fo", ctypes.c_int32), ("divide_input", ctypes.c_int32), ("n_scaler", ctypes.c_int32),
+        ("n_aggr", ctypes.c_int32), ("no_self_panel", ctypes.c_int32), ("aggr", ctypes.c_int32 * PNA_MAX_AGGR),
+        ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("x_cat", ctypes.c_void_p), ("ldx", ctypes.c_int64),
+        ("proj_img", ctypes.c_void_p), ("proj_bias", ctypes.c_void_p),
+        ("row_scale", ctypes.c_void_p * PNA_MAX_SCALER),
+        ("post_img", ctypes.c_void_p), ("post_bias", ctypes.c_void_p), ("row_post", ctypes.c_void_p),
+        ("col_scale", ctypes.c_void_p), ("col_shift", ctypes.c_void_p),
+        ("mix_img", ctypes.c_void_p), ("mix_bias", ctypes.c_void_p), ("No", ctypes.c_int32), ("mix_slope", ctypes.c_float),
+        ("residual", ctypes.c_void_p), ("ld_res", ctypes.c_int64), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
+        ("edge_type", ctypes.c_void_p), ("edge_table", ctypes.c_void_p), ("ld_edge_table", ctypes.c_int64),
+        ("n_edge_types", ctypes.c_int32), ("h_tail_readable", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -393,6 +411,8 @@ def lib():
         L.pna_contract_bf16.restype = ctypes.c_int
         L.pna_contract_bf16_tiles.argtypes = [ctypes.c_int32]
         L.pna_contract_bf16_tiles.restype = ctypes.c_int
+        L.pna_tower_layer_bf16.argtypes = [ctypes.POINTER(PnaTowerLayerBf16Args), ctypes.c_void_p]
+        L.pna_tower_layer_bf16.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

@@ -91,12 +91,20 @@ def _bf16_towers_path(module, towers, mix, graph, h, e, out_dim):
     predicate of PNASimpleLayer._bf16_path -- bf16 features, every floating-point parameter and buffer bf16, inference (eval mode, no
     gradient required), features on the GPU, exactly a Graph -- and: a 1-layer (affine) pretrans, bf16 edge features on the GPU
     when the towers read them, at most 128 output columns, aggregators and scalers the kernels know (mean / sum / max / min / std /
-    var, at most 3 scalers), a mixing network that is Linear + (Leaky)ReLU, and no stream capture in progress.  Every other call
-    takes the fp32 code and fails there as before."""
+    var, at most 3 scalers) and a mixing network that is Linear + (Leaky)ReLU.  Every other call takes the fp32 code and fails
+    there as before.  (A stream capture in progress is served: functional.towers_bf16 keeps host synchronisation out of it.)"""
     if h.dtype != torch.bfloat16 or module.training or not h.is_cuda or type(graph) is not Graph:
         return False
-    if any(t.dtype != torch.bfloat16 for t in list(module.parameters()) + list(module.buffers()) if t.is_floating_point()):
-        return False
+    params = []                                            # (a flat walk: this predicate runs on every call of a 0.1 ms layer)
+    for m in module.modules():
+        for t in m._parameters.values():
+            if t is not None:
+                if t.dtype != torch.bfloat16 and t.is_floating_point():
+                    return False
+                params.append(t)
+        for t in m._buffers.values():
+            if t is not None and t.dtype != torch.bfloat16 and t.is_floating_point():
+                return False
     t0 = towers[0]
     if any(t.training or not t.pretrans.is_affine for t in towers) or out_dim > 128:
         return False
@@ -106,9 +114,9 @@ def _bf16_towers_path(module, towers, mix, graph, h, e, out_dim):
         return False
     if mix is not None and (mix.b_norm is not None or not (mix.activation is None or isinstance(mix.activation, (nn.LeakyReLU, nn.ReLU)))):
         return False
-    if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in module.parameters())):
+    if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in params)):
         return False
-    return not (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing())
+    return True
 
 
 class PNATower(nn.Module):

@@ -176,6 +176,26 @@ def small_tower_fits(T, Fi, Fo, divided, No=None):
     return floats * 4 <= 160 * 1024
 
 
+# bf16 batches up to this many nodes take pna_tower_layer_bf16 (one C call); 0 turns the path off.  The default follows
+# tools/bench_bf16_small.py (profiles/bf16_small.json): the largest measured batch on which the one-call kernel is
+# not slower than the multi-launch path.
+BF16_SMALL_ROWS = int(os.environ.get("PNA_AMD_BF16_SMALL_ROWS", "4096"))
+
+
+def bf16_small_applies(graph, V, *, T, Fi, Fo, A, divide_input, posttrans_affine, edge_features=False, etab=None, No=None,
+                       no_self_panel=False):
+    """Whether a bf16 inference call is served by pna_tower_layer_bf16: a molecule-sized batch (0 < V <= BF16_SMALL_ROWS) without
+    heavy rows (hub rows keep the segment path of the multi-launch kernels), a posttrans that is one Linear, edge features that are
+    absent or an edge-type table `etab` (Graph.edge_type_table: <= 4 distinct rows), and a 16-row tile that fits the LDS."""
+    if not 0 < V <= BF16_SMALL_ROWS or not posttrans_affine:
+        return False
+    if edge_features and etab is None:
+        return False
+    if ops.tower_layer_bf16_lds_bytes(T, Fi, Fo, A, divide_input, No=No, no_self_panel=no_self_panel) > 160 * 1024:
+        return False
+    return graph.heavy_schedule().n_heavy == 0
+
+
 class _SmallTowerPlan:
     """Everything pna_tower_layer_f32 reads besides the graph and h -- the packed projection / posttrans / mixing images, the
     concatenated biases and folded BatchNorm constants -- and a pre-filled argument block, built once per weight state.  The
@@ -1370,6 +1390,14 @@ def simple_layer_bf16(layer, graph, h):
     A = len(layer.aggregators)
     Fb = (F + 7) // 8 * 8
     csr = graph.csr
+    if (not layer.residual or F == layer.out_dim) and bf16_small_applies(
+            graph, h.shape[0], T=1, Fi=F, Fo=layer.out_dim, A=A, divide_input=False, posttrans_affine=layer.posttrans.is_affine,
+            no_self_panel=True):
+        im = _small_simple_images_bf16(layer)
+        return ops.tower_layer_bf16(csr.rowptr, csr.col, h, n_tower=1, Fi=F, Fo=layer.out_dim, divide_input=False,
+                                    aggregators=layer.aggregators, row_scales=_row_scales(graph, layer.scalers, layer.avg_d, h.device),
+                                    post_img=im["post"], post_bias=im["post_bias"], col_scale=im["cs"], col_shift=im["ct"], slope=0.0,
+                                    residual=h if layer.residual else None, no_self_panel=True)
     agg = ops.segreduce_bf16(csr.rowptr, csr.col, h, F, layer.aggregators, block_stride=Fb, heavy=graph.heavy_schedule(),
                              workspace=graph.workspace)
     scales = _row_scales(graph, layer.scalers, layer.avg_d, h.device)
@@ -1395,7 +1423,8 @@ def simple_layer_bf16(layer, graph, h):
 
 
 def _tensor_key(ts):
-    return tuple((id(t), t._version, t.data_ptr(), str(t.device), t.dtype, tuple(t.shape)) for t in ts)
+    # (per call of every bf16 layer: the device and shape objects compare like their string / tuple forms and cost a third)
+    return tuple((id(t), t._version, t.data_ptr(), t.device, t.dtype, t.shape) for t in ts)
 
 
 def _tower_images_bf16(towers, divide_input):
@@ -1461,6 +1490,169 @@ def _tower_images_bf16(towers, divide_input):
     return res
 
 
+def _small_simple_images_bf16(layer):
+    """The images of pna_tower_layer_bf16 in its PNASimpleLayer form: post (1, S, round16(N), round32(A round8(F))) from the
+    reference-layout posttrans weight (N, S A F), the bias and the fp32-folded BatchNorm; cached per version of every source tensor."""
+    lin, bn = layer.posttrans.fully_connected[0].linear, layer.batchnorm_h if layer.batch_norm else None
+    ts = [lin.weight, lin.bias] + ([x for x in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if x is not None] if bn else [])
+    A, S, F, N = len(layer.aggregators), len(layer.scalers), layer.in_dim, lin.out_features
+    key = (_tensor_key(ts), A, S, bn.eps if bn else None)
+    hit = layer.__dict__.get("_pna_amd_bf16_small")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    Fp, Kp = (F + 7) // 8 * 8, (A * ((F + 7) // 8 * 8) + 31) // 32 * 32
+    with torch.no_grad():
+        blk = torch.zeros(S, N, A, Fp, dtype=torch.bfloat16, device=lin.weight.device)
+        blk[..., :F] = lin.weight.reshape(N, S, A, F).permute(1, 0, 2, 3)
+        post = torch.zeros(1, S, (N + 15) // 16 * 16, Kp, dtype=torch.bfloat16, device=lin.weight.device)
+        post[0, :, :N, :A * Fp] = blk.reshape(S, N, A * Fp)
+        cs, ct = _fold_batchnorm_f32(bn) if bn else (None, None)
+    res = {"post": post, "post_bias": lin.bias, "cs": cs, "ct": ct}
+    layer.__dict__["_pna_amd_bf16_small"] = (key, res, ts)
+    return res
+
+
+def _first_linear(mlp):
+    """mlp.fully_connected[0].linear through the modules' own dictionaries (nn.Module.__getattr__ and ModuleList indexing cost 4 us
+    per chain, and the image lookups below walk 2 T chains on every call of a 0.1 ms layer)."""
+    return mlp._modules["fully_connected"]._modules["0"]._modules["linear"]
+
+
+def _bn_tensors(bn):
+    p, b = bn._parameters, bn._buffers
+    return [x for x in (p["weight"], p["bias"], b["running_mean"], b["running_var"]) if x is not None]
+
+
+def _small_images_bf16(towers, mix, divide_input):
+    """The images of pna_tower_layer_bf16 (include/pna_amd.h) for T towers and, with `mix`, the mixing network, built once per version
+    of EVERY tensor they are made from -- the key of _tower_images_bf16 plus the mixing tensors -- and cached on the first tower.
+    With Fp = round8(Fi), Fop = round16(Fo), Kp = round32(A Fp), Khp = round32(Fi):
+      proj  the contraction image of the (2 T Fp, Kin) projection rows: W_a of tower t at rows t Fp, W_b at T Fp + t Fp; proj_bias
+      edge  the contraction image of the (T Fp, ed) edge rows: W_e of tower t at rows t Fp
+      post  [T][S][Fop][Kp] (each tower's OWN blocks, scalers in the layer's order) followed by the self blocks [T][Fop][Khp], flat
+      mix   (round16(No), round32(T Fo))"""
+    t0 = towers[0]
+    pre = [_first_linear(t._modules["pretrans"]) for t in towers]
+    post = [_first_linear(t._modules["posttrans"]) for t in towers]
+    bns = [t._modules["batchnorm_h"] for t in towers] if t0.batch_norm else []
+    ts = [l._parameters[k] for l in pre + post for k in ("weight", "bias")]
+    for bn in bns:
+        ts += _bn_tensors(bn)
+    if mix is not None:
+        ts += [mix.linear.weight, mix.linear.bias]
+    key = (_tensor_key(ts), divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns), mix is not None)
+    hit = t0.__dict__.get("_pna_amd_bf16_small")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    T, Fi, ed, Fo = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
+    A, S = len(t0.aggregators), len(t0.scalers)
+    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
+    Fp, Fop, Kp, Khp = r(Fi, 8), r(Fo, 16), r(A * r(Fi, 8), 32), r(Fi, 32)
+    Kin = T * Fi if divide_input else Fi
+    dev, bf = pre[0].weight.device, torch.bfloat16
+    with torch.no_grad():
+        proj = torch.zeros(1, 2 * T * Fp, Kin, dtype=bf, device=dev)
+        pbias = torch.zeros(2 * T * Fp, dtype=bf, device=dev)
+        edge = torch.zeros(1, T * Fp, max(ed, 1), dtype=bf, device=dev)
+        wpost = torch.zeros(T, S, Fop, Kp, dtype=bf, device=dev)
+        wself = torch.zeros(T, Fop, Khp, dtype=bf, device=dev)
+        for t in range(T):
+            c = slice(t * Fi, (t + 1) * Fi) if divide_input else slice(0, Fi)
+            W = pre[t].weight
+            proj[0, t * Fp:t * Fp + Fi, c] = W[:, :Fi]
+            proj[0, (T + t) * Fp:(T + t) * Fp + Fi, c] = W[:, Fi:2 * Fi]
+            pbias[(T + t) * Fp:(T + t) * Fp + Fi] = pre[t].bias
+            if ed:
+                edge[0, t * Fp:t * Fp + Fi, :ed] = W[:, 2 * Fi:]
+            Wp = post[t].weight                                                    # (Fo, (S A + 1) Fi): [h | scaler-major aggregates]
+            wself[t, :Fo, :Fi] = Wp[:, :Fi]
+            blk = torch.zeros(S, Fo, A, Fp, dtype=bf, device=dev)
+            blk[..., :Fi] = Wp[:, Fi:].reshape(Fo, S, A, Fi).permute(1, 0, 2, 3)
+            wpost[t, :, :Fo, :A * Fp] = blk.reshape(S, Fo, A * Fp)
+        res = {
+            "proj": ops.contract_image_bf16(proj), "proj_bias": pbias,
+            "edge": ops.contract_image_bf16(edge) if ed else None,
+            "post": torch.cat([wpost.reshape(-1), wself.reshape(-1)]),
+            "post_bias": torch.cat([l.bias for l in post]).contiguous(),
+            "cs": None, "ct": None, "mix": None, "mix_bias": None, "etab": None,
+        }
+        if bns:
+            folds = [_fold_batchnorm_f32(bn) for bn in bns]
+            res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
+            res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
+        if mix is not None:
+            No = mix.linear.weight.shape[0]
+            res["mix"] = torch.zeros(r(No, 16), r(T * Fo, 32), dtype=bf, device=dev)
+            res["mix"][:No, :T * Fo] = mix.linear.weight
+            res["mix_bias"] = mix.linear.bias
+    t0.__dict__["_pna_amd_bf16_small"] = (key, res, ts)                            # (ts: the addresses in the key stay taken)
+    return res
+
+
+def _small_edge_table_bf16(im, rows, ed, width):
+    """bf16 (n_types, width) = R(rows W_e^T) for the <= 4 type rows of Graph.edge_type_table, kept with the images while the rows are
+    the same storage at the same version (PNANet's rows are its embedding weight: one launch per weight state, not per call)."""
+    key = (rows.data_ptr(), rows._version, tuple(rows.shape), str(rows.device))
+    hit = im["etab"]
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = im["etab"] = (key, ops.contract_bf16(rows.contiguous(), ed, im["edge"], width), rows)   # (rows: the address stays taken)
+    return hit[1]
+
+
+def _towers_small_bf16(towers, mix, graph, h, e, snorm_n, divide_input, residual):
+    """PNATower / PNALayer through pna_tower_layer_bf16 when bf16_small_applies says so, else None (the multi-launch path follows)."""
+    from .dgl.pna_layer import _row_scales
+    t0 = towers[0]
+    T, Fi, ed, Fo = len(towers), t0.in_dim, t0.edge_dim, t0.out_dim
+    V = h.shape[0]
+    if not 0 < V <= BF16_SMALL_ROWS:
+        return None
+    etab = None
+    if t0.edge_features:
+        if e is None:
+            raise ValueError("edge_features=True but no edge features were given")
+        # while a stream is capturing the table is taken only from register_edge_types (device-side results): a table hashed from the
+        # VALUES of e would freeze the captured example's types into the replay, the per-edge route is captured instead
+        if not torch.cuda.is_current_stream_capturing() or graph.edge_types_registered(e):
+            etab = graph.edge_type_table(e)
+    No = mix.linear.weight.shape[0] if mix is not None else None
+    if not bf16_small_applies(graph, V, T=T, Fi=Fi, Fo=Fo, A=len(t0.aggregators), divide_input=divide_input,
+                              posttrans_affine=t0.posttrans.is_affine, edge_features=t0.edge_features, etab=etab, No=No):
+        return None
+    if t0.edge_features and not graph.edge_types_registered(e):
+        # a capture that follows these warm-up calls takes the per-edge multi-launch route for the first time: its images exist by then
+        _tower_images_bf16(towers, divide_input)
+        if mix is not None:
+            _mix_image_bf16(mix)
+    im = _small_images_bf16(towers, mix, divide_input)
+    csr = graph.csr
+    edge_type = edge_table = None
+    if etab is not None:
+        edge_type, edge_table = etab[0], _small_edge_table_bf16(im, etab[1], ed, T * ((Fi + 7) // 8 * 8))
+    slope = 1.0
+    if mix is not None:
+        slope = 1.0 if mix.activation is None else 0.0 if isinstance(mix.activation, torch.nn.ReLU) else mix.activation.negative_slope
+    return ops.tower_layer_bf16(csr.rowptr, csr.col, h, n_tower=T, Fi=Fi, Fo=Fo, divide_input=divide_input, aggregators=t0.aggregators,
+                                row_scales=_row_scales(graph, t0.scalers, t0.avg_d, h.device), post_img=im["post"],
+                                post_bias=im["post_bias"], proj_img=im["proj"], proj_bias=im["proj_bias"],
+                                row_post=snorm_n.reshape(-1).float() if t0.graph_norm else None, col_scale=im["cs"], col_shift=im["ct"],
+                                mix_img=im["mix"], mix_bias=im["mix_bias"], No=No or 0, slope=slope,
+                                residual=h if residual else None, edge_type=edge_type, edge_table=edge_table)
+
+
+def _mix_image_bf16(mix):
+    """The pna_contract_bf16 image of the mixing weight, cached on the module per weight state."""
+    w = mix.linear.weight
+    key = _tensor_key([w])
+    hit = mix.__dict__.get("_pna_amd_bf16_mix")
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = (key, ops.contract_image_bf16(w.unsqueeze(0)), w)
+        mix.__dict__["_pna_amd_bf16_mix"] = hit
+    return hit[1]
+
+
 def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
     """The concatenated tower outputs h_cat (V, T * out_dim per tower) of PNATower.forward, models/dgl/pna_layer.py:55-76, in inference
     on bf16 features and parameters with a 1-layer pretrans.  Four launches: the node-level projections x_src = W_a h,
@@ -1477,7 +1669,9 @@ def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
         raise ValueError(f"expected features of shape (V, {Kin}), got {tuple(h.shape)}")
     if h.stride(-1) != 1:
         h = h.contiguous()
-    V = h.shape[0]
+    out = _towers_small_bf16(towers, None, graph, h, e, snorm_n, divide_input, False)
+    if out is not None:
+        return out
     im = _tower_images_bf16(towers, divide_input)
     P, csr = im["P"], graph.csr
     x_cat = ops.contract_bf16(h, Kin, im["proj"], 2 * P, (None,), im["proj_bias"])
@@ -1485,7 +1679,9 @@ def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
     if t0.edge_features:
         if e is None:
             raise ValueError("edge_features=True but no edge features were given")
-        etab = graph.edge_type_table(e)                  # an embedding of <= 4 edge types: W_e ef once per type
+        etab = None                                      # an embedding of <= 4 edge types: W_e ef once per type (not from the VALUES of
+        if not torch.cuda.is_current_stream_capturing() or graph.edge_types_registered(e):     # e while a hipGraph is being captured)
+            etab = graph.edge_type_table(e)
         if etab is not None:
             edge_type, ef = etab
         else:
@@ -1510,17 +1706,18 @@ def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
 def tower_layer_bf16(layer, graph, h, e, snorm_n):
     """PNALayer.forward (models/dgl/pna_layer.py:130-145) in inference on bf16 features and parameters: towers_bf16, then the mixing
     network -- Linear, LeakyReLU and the residual -- as one more pna_contract_bf16 launch."""
-    h_cat = towers_bf16(list(layer.towers), graph, h, e, snorm_n, layer.divide_input)
     mix = layer.mixing_network
-    w = mix.linear.weight
-    key = _tensor_key([w])
-    hit = layer.__dict__.get("_pna_amd_bf16_mix")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, ops.contract_image_bf16(w.unsqueeze(0)), w)
-        layer.__dict__["_pna_amd_bf16_mix"] = hit
+    towers = list(layer.towers)
+    Kin = len(towers) * towers[0].in_dim if layer.divide_input else towers[0].in_dim
+    if h.dim() == 2 and h.shape[1] == Kin:
+        hs = h if h.stride(-1) == 1 else h.contiguous()
+        out = _towers_small_bf16(towers, mix, graph, hs, e, snorm_n, layer.divide_input, layer.residual)
+        if out is not None:
+            return out
+    h_cat = towers_bf16(towers, graph, h, e, snorm_n, layer.divide_input)
+    img = _mix_image_bf16(mix)
     N = layer.out_dim
     out = torch.empty(h.shape[0], N, dtype=torch.bfloat16, device=h.device)
     slope = 1.0 if mix.activation is None else 0.0 if isinstance(mix.activation, torch.nn.ReLU) else mix.activation.negative_slope
-    return ops.contract_bf16(h_cat, N, hit[1], N, (None,), mix.linear.bias, slope=slope,
+    return ops.contract_bf16(h_cat, N, img, N, (None,), mix.linear.bias, slope=slope,
                              residual=(h if h.stride(-1) == 1 else h.contiguous()) if layer.residual else None, out=out)

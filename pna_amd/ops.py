@@ -883,3 +883,78 @@ def contract_bf16(a: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_scal
     rc = _lib.lib().pna_contract_bf16(ctypes.byref(g), _lib.stream_ptr(dev))
     _lib.check(rc, "pna_contract_bf16")
     return out
+
+
+# ---- the bf16 tower layer of molecule-sized batches as one call (pna_bf16_small.hip) ------------------------------------------
+def tower_layer_bf16_lds_bytes(T: int, Fi: int, Fo: int, A: int, divide_input: bool, *, No: Optional[int] = None,
+                               no_self_panel: bool = False) -> int:
+    """Host mirror of pna_tower_layer_bf16's LDS check: bytes of one 16-row tile (aggregates of every tower, the rows' own features,
+    the concatenated tower outputs when a mixing network follows); the kernel refuses more than 160 KiB."""
+    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
+    la = T * r(A * r(Fi, 8), 32) + 8
+    lh = 0 if no_self_panel else (T if divide_input else 1) * r(Fi, 32) + 8
+    lc = 0 if No is None else r(T * Fo, 32) + 8
+    return 16 * (la + lh + lc) * 2
+
+
+def tower_layer_bf16(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *, n_tower: int, Fi: int, Fo: int, divide_input: bool,
+                     aggregators: Sequence[str], row_scales: Sequence[Optional[torch.Tensor]], post_img: torch.Tensor,
+                     post_bias: Optional[torch.Tensor] = None, proj_img: Optional[torch.Tensor] = None,
+                     proj_bias: Optional[torch.Tensor] = None, row_post: Optional[torch.Tensor] = None,
+                     col_scale: Optional[torch.Tensor] = None, col_shift: Optional[torch.Tensor] = None,
+                     mix_img: Optional[torch.Tensor] = None, mix_bias: Optional[torch.Tensor] = None, No: int = 0, slope: float = 1.0,
+                     residual: Optional[torch.Tensor] = None, edge_type: Optional[torch.Tensor] = None,
+                     edge_table: Optional[torch.Tensor] = None, no_self_panel: bool = False):
+    """PNALayer / PNATower / PNASimpleLayer (no_self_panel) in inference on bf16 rows as ONE C call, pna_tower_layer_bf16: see
+    include/pna_amd.h for the images and the arithmetic.  Returns bf16 (V, No) with a mixing image, else (V, n_tower * Fo)."""
+    V = rowptr.numel() - 1
+    dev = h.device
+    width = No if mix_img is not None else n_tower * Fo
+    out = torch.empty(V, width, dtype=torch.bfloat16, device=dev)
+    a = _lib.PnaTowerLayerBf16Args()
+    a.rowptr = _lib.dev_ptr(rowptr, torch.int32, "rowptr")
+    a.col = _lib.dev_ptr(col, torch.int32, "col")
+    a.V, a.n_tower, a.Fi, a.Fo, a.divide_input, a.n_scaler = V, n_tower, Fi, Fo, int(divide_input), len(row_scales)
+    a.n_aggr, a.no_self_panel = len(aggregators), int(no_self_panel)
+    for i, name in enumerate(aggregators):
+        if name not in _BF16_AGGS:
+            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
+        a.aggr[i] = _lib.AGG_CODES[name]
+    a.h, a.ldh = _lib.dev_ptr(h, torch.bfloat16, "h"), _ld(h)
+    xc = None
+    if no_self_panel:
+        a.h_tail_readable = int(_tail_readable(h, Fi))
+    else:
+        xw = 2 * n_tower * ((Fi + 7) // 8 * 8)
+        xc = torch.empty(V, xw, dtype=torch.bfloat16, device=dev)
+        a.x_cat, a.ldx = _lib.dev_ptr(xc, torch.bfloat16, "x_cat"), xw
+        a.proj_img, a.proj_bias = _lib.dev_ptr(proj_img, torch.bfloat16, "proj_img"), _lib.dev_ptr(proj_bias, torch.bfloat16, "proj_bias")
+    for i, rs in enumerate(row_scales):
+        if rs is not None:
+            if rs.numel() != V:
+                raise ValueError("row scale must have one entry per row")
+            a.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+    a.post_img, a.post_bias = _lib.dev_ptr(post_img, torch.bfloat16, "post_img"), _lib.dev_ptr(post_bias, torch.bfloat16, "post_bias")
+    for name, t, n in (("row_post", row_post, V), ("col_scale", col_scale, n_tower * Fo), ("col_shift", col_shift, n_tower * Fo)):
+        if t is not None:
+            if t.numel() != n:
+                raise ValueError(f"{name} must have {n} entries")
+            setattr(a, name, _lib.dev_ptr(t, torch.float32, name))
+    if mix_img is not None:
+        a.mix_img, a.mix_bias, a.No = _lib.dev_ptr(mix_img, torch.bfloat16, "mix_img"), _lib.dev_ptr(mix_bias, torch.bfloat16, "mix_bias"), No
+    a.mix_slope = float(slope)
+    if residual is not None:
+        if residual.shape[0] != V or residual.shape[1] < width:
+            raise ValueError("residual must be (V, >= output width)")
+        a.residual, a.ld_res = _lib.dev_ptr(residual, torch.bfloat16, "residual"), _ld(residual)
+    a.y, a.ldy = _lib.dev_ptr(out, torch.bfloat16, "y"), width
+    if edge_type is not None:
+        if edge_table is None or edge_type.numel() != col.numel():
+            raise ValueError("edge_type needs edge_table and one entry per edge")
+        a.edge_type = _lib.dev_ptr(edge_type, torch.int32, "edge_type")
+        a.edge_table, a.ld_edge_table = _lib.dev_ptr(edge_table, torch.bfloat16, "edge_table"), _ld(edge_table)
+        a.n_edge_types = edge_table.shape[0]
+    rc = _lib.lib().pna_tower_layer_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
+    _lib.check(rc, "pna_tower_layer_bf16")
+    del xc                                                   # (stream-ordered allocator: safe to release after the launch)
+    return out
