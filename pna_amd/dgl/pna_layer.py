@@ -119,7 +119,7 @@ def _bf16_towers_path(module, towers, mix, graph, h, e, out_dim):
     return True
 
 
-class PNATower(nn.Module):
+class PNATower(PF.DropsCachesOnConversion, nn.Module):
     def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, avg_d,
                  pretrans_layers, posttrans_layers, edge_features, edge_dim):
         super().__init__()
@@ -330,7 +330,7 @@ def _towers_forward(towers, graph, h, e, snorm_n, divide_input):
     return torch.cat(outs, dim=1) if T > 1 else outs[0]
 
 
-class PNALayer(nn.Module):
+class PNALayer(PF.DropsCachesOnConversion, nn.Module):
     def __init__(self, in_dim, out_dim, aggregators, scalers, avg_d, dropout, graph_norm, batch_norm, towers=1,
                  pretrans_layers=1, posttrans_layers=1, divide_input=True, residual=False, edge_features=False,
                  edge_dim=0):
@@ -359,10 +359,6 @@ class PNALayer(nn.Module):
                      batch_norm=batch_norm, dropout=dropout, graph_norm=graph_norm, edge_features=edge_features,
                      edge_dim=edge_dim) for _ in range(towers))
         self.mixing_network = FCLayer(out_dim, out_dim, activation="LeakyReLU")
-
-    def _apply(self, fn, *args, **kwargs):
-        self.__dict__.pop("_pna_amd_small", None)             # cached weight images follow the parameters' device / dtype
-        return super()._apply(fn, *args, **kwargs)
 
     def _small_structure_ok(self):
         """The structural conditions of the one-call path (they do not change after construction): 1-layer pretrans and
@@ -461,7 +457,7 @@ class PNALayer(nn.Module):
         return "{}(in_channels={}, out_channels={})".format(self.__class__.__name__, self.in_dim, self.out_dim)
 
 
-class PNASimpleLayer(nn.Module):
+class PNASimpleLayer(PF.DropsCachesOnConversion, nn.Module):
     """Tower-less layer of the MolHIV net (pna_layer.py:151-216): messages are the raw source features."""
 
     def __init__(self, in_dim, out_dim, aggregators, scalers, avg_d, dropout, batch_norm, residual,
@@ -489,10 +485,6 @@ class PNASimpleLayer(nn.Module):
         graph = as_graph(g)
         return PF.aggregate(graph, graph.source_features(h), self.in_dim, self.aggregators,
                             row_scales=_row_scales(graph, self.scalers, self.avg_d, h.device))
-
-    def _apply(self, fn, *args, **kwargs):
-        self.__dict__.pop("_pna_amd_small", None)             # cached weight images follow the parameters' device / dtype
-        return super()._apply(fn, *args, **kwargs)
 
     def _small_batch_path(self, graph, h):
         """Whether this call is served by pna_tower_layer_f32 (one C call, two launches: functional._SmallSimplePlan):

@@ -196,6 +196,35 @@ def bf16_small_applies(graph, V, *, T, Fi, Fo, A, divide_input, posttrans_affine
     return graph.heavy_schedule().n_heavy == 0
 
 
+def drop_weight_caches(module):
+    """Remove every `_pna_amd_*` entry from `module`, its submodules and their parameters and buffers.  Called from `_apply` (.to(),
+    .float(), .cuda(), ...): there every parameter gets NEW storage under an UNCHANGED version counter, and the allocator may hand the
+    converted tensor the address its predecessor just freed (.to(bfloat16).float() does exactly that) -- the (version, address, device)
+    keys of the caches cannot tell that state from the one they were built for.  Nothing on the per-call path: the next call rebuilds."""
+    for m in module.modules():
+        for owner in [m, *m._parameters.values(), *m._buffers.values()]:
+            d = getattr(owner, "__dict__", None)
+            if d:
+                for tag in [k for k in d if isinstance(k, str) and k.startswith("_pna_amd_")]:
+                    del d[tag]
+
+
+class DropsCachesOnConversion:
+    """Mixin of every layer and net (before nn.Module in the bases): a conversion -- `_apply`, the one route of .to(), .float(), .cuda(),
+    .cpu() -- drops every cached operand below the module.  A submodule of another class converted ON ITS OWN
+    (`layer.mixing_network.to(...)`) does not pass here: convert the layer."""
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        drop_weight_caches(self)
+        return out
+
+
+def _no_plan():
+    """What a copied / unpickled layer holds in place of its one-call plan (_SmallTowerPlan.__reduce__): nothing."""
+    return None
+
+
 class _SmallTowerPlan:
     """Everything pna_tower_layer_f32 reads besides the graph and h -- the packed projection / posttrans / mixing images, the
     concatenated biases and folded BatchNorm constants -- and a pre-filled argument block, built once per weight state.  The
@@ -265,6 +294,11 @@ class _SmallTowerPlan:
         self.args, self.ref = a, ctypes.byref(a)
         self.fn = _lib.lib().pna_tower_layer_f32
         self.check, self.stream_ptr = _lib.check, _lib.stream_ptr
+
+    def __reduce__(self):
+        # copy.deepcopy / pickle / torch.save of a warm layer: the plan holds a ctypes argument block (not copyable) that points into
+        # THIS layer's device buffers -- a copy carries no plan and builds its own on its first call
+        return (_no_plan, ())
 
     def _state(self):
         # (version, storage address, device) per tensor: `param.data = other` (EMA / SWA swaps, vector_to_parameters, offloading)
@@ -888,9 +922,13 @@ def _tower_pass_weights(layer, towers, mix):
     and the self panel W_self h_v: (N, in_dim + S in_dim) = [W_self | M_0 | .. | M_S-1], the layout of functional.posttrans with h_self = agg = h.
     Formed in float64, rounded once.  Cached on the layer."""
     Wv, d, c, ones, K = _tower_collapsed_weights(layer, towers, mix, False)
+    # Wd and beta read every tower's PRETRANS weight and bias, which the collapsed weight's key does not cover: they are keyed here, like
+    # _projection_cache_padded_multi keys them (host integers only: no device synchronisation, no tensor allocation)
+    key = tuple((p._version, p.data_ptr(), str(p.device)) for tw in towers
+                for p in (tw.pretrans.fully_connected[0].linear.weight, tw.pretrans.fully_connected[0].linear.bias) if p is not None)
     hit = layer.__dict__.get("_pna_amd_pass_w")
-    if hit is not None and hit[0] is Wv:
-        return hit[1:]
+    if hit is not None and hit[0] is Wv and hit[1] == key:
+        return hit[2:]
     T, Fi = len(towers), towers[0].in_dim
     S = Wv.shape[1] // K
     N = Wv.shape[0]
@@ -921,7 +959,7 @@ def _tower_pass_weights(layer, towers, mix):
             Wr[:, s_ * (Ka + N):s_ * (Ka + N) + Ka] = Wv[:, s_ * K:s_ * K + Ka]
         Wr[:, Ka:Ka + N] = torch.eye(N, dtype=torch.float32, device=Wv.device)
     res = (Ws, Wd.float().contiguous(), beta.float().contiguous(), Wr.contiguous(), d, c, ones)
-    layer.__dict__["_pna_amd_pass_w"] = (Wv,) + res
+    layer.__dict__["_pna_amd_pass_w"] = (Wv, key) + res
     return res
 
 

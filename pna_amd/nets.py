@@ -67,7 +67,7 @@ def readout_nodes(g, h, op):
     return PF.aggregate(rg, h, h.shape[1], [op], edge_resident=True)
 
 
-class PNANet(nn.Module):
+class PNANet(PF.DropsCachesOnConversion, nn.Module):
     def __init__(self, net_params):
         super().__init__()
         p = net_params
@@ -111,7 +111,7 @@ class PNANet(nn.Module):
         return nn.L1Loss()(scores, targets)
 
 
-class PNANetSuperpixels(nn.Module):
+class PNANetSuperpixels(PF.DropsCachesOnConversion, nn.Module):
     """nets/superpixels_graph_classification/pna_net.py:17-104: the same stack as the molecules net behind LINEAR embeddings of the
     float node features (mean colour | position: in_dim 3 for MNIST, 5 for CIFAR10) and edge features, `n_classes` outputs and a
     cross-entropy loss.  (Like the reference's forward :72-98, `in_feat_dropout` is read from the params and never applied.)
@@ -202,7 +202,7 @@ class AtomEncoderStandIn(nn.Module):
         return out
 
 
-class PNANetHIV(nn.Module):
+class PNANetHIV(PF.DropsCachesOnConversion, nn.Module):
     """nets/HIV_graph_classification/pna_net.py:9-64 (PNASimpleLayer stack, mean readout by default)."""
 
     def __init__(self, net_params):

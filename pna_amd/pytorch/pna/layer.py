@@ -21,7 +21,7 @@ _BY_ROW = ("mean", "sum", "std", "var")     # reduce over j, adjacency as weight
 _BY_COL = ("max", "min")                    # reduce over i, adjacency as mask
 
 
-class PNATower(nn.Module):
+class PNATower(PF.DropsCachesOnConversion, nn.Module):
     def __init__(self, in_features, out_features, aggregators, scalers, avg_d, self_loop, pretrans_layers,
                  posttrans_layers, device):
         super().__init__()
@@ -127,7 +127,7 @@ def _dense_towers_forward_registry(towers, x, adj, divide_input):
     return torch.cat(outs, dim=2) if len(outs) > 1 else outs[0]
 
 
-class PNALayer(nn.Module):
+class PNALayer(PF.DropsCachesOnConversion, nn.Module):
     """A single PNA convolution on dense adjacency (https://arxiv.org/abs/2004.05718)."""
 
     def __init__(self, in_features, out_features, aggregators, scalers, avg_d, towers=1, self_loop=False,

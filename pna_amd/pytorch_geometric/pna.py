@@ -70,7 +70,7 @@ def _row_factors(graph: Graph, scalers: List[str], avg_deg):
     return [None if s == "identity" else row_factor(s, deg, avg_deg).contiguous() for s in scalers], deg
 
 
-class PNAConv(torch.nn.Module):
+class PNAConv(PF.DropsCachesOnConversion, torch.nn.Module):
     """The full layer (pre_nns on [x_i, x_j, edge], towers, post_nns on [x, aggregate], final mixing Linear)."""
 
     def __init__(self, in_channels: int, out_channels: int, aggregators: List[str], scalers: List[str], deg: Tensor,
@@ -152,7 +152,7 @@ class PNAConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, towers={self.towers})"
 
 
-class PNAConvSimple(torch.nn.Module):
+class PNAConvSimple(PF.DropsCachesOnConversion, torch.nn.Module):
     """The simple layer of the MolHIV example (pna.py:167-253): messages are the raw source features."""
 
     def __init__(self, in_channels: int, out_channels: int, aggregators: List[str], scalers: List[str], deg: Tensor,

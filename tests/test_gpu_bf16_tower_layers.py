@@ -165,20 +165,33 @@ def test_fp32_forward_unchanged_by_bf16_calls(cuda_device):
 
 
 def test_changing_a_pretrans_weight_in_place_changes_the_next_output(cuda_device):
-    """The cached weight images are keyed on every tensor they are built from: the LAST tower's pretrans weight included."""
+    """The cached weight images are keyed on every tensor they are built from: the LAST tower's pretrans weight included.  After each
+    update the warm layer gives bit for bit what a fresh layer with the same state gives: a half-stale cache -- one
+    image rebuilt, another not -- changes the output too, and only the comparison with a fresh layer tells the two apart."""
     meta, a, sd = load_golden("tower_zinc_first")
     layer = _tower_layer(meta, a, sd, cuda_device)
     g = Graph(a["src"], a["dst"], meta["N"]).to(cuda_device)
     h, sn = a["h"].to(BF).to(cuda_device), a["snorm_n"].to(BF).to(cuda_device)
+
+    def fresh():
+        other = _tower_layer(meta, a, sd, cuda_device)
+        other.load_state_dict(layer.state_dict())
+        return other(g, h, None, sn)
     with torch.no_grad():
         first = layer(g, h, None, sn)
         assert torch.equal(layer(g, h, None, sn), first)
+        assert torch.equal(fresh(), first)                               # control: a fresh layer, same state, same bits
         layer.towers[-1].pretrans.fully_connected[0].linear.weight.mul_(1.5)
-        assert not torch.equal(layer(g, h, None, sn), first)
+        after = layer(g, h, None, sn)
+        assert not torch.equal(after, first)
+        assert torch.equal(after, fresh())
         layer.mixing_network.linear.weight.mul_(0.5)
         second = layer(g, h, None, sn)
+        assert torch.equal(second, fresh())
         layer.towers[1].batchnorm_h.running_var.mul_(4.0)
-        assert not torch.equal(layer(g, h, None, sn), second)
+        third = layer(g, h, None, sn)
+        assert not torch.equal(third, second)
+        assert torch.equal(third, fresh())
 
 
 # ---- nets ---------------------------------------------------------------------------------------------------------------------

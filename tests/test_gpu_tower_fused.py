@@ -159,23 +159,34 @@ def test_tower_layer_small_is_deterministic_and_capturable():
 
 
 def test_tower_layer_small_tracks_weight_updates():
-    """The cached weight images follow in-place parameter updates (optimizer steps, load_state_dict)."""
+    """The cached weight images follow in-place parameter updates (optimizer steps, load_state_dict): after EACH update the warm layer
+    gives bit for bit what a fresh layer with the same state gives, and the update is visible in the output."""
     dev = torch.device("cuda:0")
     g = _graph(400, 1200, seed=1).to(dev)
     avg = {"log": torch.log(g.in_degrees().double() + 1).mean().float().cpu()}
     layer = _layer(30, 30, 5, True, SCA, True, True, True, avg, seed=5).to(dev)
     h = torch.randn(400, 30, device=dev)
     sn = g.snorm_n()
-    with torch.no_grad():
-        y0 = layer(g, h, None, sn)
-        layer.towers[2].posttrans.fully_connected[0].linear.weight.mul_(1.5)
-        layer.mixing_network.linear.bias.add_(0.25)
-        layer.towers[0].batchnorm_h.running_var.mul_(2.0)
-        y1 = layer(g, h, None, sn)
-        assert not torch.equal(y0, y1)
+
+    def fresh_out():
         fresh = _layer(30, 30, 5, True, SCA, True, True, True, avg, seed=5).to(dev)
         fresh.load_state_dict(layer.state_dict())
-        assert torch.equal(fresh(g, h, None, sn), y1)
+        return fresh(g, h, None, sn)
+    with torch.no_grad():
+        y0 = layer(g, h, None, sn)
+        assert torch.equal(layer(g, h, None, sn), y0)                    # warm: served twice
+        assert torch.equal(fresh_out(), y0)                              # control: a fresh layer, same state, same bits
+        layer.towers[2].posttrans.fully_connected[0].linear.weight.mul_(1.5)
+        ya = layer(g, h, None, sn)
+        assert not torch.equal(y0, ya) and torch.equal(fresh_out(), ya)
+        layer.mixing_network.linear.bias.add_(0.25)
+        yb = layer(g, h, None, sn)
+        assert not torch.equal(ya, yb) and torch.equal(fresh_out(), yb)
+        layer.towers[0].batchnorm_h.running_var.mul_(2.0)
+        y1 = layer(g, h, None, sn)
+        assert not torch.equal(yb, y1)
+        assert not torch.equal(y0, y1)
+        assert torch.equal(fresh_out(), y1)
 
 
 def test_small_simple_layer_keeps_a_non_finite_own_feature_out(cuda_device, monkeypatch):
