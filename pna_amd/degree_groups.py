@@ -20,6 +20,7 @@ import os
 import torch
 
 from . import _lib
+from ._cache import memo, tensor_key
 
 TILE = 128                 # rows of a workgroup tile of the one-block grouped kernel (8 wavefronts x 16 rows, two workgroups per CU)
                            # (64 < out_dim <= 80 and 80 < out_dim <= 128 alike: the 128-column block runs one 8-wavefront workgroup per CU)
@@ -409,13 +410,9 @@ def combined_images(weight, K, row_scales, plan):
     """Packed bf16x3 images of W_D = sum_s s_s(D) W_s for every group of `plan` (one buffer, image_stride bytes apart), cached
     on the weight per (version, scaler tensors, plan).  out_dim <= 80: ONE pack call over a (G * 80, K) matrix whose 80-column
     blocks are the images; 80 < out_dim <= 128: one pack call per image (the packer cuts wider matrices into 80-column blocks)."""
-    key = (weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), K, plan.serial, plan.G,
-           tuple(None if rs is None else (rs.data_ptr(), rs._version) for rs in row_scales))
-    hit = getattr(weight, "_pna_amd_group_img", None)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    N, G = weight.shape[0], plan.G
-    with torch.no_grad():
+
+    def build():
+        N, G = weight.shape[0], plan.G
         wc = None
         for s, rs in enumerate(row_scales):
             ws = weight[:, s * K:(s + 1) * K]
@@ -424,27 +421,24 @@ def combined_images(weight, K, row_scales, plan):
         BW = 80 if N <= 80 else 128
         w_all = torch.zeros(G, BW, K, dtype=torch.float32, device=weight.device)
         w_all[:, :N] = wc
-    L = _lib.lib()
-    nh = ctypes.c_int64(0)
-    if BW == 80:
-        nb = L.pna_posttrans_x3_packed_bytes(K, G * 80, 1, 0, ctypes.byref(nh))
-        img = torch.empty(nb // 4, dtype=torch.float32, device=weight.device)
-        rc = L.pna_posttrans_x3_pack_f32(_lib.dev_ptr(w_all.view(G * 80, K), torch.float32, "weight"), K, G * 80, K, 1, 0,
-                                         _lib.dev_ptr(img, torch.float32, "w_img"), None, _lib.stream_ptr(weight.device))
-        _lib.check(rc, "pna_posttrans_x3_pack_f32")
-        stride = nb // G
-    else:
-        stride = L.pna_posttrans_x3_packed_bytes(K, 128, 1, 0, ctypes.byref(nh))
-        img = torch.empty(G * stride // 4, dtype=torch.float32, device=weight.device)
-        for i in range(G):
-            rc = L.pna_posttrans_x3_pack_f32(_lib.dev_ptr(w_all[i], torch.float32, "weight"), K, 128, K, 1, 0,
-                                             _lib.dev_ptr(img[i * stride // 4:], torch.float32, "w_img"), None, _lib.stream_ptr(weight.device))
+        L = _lib.lib()
+        nh = ctypes.c_int64(0)
+        if BW == 80:
+            nb = L.pna_posttrans_x3_packed_bytes(K, G * 80, 1, 0, ctypes.byref(nh))
+            img = torch.empty(nb // 4, dtype=torch.float32, device=weight.device)
+            rc = L.pna_posttrans_x3_pack_f32(_lib.dev_ptr(w_all.view(G * 80, K), torch.float32, "weight"), K, G * 80, K, 1, 0,
+                                             _lib.dev_ptr(img, torch.float32, "w_img"), None, _lib.stream_ptr(weight.device))
             _lib.check(rc, "pna_posttrans_x3_pack_f32")
-    try:
-        weight._pna_amd_group_img = (key, img, stride)
-    except AttributeError:
-        pass
-    return img, stride
+            stride = nb // G
+        else:
+            stride = L.pna_posttrans_x3_packed_bytes(K, 128, 1, 0, ctypes.byref(nh))
+            img = torch.empty(G * stride // 4, dtype=torch.float32, device=weight.device)
+            for i in range(G):
+                rc = L.pna_posttrans_x3_pack_f32(_lib.dev_ptr(w_all[i], torch.float32, "weight"), K, 128, K, 1, 0,
+                                                 _lib.dev_ptr(img[i * stride // 4:], torch.float32, "w_img"), None, _lib.stream_ptr(weight.device))
+                _lib.check(rc, "pna_posttrans_x3_pack_f32")
+        return img, stride
+    return memo(weight, "_pna_amd_group_img", [weight, *row_scales], (K, plan.serial, plan.G), build)
 
 
 def fused_tower_images(weight, F, row_scales, plan, x3=False):
@@ -511,24 +505,18 @@ def virtual_layer_weight(weight, F, aggregators, S):
     the aggregators), for the contraction of the rest rows -- their gather is the hand-scheduled kernel's: the standard four only --:
     (N, S * Kv), scaler blocks of Kv = 4F or 5F columns [mean | max | min | std (| sum)].  Cached on the weight."""
     aggs = tuple(aggregators)
-    key = ("virt", aggs, S, weight._version, weight.data_ptr(), tuple(weight.shape))
-    hit = getattr(weight, "_pna_amd_virtual", None)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    A = len(aggs)
-    Kv = (5 if "sum" in aggs else 4) * F
-    with torch.no_grad():
+
+    def build():
+        A = len(aggs)
+        Kv = (5 if "sum" in aggs else 4) * F
         W = weight.detach()
         w = torch.zeros(W.shape[0], S * Kv, dtype=torch.float32, device=W.device)
         for s_ in range(S):
             for j, a in enumerate(aggs):
                 slot = 4 if a == "sum" else _AGG_SLOT[a][0]
                 w[:, s_ * Kv + slot * F:s_ * Kv + (slot + 1) * F] = W[:, (s_ * A + j) * F:(s_ * A + j + 1) * F]
-    try:
-        weight._pna_amd_virtual = (key, w, Kv)
-    except AttributeError:
-        pass
-    return w, Kv
+        return w, Kv
+    return memo(weight, "_pna_amd_virtual", [weight], (aggs, S, F), build)
 
 
 def fused_images(weight, F, row_scales, plan, tower=False, x3=False, rows=None, aggregators=STANDARD_AGGREGATORS, feats=None):
@@ -540,10 +528,9 @@ def fused_images(weight, F, row_scales, plan, tower=False, x3=False, rows=None, 
     feature panel of a layer with more features than one launch gathers); aggregators: the layer's list (see _virtual_weight)."""
     N, G, S = weight.shape[0], plan.G, len(row_scales)
     aggs = tuple(aggregators)
-    key = ("fused", tower, x3, rows, feats, aggs, weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), F, plan.serial, G,
-           tuple(None if rs is None else (rs.data_ptr(), rs._version) for rs in row_scales))
-    attr = "_pna_amd_fused_img"
-    cache = getattr(weight, attr, None)                     # {plan serial: (key, image, stride)}: the block plans of a pipelined run
+    keyed = [weight, *row_scales]
+    key = (tensor_key(keyed), F, G)
+    cache = weight.__dict__.get("_pna_amd_fused_img")       # {plan serial: (key, image, stride, keyed)}: the block plans of a pipelined run
     ckey = (tower, x3, rows, feats, aggs, plan.serial)
     hit = cache.get(ckey) if isinstance(cache, dict) else None      # share one weight, each with its own groups
     if hit is not None and hit[0] == key:
@@ -568,15 +555,11 @@ def fused_images(weight, F, row_scales, plan, tower=False, x3=False, rows=None, 
     rc = L.pna_fused_pack_f32(_lib.dev_ptr(w, torch.float32, "weight"), w.stride(0), Np, Fp, sc.shape[1], _lib.dev_ptr(sc, torch.float32, "scale"),
                               G, _lib.dev_ptr(img, torch.float32, "w_img"), 1 if tower else 0, 1 if x3 else 0, _lib.stream_ptr(weight.device))
     _lib.check(rc, "pna_fused_pack_f32")
-    try:
-        if not isinstance(cache, dict):
-            cache = {}
-            weight._pna_amd_fused_img = cache
-        if len(cache) >= 64:                                 # (plans of dropped graphs: start over rather than grow)
-            cache.clear()
-        cache[ckey] = (key, img, stride)
-    except AttributeError:
-        pass
+    if not isinstance(cache, dict):
+        cache = weight.__dict__["_pna_amd_fused_img"] = {}
+    if len(cache) >= 64:                                     # (plans of dropped graphs: start over rather than grow)
+        cache.clear()
+    cache[ckey] = (key, img, stride, keyed[1:])              # (the entry holds the keyed tensors, like _cache.memo's)
     return img, stride
 
 

@@ -66,15 +66,11 @@ def as_graph(g) -> Graph:
 def _avg_log_value(avg_d):
     """avg_d['log'] as a Python float, read from the device ONCE per tensor object/version (a .item() per forward
     would put a device->host synchronisation into every layer call and make the forward un-capturable in a
-    hipGraph).  The cache lives on the tensor object itself, never keyed by address (addresses are recycled)."""
+    hipGraph).  The cache lives on the tensor object itself, never looked up by address alone (addresses are recycled)."""
     t = avg_d["log"]
     if not torch.is_tensor(t):
         return float(t)
-    hit = getattr(t, "_pna_amd_float", None)
-    if hit is None or hit[0] != (t._version, t.data_ptr(), str(t.device)):
-        hit = ((t._version, t.data_ptr(), str(t.device)), float(t))
-        t._pna_amd_float = hit
-    return hit[1]
+    return PF.memo(t, "_pna_amd_float", [t], None, lambda: float(t))
 
 
 def _row_scales(graph, scalers, avg_d, device):
@@ -160,79 +156,68 @@ class PNATower(PF.DropsCachesOnConversion, nn.Module):
         return _towers_forward([self], graph, h, e, snorm_n, divide_input=False)
 
 
+def _pretrans_linears(towers):
+    return [PF._first_linear(t._modules["pretrans"]) for t in towers]
+
+
 def _projection_cache(towers, Fi):
-    """([W_a ; W_b] (2*T*Fi, Fi), [0 ; b] (2*T*Fi)) of the towers' 1-layer pretrans, cached on the first tower per parameter
-    (version, address): one GEMM then gives the source-side rows W_a h (columns [0, T*Fi)) and the destination-side rows
+    """([W_a ; W_b] (2*T*Fi, Fi), [0 ; b] (2*T*Fi)) of the towers' 1-layer pretrans, cached on the first tower per state of its
+    parameters: one GEMM then gives the source-side rows W_a h (columns [0, T*Fi)) and the destination-side rows
     W_b h + b (columns [T*Fi, 2*T*Fi)) of every tower."""
-    lins = [t.pretrans.fully_connected[0].linear for t in towers]
-    key = tuple((p._version, p.data_ptr(), str(p.device)) for l in lins for p in (l.weight, l.bias))
-    hit = towers[0].__dict__.get("_pna_amd_proj")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            W = torch.stack([l.weight for l in lins])                                        # (T, Fi, 2Fi + ed)
-            T = len(lins)
-            Wcat = torch.cat([W[:, :, :Fi].reshape(T * Fi, Fi), W[:, :, Fi:2 * Fi].reshape(T * Fi, Fi)], dim=0).contiguous()
-            b = torch.stack([l.bias for l in lins]).reshape(-1)
-            bcat = torch.cat([torch.zeros_like(b), b]).contiguous()
-        hit = (key, Wcat, bcat)
-        towers[0].__dict__["_pna_amd_proj"] = hit
-    return hit[1], hit[2]
+
+    def build():
+        lins = _pretrans_linears(towers)
+        W = torch.stack([l.weight for l in lins])                                        # (T, Fi, 2Fi + ed)
+        T = len(lins)
+        Wcat = torch.cat([W[:, :, :Fi].reshape(T * Fi, Fi), W[:, :, Fi:2 * Fi].reshape(T * Fi, Fi)], dim=0).contiguous()
+        b = torch.stack([l.bias for l in lins]).reshape(-1)
+        return Wcat, torch.cat([torch.zeros_like(b), b]).contiguous()
+    return PF.memo(towers[0], "_pna_amd_proj", PF._tower_tensors(towers, pre=True), None, build)
 
 
 def _projection_cache_padded(tower, Fi, P):
     """_projection_cache for ONE tower with each half padded to P columns (zero weight rows): x_cat = [x_src | 0 | x_dst | 0],
     rows and halves 16-byte aligned -- the table the one-kernel tower layer reads in 16-byte strips."""
-    lin = tower.pretrans.fully_connected[0].linear
-    key = tuple((p._version, p.data_ptr(), str(p.device)) for p in (lin.weight, lin.bias)) + (P,)
-    hit = tower.__dict__.get("_pna_amd_proj_pad")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            W = torch.zeros(2 * P, Fi, dtype=lin.weight.dtype, device=lin.weight.device)
-            b = torch.zeros(2 * P, dtype=lin.weight.dtype, device=lin.weight.device)
-            W[:Fi], W[P:P + Fi], b[P:P + Fi] = lin.weight[:, :Fi], lin.weight[:, Fi:2 * Fi], lin.bias
-        hit = (key, W.contiguous(), b.contiguous())
-        tower.__dict__["_pna_amd_proj_pad"] = hit
-    return hit[1], hit[2]
+
+    def build():
+        lin, = _pretrans_linears([tower])
+        W = torch.zeros(2 * P, Fi, dtype=lin.weight.dtype, device=lin.weight.device)
+        b = torch.zeros(2 * P, dtype=lin.weight.dtype, device=lin.weight.device)
+        W[:Fi], W[P:P + Fi], b[P:P + Fi] = lin.weight[:, :Fi], lin.weight[:, Fi:2 * Fi], lin.bias
+        return W.contiguous(), b.contiguous()
+    return PF.memo(tower, "_pna_amd_proj_pad", PF._tower_tensors([tower], pre=True), P, build)
 
 
 def _projection_cache_padded_div(towers, Fi, P):
     """_projection_cache_padded for T towers with divide_input=True (models/dgl/pna_layer.py:133-136): tower t projects the input
     slice [t Fi, (t+1) Fi) -- ONE block-diagonal GEMM gives x_cat = [x_src (T Fi) | 0 | x_dst (T Fi) | 0] with tower t's rows in
     columns [t Fi, (t+1) Fi) of each half."""
-    lins = [t.pretrans.fully_connected[0].linear for t in towers]
-    key = tuple((p._version, p.data_ptr(), str(p.device)) for l in lins for p in (l.weight, l.bias)) + (P,)
-    hit = towers[0].__dict__.get("_pna_amd_proj_pad_div")
-    if hit is None or hit[0] != key:
-        T = len(lins)
-        with torch.no_grad():
-            W = torch.zeros(2 * P, T * Fi, dtype=lins[0].weight.dtype, device=lins[0].weight.device)
-            b = torch.zeros(2 * P, dtype=W.dtype, device=W.device)
-            for t, lin in enumerate(lins):
-                r = slice(t * Fi, (t + 1) * Fi)
-                W[r, r] = lin.weight[:, :Fi]
-                W[P + t * Fi:P + (t + 1) * Fi, r] = lin.weight[:, Fi:2 * Fi]
-                b[P + t * Fi:P + (t + 1) * Fi] = lin.bias
-        hit = (key, W.contiguous(), b.contiguous())
-        towers[0].__dict__["_pna_amd_proj_pad_div"] = hit
-    return hit[1], hit[2]
+
+    def build():
+        lins = _pretrans_linears(towers)
+        W = torch.zeros(2 * P, len(lins) * Fi, dtype=lins[0].weight.dtype, device=lins[0].weight.device)
+        b = torch.zeros(2 * P, dtype=W.dtype, device=W.device)
+        for t, lin in enumerate(lins):
+            r = slice(t * Fi, (t + 1) * Fi)
+            W[r, r] = lin.weight[:, :Fi]
+            W[P + t * Fi:P + (t + 1) * Fi, r] = lin.weight[:, Fi:2 * Fi]
+            b[P + t * Fi:P + (t + 1) * Fi] = lin.bias
+        return W.contiguous(), b.contiguous()
+    return PF.memo(towers[0], "_pna_amd_proj_pad_div", PF._tower_tensors(towers, pre=True), P, build)
 
 
 def _projection_cache_padded_multi(towers, Fi, P):
     """The SOURCE half of _projection_cache for T towers over the whole input (divide_input=False) with every tower's block padded to P
     columns: x_src = [W_a,0 h | 0 | .. | W_a,T-1 h | 0], blocks 16-byte aligned -- the table FusedMultiTowerCall's launches read their
     tower's 16-byte strips from (the destination half W_b h + b is linear in the row's own features: folded into the dense term)."""
-    lins = [t.pretrans.fully_connected[0].linear for t in towers]
-    key = tuple((p._version, p.data_ptr(), str(p.device)) for l in lins for p in (l.weight, l.bias)) + (P,)
-    hit = towers[0].__dict__.get("_pna_amd_proj_pad_multi")
-    if hit is None or hit[0] != key:
-        T = len(lins)
-        with torch.no_grad():
-            W = torch.zeros(T * P, Fi, dtype=lins[0].weight.dtype, device=lins[0].weight.device)
-            for t, lin in enumerate(lins):
-                W[t * P:t * P + Fi] = lin.weight[:, :Fi]
-        hit = (key, W.t().contiguous(), W)                     # (Fi, T P): x_src = h @ it; (T P, Fi): pna_project_f32's layout
-        towers[0].__dict__["_pna_amd_proj_pad_multi"] = hit
-    return hit[1], hit[2]
+
+    def build():
+        lins = _pretrans_linears(towers)
+        W = torch.zeros(len(lins) * P, Fi, dtype=lins[0].weight.dtype, device=lins[0].weight.device)
+        for t, lin in enumerate(lins):
+            W[t * P:t * P + Fi] = lin.weight[:, :Fi]
+        return W.t().contiguous(), W                           # (Fi, T P): x_src = h @ it; (T P, Fi): pna_project_f32's layout
+    return PF.memo(towers[0], "_pna_amd_proj_pad_multi", PF._tower_tensors(towers, pre=True), P, build)
 
 
 def _towers_forward(towers, graph, h, e, snorm_n, divide_input):

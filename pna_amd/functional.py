@@ -6,6 +6,7 @@ import os
 import torch
 
 from . import ops
+from ._cache import DropsCachesOnConversion, drop_weight_caches, memo, tensor_key  # noqa: F401  (PF.drop_weight_caches, PF.DropsCachesOnConversion)
 
 
 def _unit_stride(t):
@@ -66,19 +67,60 @@ def aggregate(graph, x, F, aggregators, *, n_tower=1, dst_term=None, edge_term=N
                          items=graph.work_items(), edge_type=edge_type)
 
 
+def _bn_tensors(bn):
+    """weight, bias, running mean and running variance of a BatchNorm1d, None where it has none -- through the module's own dictionaries
+    (nn.Module.__getattr__ costs about 1 us per name, on every call of a 0.1 ms layer)."""
+    p, b = bn._parameters, bn._buffers
+    return [p["weight"], p["bias"], b["running_mean"], b["running_var"]]
+
+
+def _first_linear(mlp):
+    """mlp.fully_connected[0].linear through the modules' own dictionaries (nn.Module.__getattr__ and ModuleList indexing cost 4 us
+    per chain, and the cache lookups walk up to 2 T chains on every call of a 0.1 ms layer)."""
+    return mlp._modules["fully_connected"]._modules["0"]._modules["linear"]
+
+
+def _tower_tensors(towers, pre=False, post=False, bn=False, mix=None):
+    """The keyed tensor list of a builder over "every tower's first pretrans / posttrans Linear (weight, bias), BatchNorm tensors and
+    the mixing Linear": the groups the builder READS, None where a module has no such tensor."""
+    ts = []
+    for t in towers:
+        m = t._modules
+        if pre:
+            ts += _first_linear(m["pretrans"])._parameters.values()
+        if post:
+            ts += _first_linear(m["posttrans"])._parameters.values()
+        if bn:
+            ts += _bn_tensors(m["batchnorm_h"])
+    if mix is not None:
+        ts += mix._modules["linear"]._parameters.values()
+    return ts
+
+
+def _as_is(t):
+    return t
+
+
+def _fold(bn, tag, up):
+    w, b, mean, var = ts = _bn_tensors(bn)
+
+    def build():
+        cs = (up(w) if w is not None else 1.0) * torch.rsqrt(up(var) + bn.eps)
+        ct = (up(b) if b is not None else 0.0) - up(mean) * cs
+        return cs.contiguous(), ct.contiguous()
+    return memo(bn, tag, ts, bn.eps, build)
+
+
 def _fold_batchnorm(bn):
-    """Eval-mode BatchNorm1d as y = x * col_scale + col_shift; cached ON the module per parameter/buffer version so
+    """Eval-mode BatchNorm1d as y = x * col_scale + col_shift; cached ON the module per state of its parameters and buffers so
     that an inference loop does not relaunch the five little fold kernels every forward."""
-    ts = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
-    key = tuple((id(t), t._version, t.data_ptr(), str(t.device)) for t in ts) + (bn.eps,)
-    hit = bn.__dict__.get("_pna_amd_fold")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            cs = (bn.weight if bn.weight is not None else 1.0) * torch.rsqrt(bn.running_var + bn.eps)
-            ct = (bn.bias if bn.bias is not None else 0.0) - bn.running_mean * cs
-        hit = (key, cs.contiguous(), ct.contiguous(), ts)      # `ts` keeps the keyed tensors alive (id() stays unique)
-        bn.__dict__["_pna_amd_fold"] = hit
-    return hit[1], hit[2]
+    return _fold(bn, "_pna_amd_fold", _as_is)                 # (in the module's own dtype)
+
+
+def _fold_batchnorm_f32(bn):
+    """_fold_batchnorm of a bf16 BatchNorm1d, folded in fp32 from the bf16 parameters and running statistics (the bf16 epilogue
+    of pna_posttrans_bf16 takes fp32 column constants): the same body over the tensors' .float(), under a tag of its own."""
+    return _fold(bn, "_pna_amd_fold_f32", torch.Tensor.float)
 
 
 def posttrans(agg, K, weight, bias, row_scales, h_self=None, *, row_post=None, bn=None, relu=False, residual=None,
@@ -126,15 +168,9 @@ def posttrans(agg, K, weight, bias, row_scales, h_self=None, *, row_post=None, b
 
 
 def _stack_cached(owner, tag, tensors):
-    """torch.stack(tensors) cached on `owner` per (version, address, device) of every tensor: the per-tower biases and folded
-    BatchNorm constants of a layer, which would otherwise cost a concatenation launch per forward."""
-    key = tuple((t._version, t.data_ptr(), str(t.device)) for t in tensors)
-    hit = owner.__dict__.get(tag)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, torch.stack([t.detach() for t in tensors]).contiguous())
-        owner.__dict__[tag] = hit
-    return hit[1]
+    """torch.stack(tensors) cached on `owner` per state of every tensor: the per-tower biases and folded BatchNorm constants of a
+    layer, which would otherwise cost a concatenation launch per forward."""
+    return memo(owner, tag, tensors, None, lambda: torch.stack([t.detach() for t in tensors]).contiguous())
 
 
 def posttrans_towers(agg, K, towers_lin, row_scales, hs, h_shared, out, row_post=None, bns=None, relu=False):
@@ -196,30 +232,6 @@ def bf16_small_applies(graph, V, *, T, Fi, Fo, A, divide_input, posttrans_affine
     return graph.heavy_schedule().n_heavy == 0
 
 
-def drop_weight_caches(module):
-    """Remove every `_pna_amd_*` entry from `module`, its submodules and their parameters and buffers.  Called from `_apply` (.to(),
-    .float(), .cuda(), ...): there every parameter gets NEW storage under an UNCHANGED version counter, and the allocator may hand the
-    converted tensor the address its predecessor just freed (.to(bfloat16).float() does exactly that) -- the (version, address, device)
-    keys of the caches cannot tell that state from the one they were built for.  Nothing on the per-call path: the next call rebuilds."""
-    for m in module.modules():
-        for owner in [m, *m._parameters.values(), *m._buffers.values()]:
-            d = getattr(owner, "__dict__", None)
-            if d:
-                for tag in [k for k in d if isinstance(k, str) and k.startswith("_pna_amd_")]:
-                    del d[tag]
-
-
-class DropsCachesOnConversion:
-    """Mixin of every layer and net (before nn.Module in the bases): a conversion -- `_apply`, the one route of .to(), .float(), .cuda(),
-    .cpu() -- drops every cached operand below the module.  A submodule of another class converted ON ITS OWN
-    (`layer.mixing_network.to(...)`) does not pass here: convert the layer."""
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        drop_weight_caches(self)
-        return out
-
-
 def _no_plan():
     """What a copied / unpickled layer holds in place of its one-call plan (_SmallTowerPlan.__reduce__): nothing."""
     return None
@@ -239,20 +251,13 @@ class _SmallTowerPlan:
         from . import _lib
         t0 = towers[0]
         self.edge_dim = t0.edge_dim if t0.edge_features else 0
-        self._etab = None                                      # (type-row tensor of the graph's cache, its projection W_e . ef_t)
+        self._etab = None                                      # (edge_table's entry: the graph's type rows projected, W_e . ef_t)
         pre = [t.pretrans.fully_connected[0].linear for t in towers]
         post = [t.posttrans.fully_connected[0].linear for t in towers]
-        ts = [p for l in pre + post for p in (l.weight, l.bias) if p is not None]
-        if t0.batch_norm:
-            for t in towers:
-                bn = t.batchnorm_h
-                if bn.training:
-                    raise RuntimeError("only an eval-mode BatchNorm (running statistics) can be folded into the epilogue")
-                ts += [x for x in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if x is not None]
-        if mix is not None:
-            ts += [p for p in (mix.linear.weight, mix.linear.bias) if p is not None]
-        self.ts = ts
-        self.versions = self._state()
+        if t0.batch_norm and any(t.batchnorm_h.training for t in towers):
+            raise RuntimeError("only an eval-mode BatchNorm (running statistics) can be folded into the epilogue")
+        self.ts = _tower_tensors(towers, pre=True, post=True, bn=t0.batch_norm, mix=mix)
+        self.versions = tensor_key(self.ts)
         T, Fi, Fo, S = len(towers), t0.in_dim, t0.out_dim, len(t0.scalers)
         self.T, self.Fi, self.Fo, self.S, self.divide_input = T, Fi, Fo, S, divide_input
         with torch.no_grad():
@@ -300,22 +305,13 @@ class _SmallTowerPlan:
         # THIS layer's device buffers -- a copy carries no plan and builds its own on its first call
         return (_no_plan, ())
 
-    def _state(self):
-        # (version, storage address, device) per tensor: `param.data = other` (EMA / SWA swaps, vector_to_parameters, offloading)
-        # keeps the version counter but moves the address -- the same key the other weight caches use
-        return [(x._version, x.data_ptr(), str(x.device)) for x in self.ts]
-
     def stale(self):
-        return self._state() != self.versions
+        return tensor_key(self.ts) != self.versions
 
     def edge_table(self, etab):
-        """(n_types, T*Fi) = type rows @ W_e^T, kept while the graph's type table (graph.edge_type_table: cached per feature tensor)
-        is the same object -- the weights' own staleness replaces the whole plan."""
-        hit = self._etab
-        if hit is None or hit[0] is not etab[1]:
-            with torch.no_grad():
-                hit = self._etab = (etab[1], (etab[1].to(torch.float32) @ self.We.t()).contiguous())
-        return hit[1]
+        """(n_types, T*Fi) = type rows @ W_e^T, kept per state of the graph's type rows (graph.edge_type_table: cached per feature
+        tensor) -- the weights' own staleness replaces the whole plan."""
+        return memo(self, "_etab", [etab[1]], None, lambda: (etab[1].to(torch.float32) @ self.We.t()).contiguous())
 
     def run(self, graph, h, snorm_n, row_scales, residual, etab=None):
         if h.stride(-1) != 1:
@@ -394,13 +390,14 @@ def degree_grouped_aggregate(layer, graph, h, plan, out=None, x=None):
 
 
 def _simple_layer_state(layer):
-    """(version, address) of every tensor a cached FusedDegreeCall of `layer` snapshots: the posttrans Linear and the BatchNorm."""
+    """The state (tensor_key) of every tensor a cached FusedDegreeCall of `layer` snapshots: the posttrans Linear and the BatchNorm.
+    Part of a dictionary key of SimpleLayerRows._calls; the cached call holds `layer`, which holds these tensors: the ids stay taken."""
     lin = layer.posttrans.fully_connected[0].linear
     ts = [lin.weight, lin.bias]
     if layer.batch_norm:
         bn = layer.batchnorm_h
         ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    return tuple((t._version, t.data_ptr()) for t in ts if t is not None)
+    return tensor_key(ts)
 
 
 def _layer_tail_operands(layer, h):
@@ -477,15 +474,10 @@ def _tower_collapsed_weights(owner, towers, mix, divide_input):
     layer (combined images W_D, three-block rest) applies unchanged; formed in float64, rounded once.  Cached on `owner`."""
     t0 = towers[0]
     T, Fi, Fo, S = len(towers), t0.in_dim, t0.out_dim, len(t0.scalers)
-    lins = [t.posttrans.fully_connected[0].linear for t in towers]
-    ts = [p for l in lins for p in (l.weight, l.bias)] + [mix.linear.weight, mix.linear.bias]
-    if t0.batch_norm:
-        ts += [x for t in towers for x in (t.batchnorm_h.weight, t.batchnorm_h.bias, t.batchnorm_h.running_mean, t.batchnorm_h.running_var)]
-    key = tuple((x._version, x.data_ptr(), str(x.device)) for x in ts if x is not None) + (divide_input,)
-    hit = owner.__dict__.get("_pna_amd_collapsed")
-    if hit is not None and hit[0] == key:
-        return hit[1:]
-    with torch.no_grad():
+    ts = _tower_tensors(towers, post=True, bn=t0.batch_norm, mix=mix)
+
+    def build():
+        lins = [t.posttrans.fully_connected[0].linear for t in towers]
         Wm = mix.linear.weight.double()
         out = Wm.shape[0]
         in_dim = T * Fi if divide_input else Fi
@@ -509,9 +501,8 @@ def _tower_collapsed_weights(owner, towers, mix, divide_input):
                 Wv[:, s_ * K + t * 4 * Fi:s_ * K + (t + 1) * 4 * Fi] = C[:, Fi + s_ * 4 * Fi:Fi + (s_ + 1) * 4 * Fi]
             hcol = T * 4 * Fi + (t * Fi if divide_input else 0)
             Wv[:, hcol:hcol + Fi] += C[:, :Fi]                                   # block 0 (the identity scaler's) carries the h panel
-        res = (Wv.float().contiguous(), d.float().contiguous(), c.float().contiguous(), torch.ones(out, dtype=torch.float32, device=Wm.device), K)
-    owner.__dict__["_pna_amd_collapsed"] = (key,) + res
-    return res
+        return (Wv.float().contiguous(), d.float().contiguous(), c.float().contiguous(), torch.ones(out, dtype=torch.float32, device=Wm.device), K)
+    return memo(owner, "_pna_amd_collapsed", ts, divide_input, build)
 
 
 def tower_layer_degree_grouped_applies(layer, graph, h):
@@ -633,19 +624,17 @@ def _tower_flat_weights(layer, towers, mix):
     T, Fi = len(towers), towers[0].in_dim
     if T == 1:
         return Wv, d, c, ones, K
-    hit = layer.__dict__.get("_pna_amd_flat")
-    if hit is not None and hit[0] is Wv:
-        return hit[1], d, c, ones, K
-    S = Wv.shape[1] // K
-    Fe = T * Fi
-    a_ = torch.arange(4, device=Wv.device).view(4, 1, 1)
-    t_ = torch.arange(T, device=Wv.device).view(1, T, 1)
-    f_ = torch.arange(Fi, device=Wv.device).view(1, 1, Fi)
-    cols = torch.cat([(t_ * 4 * Fi + a_ * Fi + f_).reshape(-1), torch.arange(4 * Fe, K, device=Wv.device)])      # new column -> old column
-    idx = torch.cat([s_ * K + cols for s_ in range(S)])
-    Wp = Wv.index_select(1, idx).contiguous()
-    layer.__dict__["_pna_amd_flat"] = (Wv, Wp)
-    return Wp, d, c, ones, K
+
+    def build():
+        S = Wv.shape[1] // K
+        Fe = T * Fi
+        a_ = torch.arange(4, device=Wv.device).view(4, 1, 1)
+        t_ = torch.arange(T, device=Wv.device).view(1, T, 1)
+        f_ = torch.arange(Fi, device=Wv.device).view(1, 1, Fi)
+        cols = torch.cat([(t_ * 4 * Fi + a_ * Fi + f_).reshape(-1), torch.arange(4 * Fe, K, device=Wv.device)])      # new column -> old column
+        idx = torch.cat([s_ * K + cols for s_ in range(S)])
+        return Wv.index_select(1, idx).contiguous()
+    return memo(layer, "_pna_amd_flat", [Wv], None, build), d, c, ones, K
 
 
 _SIDE_STREAMS = {}
@@ -922,17 +911,12 @@ def _tower_pass_weights(layer, towers, mix):
     and the self panel W_self h_v: (N, in_dim + S in_dim) = [W_self | M_0 | .. | M_S-1], the layout of functional.posttrans with h_self = agg = h.
     Formed in float64, rounded once.  Cached on the layer."""
     Wv, d, c, ones, K = _tower_collapsed_weights(layer, towers, mix, False)
-    # Wd and beta read every tower's PRETRANS weight and bias, which the collapsed weight's key does not cover: they are keyed here, like
-    # _projection_cache_padded_multi keys them (host integers only: no device synchronisation, no tensor allocation)
-    key = tuple((p._version, p.data_ptr(), str(p.device)) for tw in towers
-                for p in (tw.pretrans.fully_connected[0].linear.weight, tw.pretrans.fully_connected[0].linear.bias) if p is not None)
-    hit = layer.__dict__.get("_pna_amd_pass_w")
-    if hit is not None and hit[0] is Wv and hit[1] == key:
-        return hit[2:]
-    T, Fi = len(towers), towers[0].in_dim
-    S = Wv.shape[1] // K
-    N = Wv.shape[0]
-    with torch.no_grad():
+    # Wd and beta read every tower's PRETRANS weight and bias, which the collapsed weight's key does not cover: keyed here beside Wv
+
+    def build():
+        T, Fi = len(towers), towers[0].in_dim
+        S = Wv.shape[1] // K
+        N = Wv.shape[0]
         Ws = []
         for t in range(T):
             W = torch.empty(N, S * 4 * Fi, dtype=torch.float32, device=Wv.device)
@@ -958,9 +942,8 @@ def _tower_pass_weights(layer, towers, mix):
         for s_ in range(S):
             Wr[:, s_ * (Ka + N):s_ * (Ka + N) + Ka] = Wv[:, s_ * K:s_ * K + Ka]
         Wr[:, Ka:Ka + N] = torch.eye(N, dtype=torch.float32, device=Wv.device)
-    res = (Ws, Wd.float().contiguous(), beta.float().contiguous(), Wr.contiguous(), d, c, ones)
-    layer.__dict__["_pna_amd_pass_w"] = (Wv, key) + res
-    return res
+        return (Ws, Wd.float().contiguous(), beta.float().contiguous(), Wr.contiguous(), d, c, ones)
+    return memo(layer, "_pna_amd_pass_w", [Wv] + _tower_tensors(towers, pre=True), None, build)
 
 
 DENSE_TERM_RESIDENT = True          # FusedMultiTowerCall.dense_term through pna_project_scaled_f32 where it applies (False: contraction + rank-S update)
@@ -997,12 +980,9 @@ class FusedMultiTowerCall:
         self._part_full = torch.empty(V, out_pitch(N), dtype=torch.float32, device=dev)
         self.part = part = self._part_full[:, :N]
         self.part2 = torch.empty(V, out_pitch(N), dtype=torch.float32, device=dev)[:, :N] if T > 1 else None
-        bp = layer.__dict__.get("_pna_amd_beta_pad")          # beta padded to the buffer's pitch: the rank-S update runs in place on the whole buffer
-        if bp is None or bp[0] is not self.beta or bp[1].shape[1] != out_pitch(N):
-            padded = torch.zeros(self.beta.shape[0], out_pitch(N), dtype=torch.float32, device=dev)
-            padded[:, :N] = self.beta
-            bp = layer.__dict__["_pna_amd_beta_pad"] = (self.beta, padded)
-        self.beta_pad = bp[1]
+        # beta padded to the buffer's pitch: the rank-S update runs in place on the whole buffer
+        self.beta_pad = memo(layer, "_pna_amd_beta_pad", [self.beta], out_pitch(N),
+                             lambda: torch.nn.functional.pad(self.beta, (0, out_pitch(N) - N)))
         self.res = res = h if layer.residual else None
         self.slope = float(mix.activation.negative_slope)
         if t0.graph_norm and snorm_n is not None:
@@ -1259,9 +1239,8 @@ class _SmallSimplePlan(_SmallTowerPlan):
         bn = layer.batchnorm_h if layer.batch_norm else None
         if bn is not None and bn.training:
             raise RuntimeError("only an eval-mode BatchNorm (running statistics) can be folded into the epilogue")
-        self.ts = [x for x in (lin.weight, lin.bias) if x is not None] + \
-                  ([x for x in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if x is not None] if bn is not None else [])
-        self.versions = self._state()
+        self.ts = [lin.weight, lin.bias] + (_bn_tensors(bn) if bn is not None else [])
+        self.versions = tensor_key(self.ts)
         Fi, Fo, S = layer.in_dim, layer.out_dim, len(layer.scalers)
         self.T, self.Fi, self.Fo, self.S, self.divide_input = 1, Fi, Fo, S, False
         dev = lin.weight.device
@@ -1399,21 +1378,6 @@ class SimpleLayerRows:
                           col_scale=cs, col_shift=ct, relu=True, residual=x[r0:r1] if layer.residual else None)
 
 
-def _fold_batchnorm_f32(bn):
-    """_fold_batchnorm of a bf16 BatchNorm1d, folded in fp32 from the bf16 parameters and running statistics (the bf16 epilogue
-    of pna_posttrans_bf16 takes fp32 column constants); cached on the module like _fold_batchnorm."""
-    ts = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
-    key = tuple((id(t), t._version, t.data_ptr(), str(t.device)) for t in ts) + (bn.eps,)
-    hit = bn.__dict__.get("_pna_amd_fold_f32")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            cs = (bn.weight.float() if bn.weight is not None else 1.0) * torch.rsqrt(bn.running_var.float() + bn.eps)
-            ct = (bn.bias.float() if bn.bias is not None else 0.0) - bn.running_mean.float() * cs
-        hit = (key, cs.contiguous(), ct.contiguous(), ts)
-        bn.__dict__["_pna_amd_fold_f32"] = hit
-    return hit[1], hit[2]
-
-
 def simple_layer_bf16(layer, graph, h):
     """PNASimpleLayer.forward (models/dgl/pna_layer.py:197-216) in inference on bf16 features and parameters: the bf16 aggregate of
     pna_segreduce_fwd_bf16 (blocks round8(F) columns apart, fp32 statistics), then pna_posttrans_bf16 with the degree scalers,
@@ -1460,11 +1424,6 @@ def simple_layer_bf16(layer, graph, h):
     return y
 
 
-def _tensor_key(ts):
-    # (per call of every bf16 layer: the device and shape objects compare like their string / tuple forms and cost a third)
-    return tuple((id(t), t._version, t.data_ptr(), t.device, t.dtype, t.shape) for t in ts)
-
-
 def _tower_images_bf16(towers, divide_input):
     """The weight images of the bf16 tower layer (ops.contract_image_bf16), built once per version of EVERY tensor they are made
     from -- the pretrans and first posttrans Linear and the BatchNorm tensors of every tower -- and cached on the first tower.
@@ -1476,22 +1435,18 @@ def _tower_images_bf16(towers, divide_input):
       self  (1, T No, Kin) the posttrans weight on the tower's own features
     Kin = T Fi with divide_input (tower t reads the input slice [t Fi, (t+1) Fi): block-diagonal), else Fi."""
     t0 = towers[0]
-    pre = [t.pretrans.fully_connected[0].linear for t in towers]
-    post = [t.posttrans.fully_connected[0].linear for t in towers]
     bns = [t.batchnorm_h for t in towers] if t0.batch_norm and t0.posttrans.is_affine else []
-    ts = [p for l in pre + post for p in (l.weight, l.bias)]
-    ts += [x for bn in bns for x in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if x is not None]
-    key = (_tensor_key(ts), divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns))
-    hit = t0.__dict__.get("_pna_amd_bf16_images")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    T, Fi, ed, No = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
-    A, S = len(t0.aggregators), len(t0.scalers)
-    P = (T * Fi + 7) // 8 * 8
-    Kin = T * Fi if divide_input else Fi
-    dev, bf = pre[0].weight.device, torch.bfloat16
-    perm = sorted(range(S), key=lambda s: t0.scalers[s] != "identity")           # stable: an identity scaler first
-    with torch.no_grad():
+    ts = _tower_tensors(towers, pre=True, post=True, bn=bool(bns))
+
+    def build():
+        pre = [t.pretrans.fully_connected[0].linear for t in towers]
+        post = [t.posttrans.fully_connected[0].linear for t in towers]
+        T, Fi, ed, No = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
+        A, S = len(t0.aggregators), len(t0.scalers)
+        P = (T * Fi + 7) // 8 * 8
+        Kin = T * Fi if divide_input else Fi
+        dev, bf = pre[0].weight.device, torch.bfloat16
+        perm = sorted(range(S), key=lambda s: t0.scalers[s] != "identity")           # stable: an identity scaler first
         proj = torch.zeros(1, 2 * P, Kin, dtype=bf, device=dev)
         pbias = torch.zeros(2 * P, dtype=bf, device=dev)
         edge = torch.zeros(1, P, max(ed, 1), dtype=bf, device=dev)
@@ -1524,41 +1479,26 @@ def _tower_images_bf16(towers, divide_input):
             folds = [_fold_batchnorm_f32(bn) for bn in bns]
             res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
             res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
-    t0.__dict__["_pna_amd_bf16_images"] = (key, res, ts)                           # (ts: the addresses in the key stay taken)
-    return res
+        return res
+    return memo(t0, "_pna_amd_bf16_images", ts, (divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns)), build)
 
 
 def _small_simple_images_bf16(layer):
     """The images of pna_tower_layer_bf16 in its PNASimpleLayer form: post (1, S, round16(N), round32(A round8(F))) from the
     reference-layout posttrans weight (N, S A F), the bias and the fp32-folded BatchNorm; cached per version of every source tensor."""
     lin, bn = layer.posttrans.fully_connected[0].linear, layer.batchnorm_h if layer.batch_norm else None
-    ts = [lin.weight, lin.bias] + ([x for x in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if x is not None] if bn else [])
+    ts = [lin.weight, lin.bias] + (_bn_tensors(bn) if bn else [])
     A, S, F, N = len(layer.aggregators), len(layer.scalers), layer.in_dim, lin.out_features
-    key = (_tensor_key(ts), A, S, bn.eps if bn else None)
-    hit = layer.__dict__.get("_pna_amd_bf16_small")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    Fp, Kp = (F + 7) // 8 * 8, (A * ((F + 7) // 8 * 8) + 31) // 32 * 32
-    with torch.no_grad():
+
+    def build():
+        Fp, Kp = (F + 7) // 8 * 8, (A * ((F + 7) // 8 * 8) + 31) // 32 * 32
         blk = torch.zeros(S, N, A, Fp, dtype=torch.bfloat16, device=lin.weight.device)
         blk[..., :F] = lin.weight.reshape(N, S, A, F).permute(1, 0, 2, 3)
         post = torch.zeros(1, S, (N + 15) // 16 * 16, Kp, dtype=torch.bfloat16, device=lin.weight.device)
         post[0, :, :N, :A * Fp] = blk.reshape(S, N, A * Fp)
         cs, ct = _fold_batchnorm_f32(bn) if bn else (None, None)
-    res = {"post": post, "post_bias": lin.bias, "cs": cs, "ct": ct}
-    layer.__dict__["_pna_amd_bf16_small"] = (key, res, ts)
-    return res
-
-
-def _first_linear(mlp):
-    """mlp.fully_connected[0].linear through the modules' own dictionaries (nn.Module.__getattr__ and ModuleList indexing cost 4 us
-    per chain, and the image lookups below walk 2 T chains on every call of a 0.1 ms layer)."""
-    return mlp._modules["fully_connected"]._modules["0"]._modules["linear"]
-
-
-def _bn_tensors(bn):
-    p, b = bn._parameters, bn._buffers
-    return [x for x in (p["weight"], p["bias"], b["running_mean"], b["running_var"]) if x is not None]
+        return {"post": post, "post_bias": lin.bias, "cs": cs, "ct": ct}
+    return memo(layer, "_pna_amd_bf16_small", ts, (A, S, bn.eps if bn else None), build)
 
 
 def _small_images_bf16(towers, mix, divide_input):
@@ -1570,25 +1510,18 @@ def _small_images_bf16(towers, mix, divide_input):
       post  [T][S][Fop][Kp] (each tower's OWN blocks, scalers in the layer's order) followed by the self blocks [T][Fop][Khp], flat
       mix   (round16(No), round32(T Fo))"""
     t0 = towers[0]
-    pre = [_first_linear(t._modules["pretrans"]) for t in towers]
-    post = [_first_linear(t._modules["posttrans"]) for t in towers]
     bns = [t._modules["batchnorm_h"] for t in towers] if t0.batch_norm else []
-    ts = [l._parameters[k] for l in pre + post for k in ("weight", "bias")]
-    for bn in bns:
-        ts += _bn_tensors(bn)
-    if mix is not None:
-        ts += [mix.linear.weight, mix.linear.bias]
-    key = (_tensor_key(ts), divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns), mix is not None)
-    hit = t0.__dict__.get("_pna_amd_bf16_small")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    T, Fi, ed, Fo = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
-    A, S = len(t0.aggregators), len(t0.scalers)
-    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
-    Fp, Fop, Kp, Khp = r(Fi, 8), r(Fo, 16), r(A * r(Fi, 8), 32), r(Fi, 32)
-    Kin = T * Fi if divide_input else Fi
-    dev, bf = pre[0].weight.device, torch.bfloat16
-    with torch.no_grad():
+    ts = _tower_tensors(towers, pre=True, post=True, bn=t0.batch_norm, mix=mix)
+
+    def build():
+        pre = [t.pretrans.fully_connected[0].linear for t in towers]
+        post = [t.posttrans.fully_connected[0].linear for t in towers]
+        T, Fi, ed, Fo = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
+        A, S = len(t0.aggregators), len(t0.scalers)
+        r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
+        Fp, Fop, Kp, Khp = r(Fi, 8), r(Fo, 16), r(A * r(Fi, 8), 32), r(Fi, 32)
+        Kin = T * Fi if divide_input else Fi
+        dev, bf = pre[0].weight.device, torch.bfloat16
         proj = torch.zeros(1, 2 * T * Fp, Kin, dtype=bf, device=dev)
         pbias = torch.zeros(2 * T * Fp, dtype=bf, device=dev)
         edge = torch.zeros(1, T * Fp, max(ed, 1), dtype=bf, device=dev)
@@ -1623,14 +1556,17 @@ def _small_images_bf16(towers, mix, divide_input):
             res["mix"] = torch.zeros(r(No, 16), r(T * Fo, 32), dtype=bf, device=dev)
             res["mix"][:No, :T * Fo] = mix.linear.weight
             res["mix_bias"] = mix.linear.bias
-    t0.__dict__["_pna_amd_bf16_small"] = (key, res, ts)                            # (ts: the addresses in the key stay taken)
-    return res
+        return res
+    return memo(t0, "_pna_amd_bf16_small", ts,
+                (divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns), mix is not None), build)
 
 
 def _small_edge_table_bf16(im, rows, ed, width):
     """bf16 (n_types, width) = R(rows W_e^T) for the <= 4 type rows of Graph.edge_type_table, kept with the images while the rows are
-    the same storage at the same version (PNANet's rows are its embedding weight: one launch per weight state, not per call)."""
-    key = (rows.data_ptr(), rows._version, tuple(rows.shape), str(rows.device))
+    the same storage at the same version (PNANet's rows are its embedding weight: one launch per weight state, not per call).  A key
+    of its own, WITHOUT the object: PNANet registers its rows on the graph in every forward and the graph keeps `rows.detach()` -- a new
+    tensor object per forward over the same storage and version counter, which _cache.tensor_key would take for a new state."""
+    key = (rows.data_ptr(), rows._version, rows.shape, rows.dtype, rows.device)
     hit = im["etab"]
     if hit is None or hit[0] != key:
         with torch.no_grad():
@@ -1682,13 +1618,7 @@ def _towers_small_bf16(towers, mix, graph, h, e, snorm_n, divide_input, residual
 def _mix_image_bf16(mix):
     """The pna_contract_bf16 image of the mixing weight, cached on the module per weight state."""
     w = mix.linear.weight
-    key = _tensor_key([w])
-    hit = mix.__dict__.get("_pna_amd_bf16_mix")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, ops.contract_image_bf16(w.unsqueeze(0)), w)
-        mix.__dict__["_pna_amd_bf16_mix"] = hit
-    return hit[1]
+    return memo(mix, "_pna_amd_bf16_mix", [w], None, lambda: ops.contract_image_bf16(w.unsqueeze(0)))
 
 
 def towers_bf16(towers, graph, h, e, snorm_n, divide_input):

@@ -13,6 +13,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._cache import memo, tensor_key
 from .graph import HeavySchedule
 
 # Arithmetic of the posttrans contraction: "f32" = v_mfma_f32_16x16x4_f32 (bitwise an fmaf chain), "bf16x3" = fp32
@@ -122,53 +123,34 @@ def segreduce(rowptr: torch.Tensor, col: Optional[torch.Tensor], x: torch.Tensor
     return (out, argmax, argmin) if want_arg else out
 
 
-def pack_posttrans_weight(weight: torch.Tensor, K: int, n_scaler: int, Kh: int):
-    """(w_img, wh_img) tile images of a reference-layout posttrans weight (N, Kh + n_scaler*K).  Cached on the weight
-    tensor object per (version, storage address, device): inference packs once, training re-packs after every optimizer
-    step, and `module.to(device)` / `param.data = ...` swaps (EMA, SWA) -- which keep the Parameter object and its version
-    counter -- re-pack too.  The cache lives ON the tensor object: it is never looked up by address alone."""
-    key = (weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), weight.stride(0), K, n_scaler, Kh)
-    hit = getattr(weight, "_pna_amd_pack", None)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
+def _pack_posttrans(weight, K, n_scaler, Kh, size_fn, unit, pack_fn):
+    """(w_img, wh_img) of a reference-layout posttrans weight through one of the two packers of the C ABI (entry points by name);
+    `size_fn` answers in units of `unit` bytes."""
     L = _lib.lib()
     N = weight.shape[0]
     nh = ctypes.c_int64(0)
-    nw = L.pna_posttrans_packed_floats(K, N, n_scaler, Kh, ctypes.byref(nh))
-    w_img = torch.empty(nw, dtype=torch.float32, device=weight.device)
-    wh_img = torch.empty(max(nh.value, 1), dtype=torch.float32, device=weight.device) if Kh else None
-    rc = L.pna_posttrans_pack_f32(_lib.dev_ptr(weight, torch.float32, "weight"), _ld(weight), N, K, n_scaler, Kh,
-                                  _lib.dev_ptr(w_img, torch.float32, "w_img"), _lib.dev_ptr(wh_img, torch.float32, "wh_img"),
-                                  _lib.stream_ptr(weight.device))
-    _lib.check(rc, "pna_posttrans_pack_f32")
-    try:
-        weight._pna_amd_pack = (key, w_img, wh_img)
-    except AttributeError:
-        pass
+    nw = getattr(L, size_fn)(K, N, n_scaler, Kh, ctypes.byref(nh))
+    w_img = torch.empty(nw * unit // 4, dtype=torch.float32, device=weight.device)
+    wh_img = torch.empty(max(nh.value * unit // 4, 1), dtype=torch.float32, device=weight.device) if Kh else None
+    rc = getattr(L, pack_fn)(_lib.dev_ptr(weight, torch.float32, "weight"), _ld(weight), N, K, n_scaler, Kh,
+                             _lib.dev_ptr(w_img, torch.float32, "w_img"), _lib.dev_ptr(wh_img, torch.float32, "wh_img"),
+                             _lib.stream_ptr(weight.device))
+    _lib.check(rc, pack_fn)
     return w_img, wh_img
+
+
+def pack_posttrans_weight(weight: torch.Tensor, K: int, n_scaler: int, Kh: int):
+    """(w_img, wh_img) tile images of a reference-layout posttrans weight (N, Kh + n_scaler*K).  Cached ON the weight tensor object
+    (never looked up by address alone) per state of it: inference packs once, training re-packs after every optimizer step, and
+    `param.data = ...` swaps (EMA, SWA) -- which keep the Parameter object and its version counter -- re-pack too."""
+    return memo(weight, "_pna_amd_pack", [weight], (K, n_scaler, Kh),
+                lambda: _pack_posttrans(weight, K, n_scaler, Kh, "pna_posttrans_packed_floats", 4, "pna_posttrans_pack_f32"))
 
 
 def pack_posttrans_weight_x3(weight: torch.Tensor, K: int, n_scaler: int, Kh: int):
     """(w_img, wh_img) bf16x3 tile images (pna_posttrans_x3_pack_f32); cached like pack_posttrans_weight."""
-    key = (weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), weight.stride(0), K, n_scaler, Kh)
-    hit = getattr(weight, "_pna_amd_pack_x3", None)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    L = _lib.lib()
-    N = weight.shape[0]
-    nh = ctypes.c_int64(0)
-    nw = L.pna_posttrans_x3_packed_bytes(K, N, n_scaler, Kh, ctypes.byref(nh))
-    w_img = torch.empty(nw // 4, dtype=torch.float32, device=weight.device)
-    wh_img = torch.empty(max(nh.value // 4, 1), dtype=torch.float32, device=weight.device) if Kh else None
-    rc = L.pna_posttrans_x3_pack_f32(_lib.dev_ptr(weight, torch.float32, "weight"), _ld(weight), N, K, n_scaler, Kh,
-                                     _lib.dev_ptr(w_img, torch.float32, "w_img"), _lib.dev_ptr(wh_img, torch.float32, "wh_img"),
-                                     _lib.stream_ptr(weight.device))
-    _lib.check(rc, "pna_posttrans_x3_pack_f32")
-    try:
-        weight._pna_amd_pack_x3 = (key, w_img, wh_img)
-    except AttributeError:
-        pass
-    return w_img, wh_img
+    return memo(weight, "_pna_amd_pack_x3", [weight], (K, n_scaler, Kh),
+                lambda: _pack_posttrans(weight, K, n_scaler, Kh, "pna_posttrans_x3_packed_bytes", 1, "pna_posttrans_x3_pack_f32"))
 
 
 def posttrans_dw(gy: torch.Tensor, a_mat: torch.Tensor, K: int, h: Optional[torch.Tensor], row_scales: Sequence[Optional[torch.Tensor]],
@@ -230,7 +212,7 @@ def posttrans_dw_grouped(gy, a_mat, K, h, row_scales, plan, want_bias=True, a_pl
     a_mat = a_mat if a_mat.stride(1) == 1 else a_mat.contiguous()
     if h is not None and h.stride(1) != 1:
         h = h.contiguous()
-    key = tuple(None if rs is None else (rs.data_ptr(), rs._version) for rs in row_scales)
+    key = tensor_key(row_scales)
     hit = plan.__dict__.get("_dw_gscale")
     if hit is None or hit[0] != key:
         gscale = torch.ones(plan.G, S, dtype=torch.float32, device=dev)
@@ -238,7 +220,7 @@ def posttrans_dw_grouped(gy, a_mat, K, h, row_scales, plan, want_bias=True, a_pl
             if rs is not None:
                 gscale[:, s] = rs.reshape(-1)[plan.group_first_row]
         rest = [None if rs is None else rs.reshape(-1)[plan.rest_rows].unsqueeze(1).contiguous() for rs in row_scales] if plan.NR else None
-        hit = plan.__dict__["_dw_gscale"] = (key, gscale.contiguous(), rest)
+        hit = plan.__dict__["_dw_gscale"] = (key, gscale.contiguous(), rest, list(row_scales))    # (the keyed tensors: their ids stay taken)
     gscale, rest_scales = hit[1], hit[2]
     gw = torch.empty(N, Kh + S * K, dtype=torch.float32, device=dev)
     gb = torch.empty(N, dtype=torch.float32, device=dev) if want_bias else None
@@ -372,25 +354,20 @@ def _posttrans_grouped(a_mat, K, weight, row_scales, bias, out, row_post, col_sc
 def pack_fused_weight(weight: torch.Tensor, F: int, n_scaler: int):
     """Packed image of a PNASimpleLayer posttrans weight (N, S*4*F) for pna_fused_simple_f32: every aggregator block
     zero-padded from F to round_up(F, 4) input columns.  Cached on the weight object per version."""
-    key = (weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), F, n_scaler)
-    hit = getattr(weight, "_pna_amd_fpack", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    N, B4 = weight.shape[0], (F + 3) // 4 * 4
-    wp = torch.nn.functional.pad(weight.detach().reshape(N, n_scaler * 4, F), (0, B4 - F)).reshape(N, n_scaler * 4 * B4)
-    wp = wp.contiguous()
-    L = _lib.lib()
-    nh = ctypes.c_int64(0)
-    nw = L.pna_posttrans_packed_floats(4 * B4, N, n_scaler, 0, ctypes.byref(nh))
-    w_img = torch.empty(nw, dtype=torch.float32, device=weight.device)
-    rc = L.pna_posttrans_pack_f32(_lib.dev_ptr(wp, torch.float32, "weight"), _ld(wp), N, 4 * B4, n_scaler, 0,
-                                  _lib.dev_ptr(w_img, torch.float32, "w_img"), None, _lib.stream_ptr(weight.device))
-    _lib.check(rc, "pna_posttrans_pack_f32")
-    try:
-        weight._pna_amd_fpack = (key, w_img)
-    except AttributeError:
-        pass
-    return w_img
+
+    def build():
+        N, B4 = weight.shape[0], (F + 3) // 4 * 4
+        wp = torch.nn.functional.pad(weight.detach().reshape(N, n_scaler * 4, F), (0, B4 - F)).reshape(N, n_scaler * 4 * B4)
+        wp = wp.contiguous()
+        L = _lib.lib()
+        nh = ctypes.c_int64(0)
+        nw = L.pna_posttrans_packed_floats(4 * B4, N, n_scaler, 0, ctypes.byref(nh))
+        w_img = torch.empty(nw, dtype=torch.float32, device=weight.device)
+        rc = L.pna_posttrans_pack_f32(_lib.dev_ptr(wp, torch.float32, "weight"), _ld(wp), N, 4 * B4, n_scaler, 0,
+                                      _lib.dev_ptr(w_img, torch.float32, "w_img"), None, _lib.stream_ptr(weight.device))
+        _lib.check(rc, "pna_posttrans_pack_f32")
+        return w_img
+    return memo(weight, "_pna_amd_fpack", [weight], (F, n_scaler), build)
 
 
 def fused_simple(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, weight: torch.Tensor,
@@ -514,20 +491,13 @@ def posttrans_towers(agg: torch.Tensor, K: int, weights: Sequence[torch.Tensor],
     if arith == "bf16x3" and S > 3:
         arith = "f32"
     x3 = arith == "bf16x3" or (arith == "auto" and S <= 3 and M >= X3_MIN_ROWS)
-    # one buffer holding the T packed images back to back, cached on the first weight per (version, address) of all of them
-    key = tuple((w._version, w.data_ptr(), str(w.device)) for w in weights) + (K, S, Kh, x3)
-    hit = getattr(weights[0], "_pna_amd_tower_pack", None)
-    if hit is None or hit[0] != key:
+    def build():      # one buffer holding the T packed images back to back
         imgs = [(pack_posttrans_weight_x3 if x3 else pack_posttrans_weight)(w if w.stride(-1) == 1 else w.contiguous(), K, S, Kh)
                 for w in weights]
         w_all = torch.cat([i[0].reshape(-1) for i in imgs])
         wh_all = torch.cat([i[1].reshape(-1) for i in imgs]) if Kh else None
-        hit = (key, w_all, wh_all, imgs[0][0].numel(), imgs[0][1].numel() if Kh else 0)
-        try:
-            weights[0]._pna_amd_tower_pack = hit
-        except AttributeError:
-            pass
-    _, w_all, wh_all, w_stride, wh_stride = hit
+        return w_all, wh_all, imgs[0][0].numel(), imgs[0][1].numel() if Kh else 0
+    w_all, wh_all, w_stride, wh_stride = memo(weights[0], "_pna_amd_tower_pack", list(weights), (K, S, Kh, x3), build)
     g = _lib.PnaPosttransArgs()
     g.a, g.lda, g.M, g.K, g.N, g.n_scaler = _lib.dev_ptr(agg, torch.float32, "a"), _ld(agg), M, K, N, S
     for i, rs in enumerate(row_scales):
@@ -693,27 +663,19 @@ def pack_posttrans_weight_bf16(weight: torch.Tensor, n_scaler: int, A: int, F: i
     """bf16 image (n_scaler, 16 T, round32(A * Fb)) of a reference-layout posttrans weight (N, n_scaler * A * F) for an aggregate
     whose A blocks sit Fb >= F columns apart (include/pna_amd.h, pna_posttrans_bf16_args.w_img): zero columns at the padding of
     every block, zero rows beyond N.  Cached on the weight tensor like pack_posttrans_weight."""
-    key = (weight._version, weight.data_ptr(), str(weight.device), tuple(weight.shape), weight.stride(0), n_scaler, A, F, Fb)
-    hit = getattr(weight, "_pna_amd_pack_bf16", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    N = weight.shape[0]
-    if weight.dtype != torch.bfloat16 or weight.shape[1] != n_scaler * A * F:
-        raise ValueError(f"posttrans weight must be bf16 (N, {n_scaler * A * F}), got {weight.dtype} {tuple(weight.shape)}")
-    T = _lib.lib().pna_posttrans_bf16_tiles(N)
-    if T < 0:
-        raise ValueError(f"pna_posttrans_bf16: out_dim {N} outside 1..128")
-    K = A * Fb
-    Kp = (K + 31) // 32 * 32
-    with torch.no_grad():
-        img = torch.zeros(n_scaler, 16 * T, Kp, dtype=torch.bfloat16, device=weight.device)
+
+    def build():
+        N, K = weight.shape[0], A * Fb
+        if weight.dtype != torch.bfloat16 or weight.shape[1] != n_scaler * A * F:
+            raise ValueError(f"posttrans weight must be bf16 (N, {n_scaler * A * F}), got {weight.dtype} {tuple(weight.shape)}")
+        T = _lib.lib().pna_posttrans_bf16_tiles(N)
+        if T < 0:
+            raise ValueError(f"pna_posttrans_bf16: out_dim {N} outside 1..128")
+        img = torch.zeros(n_scaler, 16 * T, (K + 31) // 32 * 32, dtype=torch.bfloat16, device=weight.device)
         w = weight.reshape(N, n_scaler, A, F).permute(1, 0, 2, 3)                      # (S, N, A, F)
         img[:, :N, :K].view(n_scaler, N, A, Fb)[..., :F] = w
-    try:
-        weight._pna_amd_pack_bf16 = (key, img)
-    except AttributeError:
-        pass
-    return img
+        return img
+    return memo(weight, "_pna_amd_pack_bf16", [weight], (n_scaler, A, F, Fb), build)
 
 
 def posttrans_bf16(agg: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_scales: Sequence[Optional[torch.Tensor]],

@@ -1,7 +1,8 @@
 """Scaffolding of the cache-coherence tests (test_cache_coherence_host.py, test_gpu_cache_coherence.py).
 
 Every fast path keeps operands derived from parameters, buffers or caller tensors -- packed weight images, collapsed weights, folded
-BatchNorm constants, argument blocks -- under a `_pna_amd_*` tag on a module, a tensor or a graph, each behind a hand-written key.
+BatchNorm constants, argument blocks -- under a `_pna_amd_*` tag on a module, a tensor or a graph; the weight-derived ones all behind
+one helper and one key (pna_amd/_cache.py: memo, tensor_key), the topology and caller-tensor ones behind keys of their own.
 The invariant the tests hold every such cache to:
 
     a WARM layer (served at least twice) whose state was changed in any way torch changes state gives, on its next call, bit for
@@ -198,6 +199,13 @@ def warm_tags(*owners):
         d = getattr(obj, "__dict__", None)
         if d:
             found.update(k for k in d if isinstance(k, str) and k.startswith("_pna_amd_"))
+
+    def walk(entry):                                                 # (key, value, tensors): values are tensors or nests of them
+        for x in entry:
+            if torch.is_tensor(x):
+                scan(x)
+            elif isinstance(x, (list, tuple)):
+                walk(x)
     for o in owners:
         if isinstance(o, torch.nn.Module):
             for m in o.modules():
@@ -207,13 +215,7 @@ def warm_tags(*owners):
                         scan(t)
                 for v in list(m.__dict__.values()):                  # tensors held by a cache entry carry caches of their own (Wv)
                     if isinstance(v, tuple):
-                        for x in v:
-                            if torch.is_tensor(x):
-                                scan(x)
-                            elif isinstance(x, (list, tuple)):
-                                for y in x:
-                                    if torch.is_tensor(y):
-                                        scan(y)
+                        walk(v)
         elif o is not None:
             scan(o)
     return found

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import cache_probe as CP
+from pna_amd import _cache
 from pna_amd import functional as PF
 from pna_amd.dgl import pna_layer as PL
 from pna_amd.dgl.pna_layer import PNALayer, PNASimpleLayer
@@ -146,6 +147,112 @@ def test_stack_cached_follows_its_tensors():
         assert torch.equal(PF._stack_cached(owner, tag, ts), torch.stack(ts))
         ts[0].mul_(2.0)
         assert torch.equal(PF._stack_cached(owner, tag, ts), torch.stack(ts))
+
+
+class _Owner:
+    """Any object with a __dict__ can own an entry."""
+
+
+def _counting(value_of):
+    calls = []
+
+    def build():
+        calls.append(torch.is_grad_enabled())
+        return value_of()
+    return build, calls
+
+
+def test_memo_serves_the_same_object_and_rebuilds_on_every_visible_change():
+    """_cache.memo, the one helper behind every weight-derived cache: a warm call returns the first call's object; each way torch shows a
+    change of a keyed tensor -- and a changed `extra` -- rebuilds."""
+    owner = _Owner()
+    a, b = torch.nn.Parameter(torch.randn(3, 4)), torch.randn(4)
+    build, calls = _counting(lambda: a.detach().sum() + b.sum())
+    get = lambda ts=None, extra=7: _cache.memo(owner, "_pna_amd_test", [a, b] if ts is None else ts, extra, build)      # noqa: E731
+    first = get()
+    assert get() is first and get() is first and len(calls) == 1
+    with torch.no_grad():
+        a.mul_(2.0)                                                      # an in-place write to a keyed tensor
+    second = get()
+    assert len(calls) == 2 and second is not first and torch.equal(second, a.detach().sum() + b.sum())
+    b.add_(1.0)                                                          # ... to any of them
+    assert torch.equal(get(), a.detach().sum() + b.sum()) and len(calls) == 3
+    a.data = a.data.clone() * 3                                          # `t.data = other`: same object, same version counter, new address
+    assert torch.equal(get(), a.detach().sum() + b.sum()) and len(calls) == 4
+    assert get() is get() and len(calls) == 4
+    none = get([a, None])                                                # a slot that holds no tensor ...
+    assert len(calls) == 5 and get([a, None]) is none and len(calls) == 5
+    get([a, b])                                                          # ... becoming a tensor
+    assert len(calls) == 6
+    get([a, None])                                                       # ... and back
+    assert len(calls) == 7
+    get([a, None], extra=8)                                              # a changed `extra`
+    assert len(calls) == 8
+    get([a, None], extra=8)
+    assert len(calls) == 8
+    entry = owner.__dict__["_pna_amd_test"]
+    assert type(entry) is tuple and len(entry) == 3 and entry[0] == (_cache.tensor_key([a, None]), 8)
+
+
+def test_memo_tells_two_tensors_at_one_version_and_address_apart():
+    """Two views of one buffer share the version counter and the address: only the object differs.  The (version, address, device) keys
+    this helper replaced served the first view's entry for the second."""
+    owner, buf = _Owner(), torch.randn(12)
+    v1, v2 = buf.view(-1), buf.view(-1)
+    assert v1 is not v2 and v1._version == v2._version and v1.data_ptr() == v2.data_ptr() and v1.shape == v2.shape
+    build, calls = _counting(lambda: torch.zeros(1))
+    first = _cache.memo(owner, "_pna_amd_test", [v1], None, build)
+    assert _cache.memo(owner, "_pna_amd_test", [v1], None, build) is first and len(calls) == 1
+    assert _cache.memo(owner, "_pna_amd_test", [v2], None, build) is not first and len(calls) == 2
+
+
+def test_memo_entry_holds_its_keyed_tensors():
+    """While an entry is live the ids and addresses in its key cannot be handed to another tensor: the entry keeps the tensors."""
+    owner = _Owner()
+    t = torch.randn(5)
+    ident = id(t)
+    _cache.memo(owner, "_pna_amd_test", [t, None], None, lambda: t.sum())
+    del t
+    held = owner.__dict__["_pna_amd_test"][2]
+    assert [id(x) for x in held if x is not None] == [ident]
+    assert owner.__dict__["_pna_amd_test"][0][0][0][0] == ident          # ... the object the key names
+    # a tensor that owns its entry is not held by it (it outlives the entry anyway; holding it would be a reference cycle)
+    w, other = torch.randn(3), torch.randn(3)
+    _cache.memo(w, "_pna_amd_test", [w, other], None, lambda: w + other)
+    assert [x is other for x in w.__dict__["_pna_amd_test"][2]] == [True]
+
+
+def test_memo_builds_without_gradients():
+    owner = _Owner()
+    w = torch.nn.Parameter(torch.randn(3))
+    build, calls = _counting(lambda: w * 2.0)
+    with torch.enable_grad():
+        assert torch.is_grad_enabled()
+        value = _cache.memo(owner, "_pna_amd_test", [w], None, build)
+        assert torch.is_grad_enabled()                                   # (the caller's mode is back)
+    assert calls == [False] and not value.requires_grad
+
+
+def test_bf16_edge_table_is_built_once_per_state_of_the_rows(monkeypatch):
+    """PNANet registers its embedding weight on the graph in every forward, and the graph keeps `weight.detach()`: a NEW tensor object
+    per forward over the same storage and version counter.  The bf16 edge table must be built once per state of the weight, not per
+    alias -- its key leaves the object out (a rebuild is a kernel launch and allocations per layer and forward, and a captured graph
+    would replay it)."""
+    built = []
+    monkeypatch.setattr(PF.ops, "contract_bf16", lambda rows, ed, img, width: (built.append(rows), rows.float() @ img[0, :width, :ed].float().t())[1])
+    w = torch.nn.Parameter(torch.randn(4, 6))
+    im = {"edge": torch.randn(1, 16, 32), "etab": None}
+    a, b = w.detach(), w.detach()
+    assert a is not b and a.data_ptr() == b.data_ptr() and a._version == b._version
+    first = PF._small_edge_table_bf16(im, a, 6, 8)
+    assert PF._small_edge_table_bf16(im, b, 6, 8) is first and PF._small_edge_table_bf16(im, w.detach(), 6, 8) is first and len(built) == 1
+    with torch.no_grad():
+        w.mul_(2.0)                                                      # a new state of the weight: seen through any alias
+    second = PF._small_edge_table_bf16(im, w.detach(), 6, 8)
+    assert len(built) == 2 and torch.equal(second, first * 2.0)
+    assert PF._small_edge_table_bf16(im, b, 6, 8) is second and len(built) == 2
+    w.data = w.data.clone() + 1.0                                        # same version counter, new address
+    assert not torch.equal(PF._small_edge_table_bf16(im, w.detach(), 6, 8), second) and len(built) == 3
 
 
 def test_avg_log_value_follows_the_tensor():
@@ -299,7 +406,12 @@ def test_a_conversion_drops_every_cached_operand():
     build(layer)
     w = towers[-1].posttrans.fully_connected[0].linear.weight
     w._pna_amd_pack = ("a stand-in for the packed image ops.py keeps on the weight",)
-    assert {"_pna_amd_pass_w", "_pna_amd_collapsed", "_pna_amd_proj", "_pna_amd_fold", "_pna_amd_pack"} <= CP.warm_tags(layer)
+    w._pna_amd_group_img = ("a stand-in for the combined images degree_groups.py keeps on the weight",)
+    PL._projection_cache_padded_multi(towers, 20, 24)                    # (one tag of every file that caches through _cache.memo)
+    PF._mix_image_bf16(mix)
+    PL._avg_log_value({"log": towers[0].batchnorm_h.num_batches_tracked})                   # (a buffer in the place of avg_d['log'])
+    assert {"_pna_amd_pass_w", "_pna_amd_collapsed", "_pna_amd_proj", "_pna_amd_fold", "_pna_amd_pack", "_pna_amd_group_img",
+            "_pna_amd_proj_pad_multi", "_pna_amd_bf16_mix", "_pna_amd_float"} <= CP.warm_tags(layer)
     layer.to(torch.bfloat16).float()
     assert not CP.warm_tags(layer), sorted(CP.warm_tags(layer))
     after = build(layer)
