@@ -123,7 +123,7 @@ class DegreePlan:
         self._items, self._graph_ref, self._hs_rows = None, __import__("weakref").ref(graph), (hs.heavy_rows if hs.n_heavy > 0 else None)
         self._vmap, self._n_seg, self._split = vmap, n_seg, None
         self.rows = self.NV + self.NRp
-        self._rest_scales = {}
+        self._rest_scales, self._masked_scales = {}, {}
         self._fused, self._rest_items, self._vmap32, self._perm_all, self._rest_items_node, self._ones_rows = None, None, None, None, None, None
         self._edge_split = None
         self._deg, self._csr = deg, csr
@@ -390,6 +390,20 @@ class DegreePlan:
         return hit
 
 
+    def masked_scales(self, row_scales):
+        """(list, (V, S) matrix) of the per-row scalers with the rows without in-edges at zero (None = the identity: the mask itself): the
+        scalers of a term DGL leaves at zero for such rows.  Cached per scaler set (the tensors' addresses), at most 8 sets."""
+        key = tuple(None if r is None else r.data_ptr() for r in row_scales)
+        hit = self._masked_scales.get(key)
+        if hit is None:
+            if len(self._masked_scales) > 8:
+                self._masked_scales.clear()
+            live = (self._deg > 0).to(torch.float32)
+            ms = [live if r is None else (r * live).contiguous() for r in row_scales]
+            hit = self._masked_scales[key] = (ms, torch.stack(ms, dim=1).contiguous())
+        return hit
+
+
 def agg_pitch(K):
     """Row pitch (floats) of the plan-ordered aggregate.  The contraction reads a row as 128-byte strips, one per chunk of 32
     columns; with packed rows of 4F = 300 floats (1200 bytes) 7 strips in 8 straddle two 128-byte lines.  Measured on the
@@ -604,10 +618,10 @@ def fused_panels(F, N):
     return out[0] + out[1]            # (all of the first feature panel's launches, then the second's: those read the partial sums)
 
 
-def bind_fused_arith(a, keep, weight, F, row_scales, plan, tower, device, verification=False, rows=None, aggregators=STANDARD_AGGREGATORS, feats=None):
-    """Fill the arithmetic half of a pna_fused_degree_args block: the images of the arithmetic fused_arith() selects and, for the
-    guarded form, the plan's hand-over workspace (one per (plan, stream), like the tile counters: launches on one stream are ordered).
-    `keep`: a list that keeps the tensors alive.  verification: the agg_out instantiation (fp16 x 2, unguarded)."""
+def bind_fused_arith(a, keep, weight, F, row_scales, plan, tower, verification=False, rows=None, aggregators=STANDARD_AGGREGATORS, feats=None):
+    """Fill the arithmetic half of a pna_fused_degree_args block: the images of the arithmetic fused_arith() selects.  The guarded form's
+    hand-over workspace belongs to the stream of the launch: functional._FusedCall binds it with the tile order.  `keep`: a list that
+    keeps the tensors alive.  verification: the agg_out instantiation (fp16 x 2, unguarded)."""
     arith = _lib.FD_ARITH_H2 if verification else fused_arith()
     a.arith = arith
     if arith != _lib.FD_ARITH_X3:
@@ -618,10 +632,6 @@ def bind_fused_arith(a, keep, weight, F, row_scales, plan, tower, device, verifi
         img3, stride3 = fused_images(weight, F, row_scales, plan, tower=tower, x3=True, rows=rows, aggregators=aggregators, feats=feats)
         a.w_img_x3, a.image_stride_x3 = _lib.dev_ptr(img3, torch.float32, "w_img_x3"), stride3
         keep.append(img3)
-    if arith == _lib.FD_ARITH_GUARDED:
-        ws = guard_workspace(plan, device)
-        a.guard_ws, a.guard_ws_bytes = _lib.dev_ptr(ws, torch.int32, "guard_ws"), ws.numel() * 4
-        keep.append(ws)
     return arith
 
 
@@ -659,7 +669,7 @@ FUSED_MAX_PANELS = 3       # output-column panels of one layer (fused_panels): e
 FUSED_ARITH = os.environ.get("PNA_AMD_FUSED_ARITH", "guarded")   # guarded | bf16x3 | fp16x2 (fused_arith)
 FUSED_DYNAMIC_TAIL = int(os.environ.get("PNA_AMD_FUSED_DYNAMIC_TAIL", "4"))   # "dynamic": this many x G of the cheapest tiles end the list
 FUSED_TILE_COST = float(os.environ.get("PNA_AMD_FUSED_TILE_COST", "10"))   # a tile's constant cost in edge units (multiply + epilogue + control)
-OUT_PITCH_ALIGN = int(os.environ.get("PNA_AMD_OUT_PITCH_ALIGN", "32"))   # floats: row pitch of the one-kernel layers' own output (functional.out_pitch)
+OUT_PITCH_ALIGN = int(os.environ.get("PNA_AMD_OUT_PITCH_ALIGN", "32"))   # floats: row pitch of the one-kernel layers' own output (out_pitch)
 REST_SEG_LEN = 128         # edges per hub-row segment in the rest launch of the one-kernel layer (see DegreePlan.rest_items)
 REST_ROWS_PER_GROUP = 1    # work items per lane group in that launch (the full-graph gather: 4): a few thousand items must spread over 256 CUs
 TOWERS = True              # the tower layers (PNALayer) through the degree-grouped contraction with collapsed posttrans / mixing weights
@@ -676,13 +686,26 @@ FUSED_OVERLAP_MIN_F = 64           # ... and so it is with few features (the cha
 FUSED_OVERLAP_MAX_REST_EDGES = 1.0 / 12   # ... and so it is when the rest rows hold more than this fraction of the group rows' edges
 
 
-def out_pitch_floats(N):
-    """Row pitch (floats) of the output the degree-grouped layers allocate (functional.out_pitch: whole 128-byte lines), at least the
-    80 / 128-column block of the grouped contraction: what the kernels' 32-bit row offsets must cover (the guard used to
-    assume 80 floats while the one-kernel layer allocates 96 for 65 <= N <= 80 -- a graph of 11.2-13.4 M nodes passed the guard and was
-    then refused by pna_fused_degree_f32)."""
+def out_pitch(N):
+    """Row pitch (floats) of the output the one-kernel layers allocate: whole 128-byte lines (N = 75 -> 96 floats).  The kernel
+    stores a row as 64-byte pieces (16 columns: four lanes x 16 bytes); at a line-aligned pitch every piece is one aligned half
+    line of a line no other row shares, at the smallest 16-byte aligned pitch (76 floats) most pieces straddle two sectors and
+    neighbouring rows share lines.  Measured at C3 (one box, kernel ms): pitch 76 0.745, 80 0.735, 96 0.732.  A multi-layer net
+    reads the rows back as the next layer's source table: three whole lines per 300-byte row instead of 3.4."""
     a = max(4, int(OUT_PITCH_ALIGN))
-    return max((N + a - 1) // a * a, 80 if N <= 80 else 128 if N <= 128 else N)
+    return (N + a - 1) // a * a
+
+
+def out_pitch_floats(N):
+    """Row pitch (floats) of the output the degree-grouped layers allocate (out_pitch), at least the 80 / 128-column block of the grouped
+    contraction: what the kernels' 32-bit row offsets must cover (the guard used to assume 80 floats while the one-kernel layer
+    allocates 96 for 65 <= N <= 80 -- a graph of 11.2-13.4 M nodes passed the guard and was then refused by pna_fused_degree_f32)."""
+    return max(out_pitch(N), 80 if N <= 80 else 128 if N <= 128 else N)
+
+
+def balance_key():
+    """The knobs a balanced tile order depends on (DegreePlan.fused_balance): part of the key of everything cached per order."""
+    return (FUSED_BALANCE, FUSED_TILE_COST, FUSED_DYNAMIC_TAIL)
 
 
 def fused_applies(graph, x, F, N, aggregators=STANDARD_AGGREGATORS):

@@ -1,11 +1,13 @@
 """Graph-level functional API used by the layers: `aggregate` (gather + segment-reduce kernel) and
 `posttrans` (MFMA contraction), both differentiable through custom autograd Functions.
 """
+import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
-from . import ops
+from . import _lib, degree_groups as DG, ops
 from ._cache import DropsCachesOnConversion, drop_weight_caches, memo, tensor_key  # noqa: F401  (PF.drop_weight_caches, PF.DropsCachesOnConversion)
 
 
@@ -247,8 +249,6 @@ class _SmallTowerPlan:
     _etab = None
 
     def __init__(self, towers, mix, divide_input):
-        import ctypes
-        from . import _lib
         t0 = towers[0]
         self.edge_dim = t0.edge_dim if t0.edge_features else 0
         self._etab = None                                      # (edge_table's entry: the graph's type rows projected, W_e . ef_t)
@@ -323,7 +323,6 @@ class _SmallTowerPlan:
         csr = graph.csr
         out = torch.empty((V, self.width), dtype=torch.float32, device=dev)
         xc = torch.empty((V, self.xw), dtype=torch.float32, device=dev)
-        import ctypes
         a = type(self.args)()                                # per-call copy of the pre-filled block: concurrent calls of one layer from
         ctypes.memmove(ctypes.byref(a), self.ref, ctypes.sizeof(a))      # two host threads / streams do not race on it
         a.rowptr, a.col, a.V = csr.rowptr.data_ptr(), csr.col.data_ptr(), V
@@ -369,7 +368,6 @@ def degree_grouped_aggregate(layer, graph, h, plan, out=None, x=None):
     x = _unit_stride(x)
     csr = graph.csr
     if out is None:
-        from . import degree_groups as DG
         out = torch.empty(plan.rows, DG.agg_pitch(K), dtype=torch.float32, device=h.device)[:, :K]     # line-aligned rows
     if getattr(graph, "_pending", None) is not None:
         items_in, items_bd = plan.split_items(graph)
@@ -413,7 +411,6 @@ def _rest_posttrans(layer, graph, agg_rest, plan, scales, y, cs, ct, res):
     `agg_rest` ((plan.NRp, 4F): the four STANDARD statistics, virtual order; (plan.NRp, 5F) with room for a fifth block when the layer
     aggregates `sum`), rows scattered to node order.  A layer with another aggregator list (round 6) contracts against its weight
     re-expressed over those statistics (degree_groups.virtual_layer_weight); the sum block = in-degree x mean is formed here."""
-    from . import degree_groups as DG
     F, N = layer.in_dim, layer.out_dim
     K = 4 * F
     lin = layer.posttrans.fully_connected[0].linear
@@ -429,24 +426,27 @@ def _rest_posttrans(layer, graph, agg_rest, plan, scales, y, cs, ct, res):
                 deg[:plan.NR, 0] = plan._deg[plan.rest_rows].to(torch.float32)
                 deg = plan.__dict__["_rest_deg"] = deg[:plan.NRp]
             torch.mul(agg_rest[:, :F], deg, out=agg_rest[:, 4 * F:5 * F])
+    _contract_rest_rows(plan, agg_rest, K, weight, rest_scales, lin.bias, y, N, col_scale=cs, col_shift=ct, relu=True, residual=res)
+
+
+def _contract_rest_rows(plan, agg, K, weight, rest_scales, bias, y, N, **tail):
+    """The three-block contraction over the rest rows' compact list `agg` (plan.NRp rows, virtual order), rows scattered to node order in
+    `y`; `tail`: the epilogue operands of ops.posttrans (row_post in virtual order, residual in node order)."""
     if N <= 80 and len(rest_scales) == 3:
-        ops.posttrans(agg_rest, K, weight, rest_scales, lin.bias, out=y, col_scale=cs, col_shift=ct, relu=True, residual=res,
-                      row_perm=plan.perm_rest, n_out=N)
-    else:
-        # 128-column block (three blocks x three weight buffers do not fit the LDS) or another scaler count (no grouped
-        # instantiation): the few rest rows take the ordinary kernel over their compact list and are scattered by index (three
-        # small torch kernels)
-        rr = plan.rest_rows
-        y_r = ops.posttrans(agg_rest[:plan.NR], K, weight, [None if r is None else r[:plan.NR] for r in rest_scales],
-                            lin.bias, col_scale=cs, col_shift=ct, relu=True, residual=None if res is None else res.index_select(0, rr),
-                            arith="bf16x3")
-        y.index_copy_(0, rr, y_r)
+        ops.posttrans(agg, K, weight, rest_scales, bias, out=y, row_perm=plan.perm_rest, n_out=N, **tail)
+        return
+    # 128-column block (three blocks x three weight buffers do not fit the LDS) or another scaler count (no grouped instantiation): the few
+    # rest rows take the ordinary kernel over their compact list and are scattered by index (three small torch kernels)
+    rr, post, res = plan.rest_rows, tail.pop("row_post", None), tail.pop("residual", None)
+    y_r = ops.posttrans(agg[:plan.NR], K, weight, [None if r is None else r[:plan.NR] for r in rest_scales], bias,
+                        row_post=None if post is None else post[:plan.NR], residual=None if res is None else res.index_select(0, rr),
+                        arith="bf16x3", **tail)
+    y.index_copy_(0, rr, y_r)
 
 
 def degree_grouped_posttrans(layer, graph, h, agg, plan, out=None):
     """The two contractions over `agg` (degree_grouped_aggregate): one combined block per degree tile, three blocks for the rest;
     both scatter their rows to node order with BatchNorm / ReLU / residual in the epilogue."""
-    from . import degree_groups as DG
     from .dgl.pna_layer import _row_scales
     F, N = layer.in_dim, layer.out_dim
     K = len(layer.aggregators) * F
@@ -508,7 +508,6 @@ def _tower_collapsed_weights(owner, towers, mix, divide_input):
 def tower_layer_degree_grouped_applies(layer, graph, h):
     """Whether PNALayer.forward (eval) takes the degree-grouped path below: a large whole graph, 1-layer pretrans / posttrans, no
     edge features, the four standard aggregators, 3 scalers led by `identity`, a LeakyReLU mixing network without batch norm."""
-    from . import degree_groups as DG
     from .graph import Graph
     towers = list(layer.towers)
     t0, mix = towers[0], layer.mixing_network
@@ -537,7 +536,6 @@ def tower_layer_degree_grouped(layer, graph, h, snorm_n, x_src, x_dst):
     degree-grouped contraction per row class (combined block W_D over the degree tiles, three scaler blocks over the rest) applies
     the collapsed posttrans . graph norm . BatchNorm . mixing weight (see _tower_collapsed_weights) with LeakyReLU and the
     residual in its epilogue."""
-    from . import degree_groups as DG
     from .dgl.pna_layer import _row_scales
     towers, mix = list(layer.towers), layer.mixing_network
     t0 = towers[0]
@@ -558,12 +556,7 @@ def tower_layer_degree_grouped(layer, graph, h, snorm_n, x_src, x_dst):
     y = torch.empty(V, N, dtype=torch.float32, device=dev)
     res = hc if layer.residual else None
     slope = float(mix.activation.negative_slope)
-    post_g = post_r = None
-    if t0.graph_norm and snorm_n is not None:
-        sn = snorm_n.reshape(-1).to(torch.float32)
-        idx = plan.perm_all().long()
-        post = sn[idx]
-        post_g, post_r = post[:plan.NV].contiguous(), post[plan.NV:].contiguous()
+    post_g, post_r = _graph_norm_rows(plan, snorm_n, t0.graph_norm)
     if plan.G:
         img, stride = DG.combined_images(Wv, K, scales, plan)
         ops.posttrans(buf[:plan.NV, :K], K, Wv, [None], d, out=y, row_post=post_g, col_scale=ones, col_shift=c, leaky_slope=slope, residual=res,
@@ -571,15 +564,8 @@ def tower_layer_degree_grouped(layer, graph, h, snorm_n, x_src, x_dst):
     if plan.NR:
         from .dgl.pna_layer import _avg_log_value
         rest_scales = plan.rest_scales(tuple(t0.scalers) + (_avg_log_value(t0.avg_d),), scales)
-        if N <= 80:
-            ops.posttrans(buf[plan.NV:, :K], K, Wv, rest_scales, d, out=y, row_post=post_r, col_scale=ones, col_shift=c, leaky_slope=slope,
-                          residual=res, row_perm=plan.perm_rest, n_out=N)
-        else:
-            rr = plan.rest_rows
-            y_r = ops.posttrans(buf[plan.NV:plan.NV + plan.NR, :K], K, Wv, [None if r is None else r[:plan.NR] for r in rest_scales], d,
-                                row_post=None if post_r is None else post_r[:plan.NR], col_scale=ones, col_shift=c, leaky_slope=slope,
-                                residual=None if res is None else res.index_select(0, rr), arith="bf16x3")
-            y.index_copy_(0, rr, y_r)
+        _contract_rest_rows(plan, buf[plan.NV:, :K], K, Wv, rest_scales, d, y, N, row_post=post_r, col_scale=ones, col_shift=c, leaky_slope=slope,
+                            residual=res)
     return y
 
 
@@ -597,7 +583,6 @@ def tower_layer_degree_fused_applies(layer, graph, h):
     weight is dense anyway); and -- round 6 -- T towers with divide_input=False (:137-139: T DIFFERENT projections of the whole input,
     T x in_dim message features per edge): one launch per tower over its own 49..80 projected features, the partial sums carried from
     launch to launch (FusedMultiTowerCall)."""
-    from . import degree_groups as DG
     towers = list(layer.towers)
     T, Fi = len(towers), towers[0].in_dim
     if not DG.FUSED or not 4 <= layer.out_dim <= 80:
@@ -660,17 +645,15 @@ def _side_stream(device):
 
 
 def run_fused_call(call):
-    """The two halves of a one-kernel layer (FusedDegreeCall / FusedTowerCall): the persistent kernel over the group rows and the
+    """The two halves of a one-kernel layer (a _FusedCall): the persistent kernel over the group rows and the
     chain of small launches over the rest rows (hub rows, rare degrees).  On a large graph the chain runs BESIDE the kernel: the
     kernel books every register of every CU it sits on, so it leaves `degree_groups.FUSED_SPARE_WGS` of its workgroups out and
     the chain goes to a second stream, forked and joined with events around the call (benchmark graph: 0.852 -> 0.807 ms; the two
     halves write disjoint rows of y).  The caller's stream sees one call: everything it issued before is visible to both halves,
     everything it issues afterwards waits for both."""
-    from . import _lib
     plan = call.plan
     call.stream = _lib.stream_ptr(call.y.device)             # (the kernel goes to the stream that is current NOW, like every other launch)
-    if hasattr(call, "prologue"):
-        call.prologue()                                      # (what BOTH halves read: in front of the fork)
+    call.prologue()                                          # (what BOTH halves read: in front of the fork)
     overlap = plan.rest_overlap_applies(call.layer_F())
     if overlap and CAPTURE_OVERLAP != "beside" and torch.cuda.is_current_stream_capturing():
         overlap = False                                      # (see CAPTURE_OVERLAP)
@@ -697,15 +680,7 @@ def run_fused_call(call):
     return call.y
 
 
-def out_pitch(N):
-    """Row pitch (floats) of the output the one-kernel layers allocate: whole 128-byte lines (N = 75 -> 96 floats).  The kernel
-    stores a row as 64-byte pieces (16 columns: four lanes x 16 bytes); at a line-aligned pitch every piece is one aligned half
-    line of a line no other row shares, at the smallest 16-byte aligned pitch (76 floats) most pieces straddle two sectors and
-    neighbouring rows share lines.  Measured at C3 (one box, kernel ms): pitch 76 0.745, 80 0.735, 96 0.732.  A multi-layer net
-    reads the rows back as the next layer's source table: three whole lines per 300-byte row instead of 3.4."""
-    from . import degree_groups as DG
-    a = max(4, int(DG.OUT_PITCH_ALIGN))
-    return (N + a - 1) // a * a
+out_pitch = DG.out_pitch
 
 
 def own_buffer_cols(pitch, c0, c1, N):
@@ -735,170 +710,221 @@ DEBUG_COUNTERS = os.environ.get("PNA_AMD_DEBUG_COUNTERS", "0") == "1"   # host-s
 # on the plan skip tiles silently
 
 
-def _check_working_words(call):
-    keep = getattr(call, "_order_keep", None)
-    if keep is None:
-        return
-    torch.cuda.current_stream(call.y.device).synchronize()
-    for name, t in (("tile_counter", keep[3]), ("guard workspace", keep[4])):
-        if t is not None and t[:2].tolist() != [0, 0]:
-            raise RuntimeError(f"pna_amd: the {name} of this plan / stream is {t[:2].tolist()} in front of a launch (expected [0, 0]): an earlier launch "
-                               "was aborted or ran on another stream than it was bound on")
+class _TileOrder(NamedTuple):
+    """What one (spare, balance knobs, stream) binds into the argument blocks: device pointers, and `keep` = the tensors behind them
+    (tile_desc, row_perm, row_post, tile counter, guard workspace)."""
+    tile_desc: int
+    row_perm: int
+    tile_counter: Optional[int]
+    row_post: Optional[int]
+    guard_ws: Optional[int]
+    keep: tuple
 
 
-def _bind_tile_order(call, spare):
-    """(see _bind_tile_order_one; a layer in several output-column panels binds every panel's argument block to the same tables)"""
-    if DEBUG_COUNTERS and getattr(call, "_order_keep", None) is not None:
-        _check_working_words(call)
-    blocks = getattr(call, "panel_args", None)
-    if not blocks or len(blocks) == 1:
-        return _bind_tile_order_one(call, spare)
-    first, first_ref = call.args, call.ref
-    _bind_tile_order_one(call, spare)
-    src = call.args
-    for a, _ in blocks[1:]:
-        a.spare_workgroups, a.tile_desc, a.row_perm, a.tile_counter = src.spare_workgroups, src.tile_desc, src.row_perm, src.tile_counter
-        a.guard_ws, a.guard_ws_bytes = src.guard_ws, src.guard_ws_bytes
-    call.args, call.ref = first, first_ref
+class _FusedCall:
+    """What the three drivers of pna_fused_degree_f32 share: the argument blocks of the layer's launches, the helpers that fill them and
+    the binding of the tile order.  A subclass builds its blocks in launch order (`_block`, then `_final` or `_partial`), names the PRIMARY
+    one -- the block whose row_post follows the tile order -- in `_bind`, and brings `rest_rows()`: the rows no degree group holds, on the
+    two-kernel path over their compact list."""
+
+    def __init__(self, layer, graph, plan, h, scales, y, keep):
+        self.layer, self.graph, self.plan, self.h, self.scales, self.y = layer, graph, plan, h, scales, y
+        self.keep = list(plan.fused_tables()[:2]) + keep    # every tensor the blocks point into
+        self.blocks, self.primary = [], 0                    # [(args, byref)] in launch order
+        self.args = self.ref = self.arith = None             # the primary block; the arithmetic of the launches (_lib.FD_ARITH_*)
+        self.post_g = None                                   # per-row factor of the group rows in plan order (graph norm, or ones), if any
+        self._orders, self._post_b, self._bound = {}, {}, None     # _TileOrder per grid; post_g per balanced order; the order bound last
+        self.fn, self.check, self.stream = _lib.lib().pna_fused_degree_f32, _lib.check, _lib.stream_ptr(y.device)
+
+    launch_order = panel_args = property(lambda self: self.blocks)
+
+    def _block(self, weight, F, x, N, tower=False, pre_add=None, **panel):
+        """A new block with what every launch has: the plan's tables, the source slice `x` (its width = the features gathered), the rows,
+        the images of `weight` over F features for the arithmetic (degree_groups.bind_fused_arith; `panel`: the part of it this launch
+        takes) and the partial sums the launch adds to, if any."""
+        plan = self.plan
+        desc, ids, n_rec = plan.fused_tables()
+        a = _lib.PnaFusedDegreeArgs()
+        self.arith = DG.bind_fused_arith(a, self.keep, weight, F, self.scales, plan, tower, **panel)
+        a.tile_desc, a.tile_ids, a.n_records = _lib.dev_ptr(desc, torch.int32, "tile_desc"), _lib.dev_ptr(ids, torch.int32, "tile_ids"), n_rec
+        a.x, a.ldx, a.x_rows, a.F, a.N = _lib.dev_ptr(x, torch.float32, "x"), x.stride(0), x.shape[0], x.shape[1], N
+        a.row_perm, a.M, a.n_nodes = _lib.dev_ptr(plan.perm, torch.int32, "row_perm"), plan.NV, self.h.shape[0]
+        if pre_add is not None:
+            a.pre_add, a.ld_pre_add = _lib.dev_ptr(pre_add, torch.float32, "pre_add"), pre_add.stride(0)
+        self.blocks.append((a, ctypes.byref(a)))
+        return a
+
+    @staticmethod
+    def _final(a, y, bias, col_scale, col_shift, residual, relu, act_slope=0.0, cols_writable=0):
+        """The epilogue of a launch that finishes its columns of the layer (row_post: see _bind_tile_order)."""
+        a.bias = _lib.dev_ptr(bias, torch.float32, "bias")
+        a.col_scale, a.col_shift = _lib.dev_ptr(col_scale, torch.float32, "col_scale"), _lib.dev_ptr(col_shift, torch.float32, "col_shift")
+        if residual is not None:
+            a.residual, a.ld_res = _lib.dev_ptr(residual, torch.float32, "residual"), residual.stride(0)
+        a.y, a.ldy, a.relu, a.act_slope = _lib.dev_ptr(y, torch.float32, "y"), y.stride(0), relu, act_slope
+        a.y_cols_writable = cols_writable
+
+    @staticmethod
+    def _partial(a, buf, c0, c1):
+        """A launch that leaves partial sums in the columns [c0, c1) of `buf`: no bias, no factor, no activation, no residual."""
+        a.y, a.ldy, a.relu = _lib.dev_ptr(buf[:, c0:c1], torch.float32, "y"), buf.stride(0), 0
+        a.y_cols_writable = own_buffer_cols(buf.stride(0), c0, c1, buf.shape[1])
+
+    def _bind(self, primary):
+        self.primary = primary
+        self.args, self.ref = self.blocks[primary]
+        self._bind_tile_order(0)
+
+    def layer_F(self):
+        return self.layer.in_dim
+
+    def set_spare(self, on):
+        self._bind_tile_order(DG.FUSED_SPARE_WGS if on else 0)
+
+    def prologue(self):
+        """What both halves read (run_fused_call launches it in front of the fork): nothing, unless a subclass says so."""
+
+    def group_rows(self):
+        for _, ref in self.blocks:
+            self.check(self.fn(ref, self.stream), "pna_fused_degree_f32")
+        return self.y
+
+    def _bind_tile_order(self, spare):
+        """Point every block at the plan's tile list for the grid `spare` gives, on the current stream (_tile_order).  Per (grid, balance
+        knobs, stream) the pointers only: this runs in front of every launch."""
+        if DEBUG_COUNTERS and self._bound is not None:
+            self._check_working_words()
+        spare = int(spare)
+        stream = int(torch.cuda.current_stream(self.y.device).cuda_stream)      # (the counter pair and the guard's workspace belong to the stream)
+        key = (spare, DG.balance_key(), stream)
+        o = self._orders.get(key)
+        if o is None:
+            o = self._orders[key] = self._tile_order(spare, stream)
+        self._bound = o
+        for a, _ in self.blocks:
+            a.spare_workgroups, a.tile_desc, a.row_perm, a.tile_counter = spare, o.tile_desc, o.row_perm, o.tile_counter
+            if o.guard_ws is not None:
+                a.guard_ws = o.guard_ws
+        if o.row_post is not None:
+            self.args.row_post = o.row_post
+
+    def _tile_order(self, spare, stream):
+        """The _TileOrder of a grid: the load-balanced order (DegreePlan.fused_balance) for the production instantiations of the 64-row-tile
+        shapes, the plan's own order otherwise (the verification instantiation writes agg_out in plan order; the 8-wavefront build of the
+        wide shapes has 128-row tiles); post_g permuted with its rows; the stream's tile counter pair and guard workspace."""
+        plan, a, dev = self.plan, self.args, self.y.device
+        bal = None
+        if not a.agg_out and plan.NV and _lib.lib().pna_fused_degree_tile_rows(a.F, a.N) == 64:
+            bal = plan.fused_balance(_fused_grid(dev, spare, plan.NV // 64))
+        post = self.post_g
+        if bal is None:
+            desc, perm = plan.fused_tables()[0], plan.perm
+        else:
+            desc, perm, src = bal
+            if post is not None and post is not plan.ones_rows():
+                moved = self._post_b.get(src.data_ptr())
+                if moved is None:
+                    moved = self._post_b[src.data_ptr()] = post.view(plan.NV // 64, 64)[src].reshape(-1).contiguous()
+                post = moved
+        counter = None
+        if bal is not None and DG.FUSED_BALANCE == "dynamic":
+            # ONE counter pair per (plan, stream) (zero between launches: the kernel's last workgroup resets it; launches on one stream are
+            # ordered, launches on different streams get different pairs): a per-call tensor would put an allocation and a fill kernel in
+            # front of every forward
+            counters = plan.__dict__.setdefault("_tile_counters", {})
+            counter = counters.get((str(dev), stream))
+            if counter is None:                                  # (claims | finished: the kernel leaves them zero)
+                if len(counters) > 16:
+                    counters.clear()
+                counter = counters[(str(dev), stream)] = torch.zeros(2, dtype=torch.int32, device=dev)
+        gws = None
+        if a.arith == _lib.FD_ARITH_GUARDED:                     # the guard's hand-over workspace: one per (plan, stream) too
+            gws = DG.guard_workspace(plan, dev)
+            for b, _ in self.blocks:
+                b.guard_ws_bytes = gws.numel() * 4
+
+        def ptr(t, dtype, name):
+            return None if t is None else _lib.dev_ptr(t, dtype, name).value
+        return _TileOrder(ptr(desc, torch.int32, "tile_desc"), ptr(perm, torch.int32, "row_perm"), ptr(counter, torch.int32, "tile_counter"),
+                          ptr(post, torch.float32, "row_post"), ptr(gws, torch.int32, "guard_ws"), (desc, perm, post, counter, gws))
+
+    def _check_working_words(self):
+        """DEBUG_COUNTERS: the tile counter pair and the guard's working words of the order bound last are zero."""
+        *_, counter, gws = self._bound.keep
+        torch.cuda.current_stream(self.y.device).synchronize()
+        for name, t in (("tile_counter", counter), ("guard workspace", gws)):
+            if t is not None and t[:2].tolist() != [0, 0]:
+                raise RuntimeError(f"pna_amd: the {name} of this plan / stream is {t[:2].tolist()} in front of a launch (expected [0, 0]): an earlier launch "
+                                   "was aborted or ran on another stream than it was bound on")
 
 
-def _bind_tile_order_one(call, spare):
-    """Point the call's argument block at the plan's tile list for the grid `spare` gives: the load-balanced order
-    (DegreePlan.fused_balance) for the production instantiations of the 64-row-tile shapes, the plan's own order otherwise (the
-    verification instantiation writes agg_out in plan order; the 8-wavefront build of the wide shapes has 128-row tiles)."""
-    from . import _lib
-    plan, a = call.plan, call.args
-    memo = call.__dict__.setdefault("_orders", {})
-    mkey = (int(spare), DG_balance_key(), int(torch.cuda.current_stream(call.y.device).cuda_stream))      # (the counter pair belongs to the stream)
-    hit = memo.get(mkey)
-    if hit is not None:                                   # (per call and grid: the pointers only -- this runs in front of every launch)
-        a.spare_workgroups, a.tile_desc, a.row_perm, a.tile_counter = int(spare), hit[0], hit[1], hit[2]
-        if hit[3] is not None:
-            a.row_post = hit[3]
-        if hit[5] is not None:
-            a.guard_ws = hit[5]
-        return
-    a.spare_workgroups = int(spare)
-    bal = None
-    if not a.agg_out and plan.NV and _lib.lib().pna_fused_degree_tile_rows(a.F, a.N) == 64:
-        bal = plan.fused_balance(_fused_grid(call.y.device, int(spare), plan.NV // 64))
-    if bal is None:
-        desc, perm, post = plan.fused_tables()[0], plan.perm, getattr(call, "post_g", None)
-    else:
-        desc, perm, src = bal
-        post = getattr(call, "post_g", None)
-        if post is not None and post is not plan.ones_rows():
-            key = ("post", src.data_ptr())
-            hit = call.__dict__.setdefault("_post_b", {}).get(key)
-            if hit is None:
-                hit = call._post_b[key] = post.view(plan.NV // 64, 64)[src].reshape(-1).contiguous()
-            post = hit
-    from . import degree_groups as DG
-    counter = None
-    if bal is not None and DG.FUSED_BALANCE == "dynamic":
-        # ONE counter pair per (plan, stream) (zero between launches: the kernel's last workgroup resets it; launches on one stream are
-        # ordered, launches on different streams get different pairs): a per-call tensor would put an allocation and a fill kernel in
-        # front of every forward
-        ckey = (str(call.y.device), int(torch.cuda.current_stream(call.y.device).cuda_stream))
-        counters = plan.__dict__.setdefault("_tile_counters", {})
-        counter = counters.get(ckey)
-        if counter is None:                                  # (claims | finished: the kernel leaves them zero)
-            if len(counters) > 16:
-                counters.clear()
-            counter = counters[ckey] = torch.zeros(2, dtype=torch.int32, device=call.y.device)
-    a.tile_counter = None if counter is None else _lib.dev_ptr(counter, torch.int32, "tile_counter")
-    gws = None
-    if a.arith == _lib.FD_ARITH_GUARDED:                     # the guard's hand-over workspace belongs to the stream too
-        gws = DG.guard_workspace(plan, call.y.device)
-        a.guard_ws, a.guard_ws_bytes = _lib.dev_ptr(gws, torch.int32, "guard_ws"), gws.numel() * 4
-    call._order_keep = (desc, perm, post, counter, gws)
-    a.tile_desc, a.row_perm = _lib.dev_ptr(desc, torch.int32, "tile_desc"), _lib.dev_ptr(perm, torch.int32, "row_perm")
-    rp = None
-    if post is not None and a.row_post:
-        rp = a.row_post = _lib.dev_ptr(post, torch.float32, "row_post")
-    memo[mkey] = (a.tile_desc, a.row_perm, a.tile_counter, rp, call._order_keep, a.guard_ws if gws is not None else None)
+def _graph_norm_rows(plan, snorm_n, graph_norm, ones=False):
+    """(post_g, post_r): the graph norm's per-row factor in the plan's order, group rows | rest rows.  Without graph norm: (None, None), or
+    -- `ones`, the one-kernel tower calls, whose kernel always multiplies -- (plan.ones_rows(), None)."""
+    if graph_norm and snorm_n is not None:
+        post = snorm_n.reshape(-1).to(torch.float32)[plan.perm_all().long()]
+        return post[:plan.NV].contiguous(), post[plan.NV:].contiguous()
+    return (plan.ones_rows() if ones else None), None
 
 
-def DG_balance_key():
-    from . import degree_groups as DG
-    return (DG.FUSED_BALANCE, DG.FUSED_TILE_COST, DG.FUSED_DYNAMIC_TAIL)
+class _FusedTowerRows(_FusedCall):
+    """What the two tower drivers share: the collapsed epilogue (bias d, graph norm, constants c, LeakyReLU, residual) and the rest rows
+    -- gather over the projected sources, the rows' own term copied behind the statistics, three-block contraction; a subclass gives the
+    gather's arguments (`_rest_operands`)."""
+
+    def __init__(self, layer, graph, h, snorm_n, keep):
+        from .dgl.pna_layer import _row_scales
+        plan, t0 = DG.plan_of(graph), layer.towers[0]
+        N = layer.out_dim
+        y = torch.empty(h.shape[0], out_pitch(N), dtype=torch.float32, device=h.device)[:, :N]
+        super().__init__(layer, graph, plan, h, _row_scales(graph, t0.scalers, t0.avg_d, h.device), y, keep)
+        self.t0, self.res, self.slope = t0, (h if layer.residual else None), float(layer.mixing_network.activation.negative_slope)
+        self.post_g, self.post_r = _graph_norm_rows(plan, snorm_n, t0.graph_norm, ones=True)
+
+    def _tower_final(self, a):
+        N = self.y.shape[1]
+        self._final(a, self.y, self.d, self.ones, self.c, self.res, 2, self.slope, own_buffer_cols(self.y.stride(0), 0, N, N))
+
+    def rest_rows(self):
+        plan, graph, t0 = self.plan, self.graph, self.t0
+        if plan.NR:
+            from .dgl.pna_layer import _avg_log_value
+            F, n_tower, gather, own, weight = self._rest_operands()
+            Ka = n_tower * 4 * F
+            K = Ka + own.shape[1]
+            agg = torch.empty(plan.NRp, DG.agg_pitch(K), dtype=torch.float32, device=self.y.device)
+            csr = graph.csr
+            ops.segreduce(csr.rowptr, csr.col, self.x_src, F, t0.aggregators, (None,), n_tower=n_tower, out=agg, tower_stride_out=4 * F,
+                          workspace=graph.workspace, tune=dict(generic=2, rows_per_group=DG.REST_ROWS_PER_GROUP), **gather)
+            ops.pack_rows(own, plan.perm_all()[plan.NV:], out=agg[:, Ka:K])
+            rest_scales = plan.rest_scales(tuple(t0.scalers) + (_avg_log_value(t0.avg_d),), self.scales)
+            _contract_rest_rows(plan, agg[:, :K], K, weight, rest_scales, self.d, self.y, self.y.shape[1], row_post=self.post_r,
+                                col_scale=self.ones, col_shift=self.c, leaky_slope=self.slope, residual=self.res)
+        return self.y
 
 
-class FusedTowerCall:
+class FusedTowerCall(_FusedTowerRows):
     """One PNALayer forward (one tower, or T towers with divide_input=True; eval) on the one-kernel path after the node-level projection, cut into its launches like
     FusedDegreeCall: `group_rows()` = pna_fused_degree_f32 in tower mode, `rest_rows()` = gather with the destination term + the
     rows' own features + three-block contraction over the compact list of the rows no degree group holds."""
 
     def __init__(self, layer, graph, h, snorm_n, x_cat):
-        from . import _lib, degree_groups as DG
-        from .dgl.pna_layer import _row_scales
-        import ctypes
-        towers, mix = list(layer.towers), layer.mixing_network
-        t0 = towers[0]
-        Fi, V, dev = len(towers) * t0.in_dim, h.shape[0], h.device          # (Fi: message features per edge, ALL towers -- see _tower_flat_weights)
+        towers = list(layer.towers)
+        Fi = len(towers) * towers[0].in_dim                  # (message features per edge, ALL towers -- see _tower_flat_weights)
         P = x_cat.shape[1] // 2
-        self.layer, self.graph, self.plan, self.t0, self.Fe = layer, graph, DG.plan_of(graph), t0, Fi
-        plan = self.plan
-        self.Wv, self.d, self.c, self.ones, self.K = Wv, d, c, ones, K = _tower_flat_weights(layer, towers, mix)
-        N = Wv.shape[0]
-        self.x_src, self.x_dst, self.h = x_cat[:, :Fi], x_cat[:, P:P + Fi], h
-        self.scales = scales = _row_scales(graph, t0.scalers, t0.avg_d, dev)
-        self.y = y = torch.empty(V, out_pitch(N), dtype=torch.float32, device=dev)[:, :N]
-        self.res = res = h if layer.residual else None
-        self.slope = float(mix.activation.negative_slope)
-        if t0.graph_norm and snorm_n is not None:
-            post = snorm_n.reshape(-1).to(torch.float32)[plan.perm_all().long()]
-            self.post_g, self.post_r = post[:plan.NV].contiguous(), post[plan.NV:].contiguous()
-        else:
-            self.post_g, self.post_r = plan.ones_rows(), None
-        desc, ids, n_rec = plan.fused_tables()
-        self.keep = [desc, ids, x_cat]
-        a = _lib.PnaFusedDegreeArgs()
-        self.arith = DG.bind_fused_arith(a, self.keep, Wv, Fi, scales, plan, True, dev)
-        a.tile_desc, a.tile_ids, a.n_records = _lib.dev_ptr(desc, torch.int32, "tile_desc"), _lib.dev_ptr(ids, torch.int32, "tile_ids"), n_rec
-        a.x, a.ldx, a.x_rows, a.F, a.N = _lib.dev_ptr(self.x_src, torch.float32, "x_src"), x_cat.stride(0), V, Fi, N
+        super().__init__(layer, graph, h, snorm_n, [x_cat])
+        self.Wv, self.d, self.c, self.ones, self.K = _tower_flat_weights(layer, towers, layer.mixing_network)
+        self.Fe, self.x_src, self.x_dst = Fi, x_cat[:, :Fi], x_cat[:, P:P + Fi]
+        a = self._block(self.Wv, Fi, self.x_src, self.Wv.shape[0], tower=True)
         a.x_dst, a.ld_xdst = _lib.dev_ptr(self.x_dst, torch.float32, "x_dst"), x_cat.stride(0)
         a.h_self, a.ld_h = _lib.dev_ptr(h, torch.float32, "h"), h.stride(0)
-        a.row_post = _lib.dev_ptr(self.post_g, torch.float32, "row_post")
-        a.row_perm, a.M, a.n_nodes = _lib.dev_ptr(plan.perm, torch.int32, "row_perm"), plan.NV, V
-        a.bias = _lib.dev_ptr(d, torch.float32, "bias")
-        a.col_scale, a.col_shift = _lib.dev_ptr(ones, torch.float32, "col_scale"), _lib.dev_ptr(c, torch.float32, "col_shift")
-        if res is not None:
-            a.residual, a.ld_res = _lib.dev_ptr(res, torch.float32, "residual"), res.stride(0)
-        a.y, a.ldy, a.relu, a.act_slope = _lib.dev_ptr(y, torch.float32, "y"), y.stride(0), 2, self.slope
-        a.y_cols_writable = own_buffer_cols(y.stride(0), 0, N, N)
-        self.args, self.ref = a, ctypes.byref(a)
-        self.fn, self.check, self.stream = _lib.lib().pna_fused_degree_f32, _lib.check, _lib.stream_ptr(dev)
-        _bind_tile_order(self, 0)
+        self._tower_final(a)
+        self._bind(0)
 
-    def layer_F(self):
-        return self.args.F
-
-    def set_spare(self, on):
-        from . import degree_groups as DG
-        _bind_tile_order(self, DG.FUSED_SPARE_WGS if on else 0)
-
-    def group_rows(self):
-        self.check(self.fn(self.ref, self.stream), "pna_fused_degree_f32")
-        return self.y
-
-    def rest_rows(self):
-        plan, graph, t0 = self.plan, self.graph, self.t0
-        if plan.NR:
-            from . import degree_groups as DG
-            from .dgl.pna_layer import _avg_log_value
-            Fi, K, N = self.Fe, self.K, self.Wv.shape[0]
-            items, orow, hout, hs = plan.rest_items_by_node(graph)
-            agg = torch.empty(plan.NRp, DG.agg_pitch(K), dtype=torch.float32, device=self.y.device)
-            csr = graph.csr
-            ops.segreduce(csr.rowptr, csr.col, self.x_src, Fi, t0.aggregators, (None,), n_tower=1, tower_stride_in=Fi, dst_term=self.x_dst,
-                          out=agg, tower_stride_out=4 * Fi, heavy=hs, workspace=graph.workspace, items=items, out_row_of=orow, heavy_out=hout,
-                          tune=dict(generic=2, rows_per_group=DG.REST_ROWS_PER_GROUP))
-            ops.pack_rows(_unit_stride(self.h), plan.perm_all()[plan.NV:], out=agg[:, 4 * Fi:5 * Fi])
-            rest_scales = plan.rest_scales(tuple(t0.scalers) + (_avg_log_value(t0.avg_d),), self.scales)
-            ops.posttrans(agg[:, :K], K, self.Wv, rest_scales, self.d, out=self.y, row_post=self.post_r, col_scale=self.ones, col_shift=self.c,
-                          leaky_slope=self.slope, residual=self.res, row_perm=plan.perm_rest, n_out=N)
-        return self.y
+    def _rest_operands(self):
+        items, orow, hout, hs = self.plan.rest_items_by_node(self.graph)
+        gather = dict(tower_stride_in=self.Fe, dst_term=self.x_dst, heavy=hs, items=items, out_row_of=orow, heavy_out=hout)
+        return self.Fe, 1, gather, _unit_stride(self.h), self.Wv
 
 
 def _tower_pass_weights(layer, towers, mix):
@@ -949,7 +975,7 @@ def _tower_pass_weights(layer, towers, mix):
 DENSE_TERM_RESIDENT = True          # FusedMultiTowerCall.dense_term through pna_project_scaled_f32 where it applies (False: contraction + rank-S update)
 
 
-class FusedMultiTowerCall:
+class FusedMultiTowerCall(_FusedTowerRows):
     """One PNALayer forward with T towers over the WHOLE input (divide_input=False; models/dgl/pna_layer.py:137-139; eval) on the one-kernel
     path (round 6).  Every tower has its own projection of the input -- T x Fi message features per edge -- and a wavefront
     cannot hold T x 80 running statistics: the layer is one dense launch over the rows' own features (everything linear in h_v: the
@@ -960,83 +986,30 @@ class FusedMultiTowerCall:
     row of partial sums.  `rest_rows()`: the rows no degree group holds, all towers at once on the two-kernel path."""
 
     def __init__(self, layer, graph, h, snorm_n, x_src):
-        from . import _lib, degree_groups as DG
-        from .dgl.pna_layer import _row_scales
-        import ctypes
-        towers, mix = list(layer.towers), layer.mixing_network
-        t0 = towers[0]
-        T, Fi, V, dev = len(towers), t0.in_dim, h.shape[0], h.device
-        P = x_src.shape[1] // T
-        self.layer, self.graph, self.plan, self.t0, self.T, self.Fi, self.P = layer, graph, DG.plan_of(graph), t0, T, Fi, P
-        plan = self.plan
-        Ws, self.Wd, self.beta, self.Wr, self.d, self.c, self.ones = _tower_pass_weights(layer, towers, mix)
-        d, c, ones = self.d, self.c, self.ones
-        N = Ws[0].shape[0]
-        self.x_src, self.h = x_src, h
-        self.scales = scales = _row_scales(graph, t0.scalers, t0.avg_d, dev)
-        self.y = y = torch.empty(V, out_pitch(N), dtype=torch.float32, device=dev)[:, :N]
+        towers = list(layer.towers)
+        T, Fi, V, dev = len(towers), towers[0].in_dim, h.shape[0], h.device
+        Ws, self.Wd, self.beta, self.Wr, self.d, self.c, self.ones = _tower_pass_weights(layer, towers, layer.mixing_network)
+        super().__init__(layer, graph, h, snorm_n, [x_src, Ws])
+        self.T, self.Fi, self.P, self.x_src = T, Fi, x_src.shape[1] // T, x_src
+        N, P = Ws[0].shape[0], self.P
         # partial sums ping-pong between two buffers: a launch never writes the rows it reads -- the guard's second launch computes a
         # handed-over tile AGAIN from the same pre_add rows (in place it would add the tile's share twice: found by tools/fuzz_fused.py)
         self._part_full = torch.empty(V, out_pitch(N), dtype=torch.float32, device=dev)
-        self.part = part = self._part_full[:, :N]
+        self.part = self._part_full[:, :N]
         self.part2 = torch.empty(V, out_pitch(N), dtype=torch.float32, device=dev)[:, :N] if T > 1 else None
         # beta padded to the buffer's pitch: the rank-S update runs in place on the whole buffer
         self.beta_pad = memo(layer, "_pna_amd_beta_pad", [self.beta], out_pitch(N),
                              lambda: torch.nn.functional.pad(self.beta, (0, out_pitch(N) - N)))
-        self.res = res = h if layer.residual else None
-        self.slope = float(mix.activation.negative_slope)
-        if t0.graph_norm and snorm_n is not None:
-            post = snorm_n.reshape(-1).to(torch.float32)[plan.perm_all().long()]
-            self.post_g, self.post_r = post[:plan.NV].contiguous(), post[plan.NV:].contiguous()
-        else:
-            self.post_g, self.post_r = plan.ones_rows(), None
         # the scalers of the dense term: zero for rows without in-edges (DGL leaves their aggregate -- the destination term with it -- at zero)
-        hit = plan.__dict__.setdefault("_masked_scales", {})
-        mkey = tuple(None if r is None else r.data_ptr() for r in scales)
-        if mkey not in hit:
-            if len(hit) > 8:
-                hit.clear()
-            live = (plan._deg > 0).to(torch.float32)
-            ms = [live if r is None else (r * live).contiguous() for r in scales]
-            hit[mkey] = (ms, torch.stack(ms, dim=1).contiguous())
-        self.mscales, self.mscale_mat = hit[mkey]
-        desc, ids, n_rec = plan.fused_tables()
-        self.keep = [desc, ids, x_src, Ws]
-        blocks = []
+        self.mscales, self.mscale_mat = self.plan.masked_scales(self.scales)
         for t in range(T):
-            last = t == T - 1
-            a = _lib.PnaFusedDegreeArgs()
-            self.arith = DG.bind_fused_arith(a, self.keep, Ws[t], Fi, scales, plan, False, dev)
-            a.tile_desc, a.tile_ids, a.n_records = _lib.dev_ptr(desc, torch.int32, "tile_desc"), _lib.dev_ptr(ids, torch.int32, "tile_ids"), n_rec
-            xs = x_src[:, t * P:t * P + Fi]
-            a.x, a.ldx, a.x_rows, a.F, a.N = _lib.dev_ptr(xs, torch.float32, "x_src"), x_src.stride(0), V, Fi, N
-            a.row_perm, a.M, a.n_nodes = _lib.dev_ptr(plan.perm, torch.int32, "row_perm"), plan.NV, V
-            src_buf, dst_buf = (part, self.part2) if t % 2 == 0 else (self.part2, part)
-            a.pre_add, a.ld_pre_add = _lib.dev_ptr(src_buf, torch.float32, "pre_add"), src_buf.stride(0)
-            if last:
-                a.row_post = _lib.dev_ptr(self.post_g, torch.float32, "row_post")
-                a.bias = _lib.dev_ptr(d, torch.float32, "bias")
-                a.col_scale, a.col_shift = _lib.dev_ptr(ones, torch.float32, "col_scale"), _lib.dev_ptr(c, torch.float32, "col_shift")
-                if res is not None:
-                    a.residual, a.ld_res = _lib.dev_ptr(res, torch.float32, "residual"), res.stride(0)
-                a.y, a.ldy, a.relu, a.act_slope = _lib.dev_ptr(y, torch.float32, "y"), y.stride(0), 2, self.slope
-                a.y_cols_writable = own_buffer_cols(y.stride(0), 0, N, N)
-            else:                                            # a partial sum: no bias, no factor, no activation
-                a.y, a.ldy, a.relu = _lib.dev_ptr(dst_buf, torch.float32, "y"), dst_buf.stride(0), 0
-                a.y_cols_writable = own_buffer_cols(dst_buf.stride(0), 0, N, N)
-            blocks.append((a, ctypes.byref(a)))
-        self.launch_order = blocks
-        self.panel_args = [blocks[-1]] + blocks[:-1]         # (_bind_tile_order: the primary block is the one whose row_post follows the tile order)
-        self.args, self.ref = blocks[-1]
-        self.fn, self.check, self.stream = _lib.lib().pna_fused_degree_f32, _lib.check, _lib.stream_ptr(dev)
-        _bind_tile_order(self, 0)
-
-    def layer_F(self):
-        return self.Fi
-
-    def set_spare(self, on):
-        from . import degree_groups as DG
-        _bind_tile_order(self, DG.FUSED_SPARE_WGS if on else 0)
+            src_buf, dst_buf = (self.part, self.part2) if t % 2 == 0 else (self.part2, self.part)
+            a = self._block(Ws[t], Fi, x_src[:, t * P:t * P + Fi], N, pre_add=src_buf)
+            if t == T - 1:
+                self._tower_final(a)
+            else:
+                self._partial(a, dst_buf, 0, N)
+        self._bind(T - 1)
 
     def dense_term(self):
         """part = W_self h + sum_s scale_s [deg > 0] (M_s h + beta_s): one contraction launch over the rows' own features + a rank-S update."""
@@ -1048,34 +1021,12 @@ class FusedMultiTowerCall:
         torch.addmm(self._part_full, self.mscale_mat, self.beta_pad, out=self._part_full)   # (+= [deg > 0] scale_s beta_s; the padding columns stay unread)
         return self.part
 
-    def prologue(self):
-        """What both halves read: the dense term of every row (run_fused_call launches it in front of the fork)."""
-        self.dense_term()
+    prologue = dense_term                                    # (what both halves read: run_fused_call launches it in front of the fork)
 
-    def group_rows(self):
-        for _, ref in self.launch_order:
-            self.check(self.fn(ref, self.stream), "pna_fused_degree_f32")
-        return self.y
-
-    def rest_rows(self):
-        plan, graph, t0, T, Fi, P = self.plan, self.graph, self.t0, self.T, self.Fi, self.P
-        if plan.NR:
-            from . import degree_groups as DG
-            from .dgl.pna_layer import _avg_log_value
-            N, Ka = self.Wr.shape[0], T * 4 * Fi
-            K = Ka + N
-            items, hout, hs = plan.rest_items(graph)
-            agg = torch.empty(plan.NRp, DG.agg_pitch(K), dtype=torch.float32, device=self.y.device)
-            csr = graph.csr
-            # statistics of a_u alone, all towers (the destination term is in the dense term, like the group rows')
-            ops.segreduce(csr.rowptr, csr.col, self.x_src, Fi, t0.aggregators, (None,), n_tower=T, tower_stride_in=P,
-                          out=agg, tower_stride_out=4 * Fi, heavy=hs, workspace=graph.workspace, items=items, heavy_out=hout,
-                          tune=dict(generic=2, rows_per_group=DG.REST_ROWS_PER_GROUP))
-            ops.pack_rows(self.part, plan.perm_all()[plan.NV:], out=agg[:, Ka:K])
-            rest_scales = plan.rest_scales(tuple(t0.scalers) + (_avg_log_value(t0.avg_d),), self.scales)
-            ops.posttrans(agg[:, :K], K, self.Wr, rest_scales, self.d, out=self.y, row_post=self.post_r, col_scale=self.ones, col_shift=self.c,
-                          leaky_slope=self.slope, residual=self.res, row_perm=plan.perm_rest, n_out=N)
-        return self.y
+    def _rest_operands(self):
+        # statistics of a_u alone, all towers (the destination term is in the dense term, like the group rows'); the dense term rides behind them
+        items, hout, hs = self.plan.rest_items(self.graph)
+        return self.Fi, self.T, dict(tower_stride_in=self.P, heavy=hs, items=items, heavy_out=hout), self.part, self.Wr
 
 
 def tower_layer_degree_fused_multi(layer, graph, h, snorm_n, x_src):
@@ -1092,85 +1043,49 @@ def tower_layer_degree_fused(layer, graph, h, snorm_n, x_cat):
     return run_fused_call(FusedTowerCall(layer, graph, h, snorm_n, x_cat))
 
 
-class FusedDegreeCall:
+class FusedDegreeCall(_FusedCall):
     """One PNASimpleLayer forward on the one-kernel path, cut into its two halves so that bench.py can time them apart:
     `group_rows()` = pna_fused_degree_f32 (99.6 % of the benchmark graph's rows) -- one launch per output-column panel
     (degree_groups.fused_panels: one, unless the layer is wider than an instantiation) --, `rest_rows()` = gather + three-block
     contraction over the compact list of the rows no degree group holds.  Holds the argument blocks and every tensor they point into."""
 
     def __init__(self, layer, graph, h, x=None, out=None, agg_out=None, plan=None):
-        from . import _lib, degree_groups as DG
         from .dgl.pna_layer import _row_scales
-        import ctypes
-        F, N = layer.in_dim, layer.out_dim
-        self.layer, self.graph, self.plan = layer, graph, DG.plan_of(graph) if plan is None else plan      # (plan: a row block's)
-        plan = self.plan
+        F, N, V = layer.in_dim, layer.out_dim, h.shape[0]
         self.x = x = graph.source_features(h) if x is None else x
         lin = layer.posttrans.fully_connected[0].linear
-        self.scales = scales = _row_scales(graph, layer.scalers, layer.avg_d, h.device)
-        V = h.shape[0]
         # (rows at a 16-byte aligned pitch: the next layer of a stack can read them in 16-byte strips, i.e. stay on this path)
-        self.y = y = torch.empty(V, out_pitch(N), dtype=torch.float32, device=h.device)[:, :N] if out is None else out
+        y = torch.empty(V, out_pitch(N), dtype=torch.float32, device=h.device)[:, :N] if out is None else out
+        super().__init__(layer, graph, DG.plan_of(graph) if plan is None else plan, h,      # (plan: a row block's)
+                         _row_scales(graph, layer.scalers, layer.avg_d, h.device), y, [lin, agg_out, h])
         self.cs, self.ct, self.res = cs, ct, res = _layer_tail_operands(layer, h)
-        desc, ids, n_rec = plan.fused_tables()
-        self.keep = [desc, ids, lin, agg_out, h]
         aggs = tuple(layer.aggregators)
         panels = DG.fused_panels(F, N)
         if panels is None or not DG.aggregators_fusable(aggs):
             raise RuntimeError(f"pna_fused_degree: no instantiation for F={F}, N={N}, aggregators={aggs}")
         if agg_out is not None and (len(panels) != 1 or aggs != DG.STANDARD_AGGREGATORS):
             raise RuntimeError("pna_fused_degree: agg_out (verification) takes the four standard aggregators and a one-launch layer")
-        self.panel_args = []
         whole = len(panels) == 1
         last_f0 = panels[-1][0]                               # (the feature panel whose launches apply the epilogue)
         self.part = None
         if any(f0 != last_f0 for f0, _, _, _ in panels):      # feature panels: partial sums between the launches
             self.part = torch.empty(V, out_pitch(N), dtype=torch.float32, device=h.device)[:, :N]
         for f0, f1, c0, c1 in panels:
-            a = _lib.PnaFusedDegreeArgs()
-            final, first = f0 == last_f0, f0 == 0
-            self.arith = DG.bind_fused_arith(a, self.keep, lin.weight, F, scales, plan, False, h.device, verification=agg_out is not None,
-                                             rows=None if whole else (c0, c1), aggregators=aggs, feats=None if (f0, f1) == (0, F) else (f0, f1))
-            a.tile_desc, a.tile_ids, a.n_records = _lib.dev_ptr(desc, torch.int32, "tile_desc"), _lib.dev_ptr(ids, torch.int32, "tile_ids"), n_rec
-            a.x, a.ldx, a.x_rows, a.F, a.N = _lib.dev_ptr(x[:, f0:f1], torch.float32, "x"), x.stride(0), x.shape[0], f1 - f0, c1 - c0
-            a.row_perm, a.M, a.n_nodes = _lib.dev_ptr(plan.perm, torch.int32, "row_perm"), plan.NV, V
+            a = self._block(lin.weight, F, x[:, f0:f1], c1 - c0, pre_add=self.part[:, c0:c1] if f0 else None, verification=agg_out is not None,
+                            rows=None if whole else (c0, c1), aggregators=aggs, feats=None if (f0, f1) == (0, F) else (f0, f1))
             sl = lambda t: None if t is None else t[c0:c1]      # noqa: E731  (a panel's slice of a per-column vector: still unit stride)
-            if not first:
-                a.pre_add, a.ld_pre_add = _lib.dev_ptr(self.part[:, c0:c1], torch.float32, "pre_add"), self.part.stride(0)
-            if final:
-                a.bias = _lib.dev_ptr(sl(lin.bias), torch.float32, "bias")
-                a.col_scale, a.col_shift = _lib.dev_ptr(sl(cs), torch.float32, "col_scale"), _lib.dev_ptr(sl(ct), torch.float32, "col_shift")
-                if res is not None:
-                    a.residual, a.ld_res = _lib.dev_ptr(res[:, c0:c1], torch.float32, "residual"), res.stride(0)
-                a.y, a.ldy, a.relu = _lib.dev_ptr(y[:, c0:c1], torch.float32, "y"), y.stride(0), 1
-                if out is None:
-                    a.y_cols_writable = own_buffer_cols(y.stride(0), c0, c1, N)
-            else:                                            # a partial sum: no bias, no BatchNorm, no activation, no residual
-                a.y, a.ldy, a.relu = _lib.dev_ptr(self.part[:, c0:c1], torch.float32, "y"), self.part.stride(0), 0
-                a.y_cols_writable = own_buffer_cols(self.part.stride(0), c0, c1, N)
+            if f0 == last_f0:
+                self._final(a, y[:, c0:c1], sl(lin.bias), sl(cs), sl(ct), None if res is None else res[:, c0:c1], 1,
+                            cols_writable=own_buffer_cols(y.stride(0), c0, c1, N) if out is None else 0)
+            else:
+                self._partial(a, self.part, c0, c1)
             if agg_out is not None:
                 a.agg_out, a.ld_agg = _lib.dev_ptr(agg_out, torch.float32, "agg_out"), agg_out.stride(0)
-            self.panel_args.append((a, ctypes.byref(a)))
-        self.args, self.ref = self.panel_args[0]
-        self.fn, self.check, self.stream = _lib.lib().pna_fused_degree_f32, _lib.check, _lib.stream_ptr(h.device)
-        _bind_tile_order(self, 0)
-
-    def layer_F(self):
-        return self.layer.in_dim
-
-    def set_spare(self, on):
-        from . import degree_groups as DG
-        _bind_tile_order(self, DG.FUSED_SPARE_WGS if on else 0)
-
-    def group_rows(self):
-        for _, ref in self.panel_args:
-            self.check(self.fn(ref, self.stream), "pna_fused_degree_f32")
-        return self.y
+        self._bind(0)
 
     def rest_rows(self):
         plan, layer, graph = self.plan, self.layer, self.graph
         if plan.NR:
-            from . import degree_groups as DG
             F = layer.in_dim
             K = 4 * F                                        # (the four standard statistics whatever the layer's list: _rest_posttrans)
             Kb = 5 * F if "sum" in layer.aggregators else K  # (+ room for the sum block)
@@ -1199,7 +1114,6 @@ def simple_layer_degree_grouped(layer, graph, h):
     aggregate in degree order, the contraction multiplies every tile by its degree's combined weight W_D = sum_s s_s(D) W_s
     (one scaler block instead of three), the rows of rare degrees and the hub rows take the ordinary three-block contraction
     over a compacted list."""
-    from . import degree_groups as DG
     plan = DG.plan_of(graph)
     from .graph import Graph
     aggs = tuple(layer.aggregators)
@@ -1233,8 +1147,6 @@ class _SmallSimplePlan(_SmallTowerPlan):
     node whose own feature is Inf / NaN keeps the finite output the reference and the three-kernel path give it."""
 
     def __init__(self, layer):
-        import ctypes
-        from . import _lib
         lin = layer.posttrans.fully_connected[0].linear
         bn = layer.batchnorm_h if layer.batch_norm else None
         if bn is not None and bn.training:
@@ -1300,7 +1212,6 @@ class SimpleLayerRows:
     wants_full_out = True          # BlockPipeline hands __call__ the whole next table (the one-kernel layer scatters rows by node id)
 
     def __init__(self, layers, graph, n_blocks, fused=None):
-        from . import degree_groups as DG
         self.layers, self.g = list(layers), graph
         l0 = self.layers[0]
         self.F = l0.in_dim
@@ -1325,7 +1236,6 @@ class SimpleLayerRows:
         degree value that fills a tile, mostly leftover rows).  Blocks 1.. hold only the rows of their range whose degree fills
         tiles INSIDE the block (one launch each); block 0 takes, besides its own rows, the hub rows and every block's leftovers
         (its chain of small rest-row launches runs once per layer, first: a row may be ready earlier than its block, never later)."""
-        from . import degree_groups as DG
         if not self._plans:
             V, B = self.g.num_nodes, self.n_blocks
             bounds = [(V * i) // B for i in range(B + 1)]
@@ -1341,7 +1251,6 @@ class SimpleLayerRows:
 
     def __call__(self, l, table, r0, r1, out, b):
         from .dgl.pna_layer import _row_scales
-        from . import degree_groups as DG
         layer, g, F = self.layers[l], self.g, self.F
         csr = g.csr
         K = 4 * F
