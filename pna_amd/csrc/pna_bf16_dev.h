@@ -1,5 +1,6 @@
-// pna_bf16_dev.h -- device helpers shared by the bf16 inference kernels (pna_bf16.hip, pna_bf16_tower.hip): the bf16 <-> fp32
-// conversions, the per-lane statistics of the gather kernels (8 features per lane, fp32) and the finalisation of one row.
+// pna_bf16_dev.h -- device helpers shared by the bf16 inference kernels (pna_bf16_gather.hip, pna_bf16_contract.hip,
+// pna_bf16_small.hip): the bf16 <-> fp32 conversions, the per-lane statistics of a gather (8 features per lane, fp32), the ONE fold
+// over a row's in-edges (fold_edges) and the ONE finalisation of a row's statistics (finish_stats).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,9 +71,83 @@ __device__ __forceinline__ void fold(Acc& c, const float (&v)[8]) {
   }
 }
 
-// finalize one row's statistics (pna_rowstats.h: the fp32 kernel's formulas) and store every aggregator block, rounded to bf16 once
-template <bool VOUT>
-__device__ __forceinline__ void finish_row(const SegArgs& a, int row, int deg, int f0, const Acc& c) {
+// The optional message term of fold_edges: message of CSR edge k = x[col[k]] + dst + edge row, formed in fp32.  dst: this lane's 8
+// columns of the destination row (null: +0.0 is added, which turns a gathered -0.0 into +0.0); er: this lane's 8 columns of edge row
+// 0 (null: no edge term), rows lde apart; et: the edge's row in a table of n_er rows (null: CSR edge k reads row k).
+struct MsgTerm {
+  const u16* dst; const u16* er; int64_t lde; const int32_t* et; int n_er;
+};
+
+// The in-edges [beg, end) of one destination row folded in CSR order for the 8 features at xb of every source row (nf of them
+// exist); four edges in flight per lane.  V8 / VT: 16-byte loads of the source rows / of the term rows.  MSG = false: no term is
+// read or added (not even a zero: -0.0 + 0.0 is +0.0, and max / min would see it).  TYPED: edge rows always come from the type table.
+template <bool V8, bool VT, bool MSG, bool TYPED = false>
+__device__ __forceinline__ void fold_edges(const int32_t* col, const u16* xb, int64_t ldx, int beg, int end, int nf, const MsgTerm& t,
+                                           Acc& c) {
+  float d[8];
+  if (MSG) {
+    if (t.dst) {
+      load8<VT>(t.dst, nf, d);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d[j] = 0.f;
+    }
+  }
+  const u16* eb = MSG ? t.er : nullptr;
+  auto edge_row = [&](int k) __attribute__((always_inline)) {
+    if (!TYPED && !t.et) return (size_t)k;
+    int r = t.et[k];
+    r = r < 0 ? 0 : r >= t.n_er ? t.n_er - 1 : r;              // a type outside the table reads a row of the table, never beyond it
+    return (size_t)r;
+  };
+  int k = beg;
+  for (; k + 4 <= end; k += 4) {
+    int id[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) id[u] = col[k + u];
+    float v[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) load8<V8>(xb + (size_t)id[u] * ldx, nf, v[u]);
+    if (MSG) {
+      if (eb) {
+        float w[4][8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) load8<VT>(eb + edge_row(k + u) * t.lde, nf, w[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[u][j] = (v[u][j] + d[j]) + w[u][j];
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[u][j] = v[u][j] + d[j];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) fold(c, v[u]);
+  }
+  for (; k < end; ++k) {
+    float v[8];
+    load8<V8>(xb + (size_t)col[k] * ldx, nf, v);
+    if (MSG) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = v[j] + d[j];
+      if (eb) {
+        float w[8];
+        load8<VT>(eb + edge_row(k) * t.lde, nf, w);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = v[j] + w[j];
+      }
+    }
+    fold(c, v);
+  }
+}
+
+// One row's statistics of nf <= 8 features finalized (pna_rowstats.h: the fp32 kernel's formulas): store(ai, r) receives the eight
+// values of aggregator block ai, each rounded to bf16 once (zeros for deg <= 0 and for the features beyond nf).
+template <class Store>
+__device__ __forceinline__ void finish_stats(int deg, int nf, const Acc& c, int n_aggr, const int* aggr, Store store) {
   float mean[8], msq[8];
   const float D = (float)deg, invD = 1.0f / D;
 #pragma unroll
@@ -80,15 +155,13 @@ __device__ __forceinline__ void finish_row(const SegArgs& a, int row, int deg, i
     mean[j] = pna_dev::div_rn(c.s[j], D, invD);
     msq[j] = pna_dev::div_rn(c.q[j], D, invD);
   }
-  u16* o = a.out + (size_t)row * a.ldo + f0;
-  const int nw = a.F - f0 < 8 ? a.F - f0 : 8;         // element stores: only the block's own features
-  for (int ai = 0; ai < a.n_aggr; ++ai) {
-    const int code = a.aggr[ai];
+  for (int ai = 0; ai < n_aggr; ++ai) {
+    const int code = aggr[ai];
     u16 r[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float val;
-      if (deg <= 0 || f0 + j >= a.F) {
+      if (deg <= 0 || j >= nf) {
         val = 0.f;
       } else {
         float var = msq[j] - mean[j] * mean[j];
@@ -104,18 +177,33 @@ __device__ __forceinline__ void finish_row(const SegArgs& a, int row, int deg, i
       }
       r[j] = f2bf(val);
     }
+    store(ai, r);
+  }
+}
+
+// eight bf16 values as one 16-byte store
+__device__ __forceinline__ void store8(u16* o, const u16 (&r)[8]) {
+  u4 w;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = (unsigned)r[2 * j] | ((unsigned)r[2 * j + 1] << 16);
+  *reinterpret_cast<u4*>(o) = w;
+}
+
+// one row's aggregator blocks into a.out: 16-byte stores (VOUT), else element stores of the block's own features only
+template <bool VOUT>
+__device__ __forceinline__ void finish_row(const SegArgs& a, int row, int deg, int f0, const Acc& c) {
+  u16* o = a.out + (size_t)row * a.ldo + f0;
+  const int nf = a.F - f0, nw = nf < 8 ? nf : 8;
+  finish_stats(deg, nf, c, a.n_aggr, a.aggr, [&](int ai, const u16 (&r)[8]) __attribute__((always_inline)) {
     u16* ob = o + (size_t)ai * a.bs;
     if (VOUT) {
-      u4 w;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w[j] = (unsigned)r[2 * j] | ((unsigned)r[2 * j + 1] << 16);
-      *reinterpret_cast<u4*>(ob) = w;
+      store8(ob, r);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         if (j < nw) ob[j] = r[j];
     }
-  }
+  });
 }
 
 // the fp32 partials (s, q, mx, mn) of one heavy-row segment, [n_seg][4][F8]

@@ -2,10 +2,10 @@
 // and at most two launches for PNALayer / PNATower / PNASimpleLayer in inference (the bf16 counterpart of pna_tower_layer_f32,
 // pna_tower_fused.hip).  See include/pna_amd.h for the arguments and the arithmetic contract, DESIGN.md 4.12 for the layout.
 //
-// Launch 1 is pna_contract_bf16 (pna_bf16_tower.hip) on the projection image: x_cat = [x_src | x_dst] of every tower, each tower's
+// Launch 1 is pna_contract_bf16 (pna_bf16_contract.hip) on the projection image: x_cat = [x_src | x_dst] of every tower, each tower's
 // block Fp = round8(Fi) columns wide so that every 8-feature piece is one 16-byte load.
 // Launch 2, k_tower_rows_bf16: one workgroup (4 wavefronts) per 16 destination rows.
-//   gather    one lane per (row, tower, 8 features): x_src[u] + x_dst[v] + edge row in fp32, the statistics of pna_bf16_dev.h, every
+//   gather    one lane per (row, tower, 8 features): x_src[u] + x_dst[v] + edge row in fp32 (fold_edges and finish_stats of pna_bf16_dev.h), every
 //             aggregate rounded to bf16 into the LDS tile agg[16][T][A][Fp]; the rows' own features h go to a second LDS tile
 //   towers    one wavefront per (tower, 16 output columns): the tower's OWN weight blocks only (A Fp columns per scaler, Fi for the
 //             self block), v_mfma_f32_16x16x32_bf16 with the A fragments from LDS and the B fragments straight from the weight image
@@ -44,105 +44,6 @@ struct RArgs {
   u16* y; int64_t ldy;
   int LA, LH, LC;                             // LDS row pitches (elements) of the three tiles
 };
-
-__device__ __forceinline__ u4 pack8(const u16 (&r)[8]) {
-  u4 w;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) w[j] = (unsigned)r[2 * j] | ((unsigned)r[2 * j + 1] << 16);
-  return w;
-}
-
-// the in-edges of destination `row` folded in CSR order for the 8 features at column c0 of the source rows; four edges in flight
-template <bool V8>
-__device__ __forceinline__ void gather_piece(const RArgs& a, int row, int beg, int end, int c0, int nf, Acc& c) {
-  const u16* xb = a.x + c0;
-  float d[8];
-  if (a.dst_off >= 0) {
-    load8<true>(a.x + (size_t)row * a.ldx + a.dst_off + c0, 8, d);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d[j] = 0.f;
-  }
-  const u16* eb = a.et ? a.etab + c0 : nullptr;
-  auto edge_row = [&](int k) __attribute__((always_inline)) {
-    int t = a.et[k];
-    t = t < 0 ? 0 : t >= a.n_et ? a.n_et - 1 : t;              // a type outside the table reads a row of the table, never beyond it
-    return (size_t)t;
-  };
-  int k = beg;
-  for (; k + 4 <= end; k += 4) {
-    int id[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) id[u] = a.col[k + u];
-    float v[4][8];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) load8<V8>(xb + (size_t)id[u] * a.ldx, nf, v[u]);
-    if (eb) {
-      float w[4][8];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) load8<true>(eb + edge_row(k + u) * a.lde, 8, w[u]);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[u][j] = (v[u][j] + d[j]) + w[u][j];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[u][j] = v[u][j] + d[j];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) fold(c, v[u]);
-  }
-  for (; k < end; ++k) {
-    float v[8];
-    load8<V8>(xb + (size_t)a.col[k] * a.ldx, nf, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = v[j] + d[j];
-    if (eb) {
-      float w[8];
-      load8<true>(eb + edge_row(k) * a.lde, 8, w);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = v[j] + w[j];
-    }
-    fold(c, v);
-  }
-}
-
-// the statistics of one piece finalized (pna_bf16_dev.h finish_row: the same formulas) into the A aggregator blocks of an LDS row
-__device__ __forceinline__ void finish_piece(const RArgs& a, int deg, int nf, const Acc& c, u16* o) {
-  float mean[8], msq[8];
-  const float D = (float)deg, invD = 1.0f / D;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    mean[j] = pna_dev::div_rn(c.s[j], D, invD);
-    msq[j] = pna_dev::div_rn(c.q[j], D, invD);
-  }
-  for (int ai = 0; ai < a.A; ++ai) {
-    const int code = a.aggr[ai];
-    u16 r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float val;
-      if (deg <= 0 || j >= nf) {
-        val = 0.f;
-      } else {
-        float var = msq[j] - mean[j] * mean[j];
-        var = var < 0.f ? 0.f : var;
-        switch (code) {
-          case PNA_AGG_MEAN: val = mean[j]; break;
-          case PNA_AGG_SUM: val = c.s[j]; break;
-          case PNA_AGG_MAX: val = c.q[j] != c.q[j] ? c.q[j] : c.mx[j]; break;
-          case PNA_AGG_MIN: val = c.q[j] != c.q[j] ? c.q[j] : c.mn[j]; break;
-          case PNA_AGG_STD: val = sqrtf(var + 1e-5f); break;
-          default: val = var; break;                   // PNA_AGG_VAR
-        }
-      }
-      r[j] = f2bf(val);
-    }
-    *reinterpret_cast<u4*>(o + ai * a.Fp) = pack8(r);
-  }
-}
 
 // acc[b] += A (16 LDS rows at `al`, pitch la) . B_b^T (16 rows of NB weight blocks `stride` elements apart at `w`, pitch kp) over kp
 // columns: one A fragment per 32 columns for all blocks, their B fragments in flight together
@@ -189,8 +90,17 @@ __global__ __launch_bounds__(kBlock) void k_tower_rows_bf16(const RArgs a) {
       const int beg = a.rowptr[row], end = a.rowptr[row + 1];
       Acc c;
       acc_init(c);
-      gather_piece<V8>(a, row, beg, end, t * a.Fp + f0, a.Fi - f0, c);
-      finish_piece(a, end - beg, a.Fi - f0, c, agg + r * a.LA + t * a.Kp + f0);
+      // x_src[u] + x_dst[row] + the edge type's table row: the terms are always whole 16-byte pieces
+      const int c0 = t * a.Fp + f0;
+      MsgTerm m;
+      m.dst = a.dst_off >= 0 ? a.x + (size_t)row * a.ldx + a.dst_off + c0 : nullptr;
+      m.er = a.et ? a.etab + c0 : nullptr;
+      m.lde = a.lde; m.et = a.et; m.n_er = a.n_et;
+      fold_edges<V8, true, true, true>(a.col, a.x + c0, a.ldx, beg, end, a.Fi - f0, m, c);
+      u16* o = agg + r * a.LA + t * a.Kp + f0;                  // the A aggregator blocks of the LDS row
+      finish_stats(end - beg, a.Fi - f0, c, a.A, a.aggr, [&](int ai, const u16 (&v)[8]) __attribute__((always_inline)) {
+        store8(o + ai * a.Fp, v);
+      });
     }
   }
   // ---- the rows' own features, one block of round32(Fi) columns per input slice

@@ -611,33 +611,27 @@ def tower_layer(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *, n_t
     return out
 
 
-# ---- bf16 inference of PNASimpleLayer (pna_bf16.hip) -------------------------------------------------------------------------
+# ---- bf16 inference of PNASimpleLayer (pna_bf16_gather.hip, pna_bf16_contract.hip) ------------------------------------------------
 _BF16_AGGS = ("mean", "sum", "max", "min", "std", "var")
 
 
-def segreduce_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
-                   block_stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
-                   heavy: Optional[HeavySchedule] = None, workspace=None):
-    """bf16 (V, A * bs) aggregate (bs = block_stride, default F) of the bf16 source rows x (any pitch >= F) through
-    pna_segreduce_fwd_bf16: fp32 statistics rounded to bf16 once, identity scaler.  The returned tensor's pitch is a multiple of
-    8 elements.  block_stride a multiple of 8: the columns [F, round8(F)) of every block hold zeros."""
-    V = rowptr.numel() - 1
-    A = len(aggregators)
-    bs = F if block_stride is None else int(block_stride)
+def _tail_readable(t: torch.Tensor, F: int) -> bool:
+    """Whether the columns [F, round8(F)) of every row of the 2-D view t lie inside its storage (16-byte row pieces may read them)."""
+    if F % 8 == 0 or t.shape[0] == 0:
+        return True
+    last = t.storage_offset() + (t.shape[0] - 1) * _ld(t) + (F + 7) // 8 * 8
+    return last * t.element_size() <= t.untyped_storage().nbytes()
+
+
+def _run_gather_bf16(a, entry: str, rowptr, col, x, F, aggregators, out, bs, heavy, workspace):
+    """Fills what pna_segreduce_bf16_args and pna_gather_bf16_args share (graph, source rows, aggregator codes, output, heavy-row
+    schedule and its workspace), calls `entry` and keeps a workspace of its own alive on the stream."""
     dev = x.device
-    if out is None:
-        width = (A - 1) * bs + F
-        out = torch.empty(V, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)[:, :width]
-    a = _lib.PnaSegreduceBf16Args()
     a.rowptr = _lib.dev_ptr(rowptr, torch.int32, "rowptr")
     a.col = _lib.dev_ptr(col, torch.int32, "col")
-    a.V, a.F = V, F
+    a.V, a.F = rowptr.numel() - 1, F
     a.x, a.ldx = _lib.dev_ptr(x, torch.bfloat16, "x"), _ld(x)
-    if F % 8 and x.shape[0] > 0:
-        # the 16-byte gather reads up to round8(F) columns of every row: allowed when the storage holds them
-        last = x.storage_offset() + (x.shape[0] - 1) * _ld(x) + (F + 7) // 8 * 8
-        a.x_tail_readable = int(last * x.element_size() <= x.untyped_storage().nbytes())
-    a.n_aggr = A
+    a.n_aggr = len(aggregators)
     for i, name in enumerate(aggregators):
         if name not in _BF16_AGGS:
             raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
@@ -652,11 +646,37 @@ def segreduce_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: 
         nbytes = _lib.lib().pna_segreduce_bf16_partials_bytes(heavy.n_seg, F)
         keep = workspace(nbytes) if workspace is not None else torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         a.partials = _lib.dev_ptr(keep, torch.float32, "partials")
-    rc = _lib.lib().pna_segreduce_fwd_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
-    _lib.check(rc, "pna_segreduce_fwd_bf16")
+    rc = getattr(_lib.lib(), entry)(ctypes.byref(a), _lib.stream_ptr(dev))
+    _lib.check(rc, entry)
     if keep is not None and workspace is None:
         keep.record_stream(torch.cuda.current_stream(dev))
     return out
+
+
+def _fill_row_scales(a, row_scales, M):
+    for i, rs in enumerate(row_scales):
+        if rs is not None:
+            if rs.numel() != M:
+                raise ValueError("row scale must have one entry per row")
+            a.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+
+
+def segreduce_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
+                   block_stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                   heavy: Optional[HeavySchedule] = None, workspace=None):
+    """bf16 (V, A * bs) aggregate (bs = block_stride, default F) of the bf16 source rows x (any pitch >= F) through
+    pna_segreduce_fwd_bf16: fp32 statistics rounded to bf16 once, identity scaler.  The returned tensor's pitch is a multiple of
+    8 elements.  block_stride a multiple of 8: the columns [F, round8(F)) of every block hold zeros."""
+    V = rowptr.numel() - 1
+    A = len(aggregators)
+    bs = F if block_stride is None else int(block_stride)
+    if out is None:
+        width = (A - 1) * bs + F
+        out = torch.empty(V, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=x.device)[:, :width]
+    a = _lib.PnaSegreduceBf16Args()
+    # the 16-byte gather reads up to round8(F) columns of every row: allowed when the storage holds them
+    a.x_tail_readable = int(_tail_readable(x, F))
+    return _run_gather_bf16(a, "pna_segreduce_fwd_bf16", rowptr, col, x, F, aggregators, out, bs, heavy, workspace)
 
 
 def pack_posttrans_weight_bf16(weight: torch.Tensor, n_scaler: int, A: int, F: int, Fb: int):
@@ -692,11 +712,7 @@ def posttrans_bf16(agg: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_s
         out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     a = _lib.PnaPosttransBf16Args()
     a.a, a.lda, a.M, a.K, a.N, a.n_scaler = _lib.dev_ptr(agg, torch.bfloat16, "agg"), _ld(agg), M, K, N, S
-    for i, rs in enumerate(row_scales):
-        if rs is not None:
-            if rs.numel() != M:
-                raise ValueError("row scale must have one entry per row")
-            a.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+    _fill_row_scales(a, row_scales, M)
     a.w_img = _lib.dev_ptr(w_img, torch.bfloat16, "w_img")
     a.bias = _lib.dev_ptr(bias, torch.bfloat16, "bias")
     a.epilogue, a.relu = int(epilogue), int(relu)
@@ -710,15 +726,7 @@ def posttrans_bf16(agg: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_s
     return out
 
 
-# ---- bf16 inference of PNALayer / PNATower (pna_bf16_tower.hip) --------------------------------------------------------------
-def _tail_readable(t: torch.Tensor, F: int) -> bool:
-    """Whether the columns [F, round8(F)) of every row of the 2-D view t lie inside its storage (16-byte row pieces may read them)."""
-    if F % 8 == 0 or t.shape[0] == 0:
-        return True
-    last = t.storage_offset() + (t.shape[0] - 1) * _ld(t) + (F + 7) // 8 * 8
-    return last * t.element_size() <= t.untyped_storage().nbytes()
-
-
+# ---- bf16 inference of PNALayer / PNATower (pna_bf16_gather.hip, pna_bf16_contract.hip) ------------------------------------------
 def gather_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
                 dst_term: Optional[torch.Tensor] = None, edge_rows: Optional[torch.Tensor] = None,
                 edge_type: Optional[torch.Tensor] = None, block_stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
@@ -735,10 +743,6 @@ def gather_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int
         width = A * bs if bs % 8 == 0 else (A - 1) * bs + F
         out = torch.empty(V, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)[:, :width]
     a = _lib.PnaGatherBf16Args()
-    a.rowptr = _lib.dev_ptr(rowptr, torch.int32, "rowptr")
-    a.col = _lib.dev_ptr(col, torch.int32, "col")
-    a.V, a.F = V, F
-    a.x, a.ldx = _lib.dev_ptr(x, torch.bfloat16, "x"), _ld(x)
     tails = _tail_readable(x, F)
     if dst_term is not None:
         if dst_term.shape[0] != V or dst_term.shape[1] < F:
@@ -758,26 +762,7 @@ def gather_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int
     elif edge_type is not None:
         raise ValueError("edge_type without edge_rows")
     a.tails_readable = int(tails)
-    a.n_aggr = A
-    for i, name in enumerate(aggregators):
-        if name not in _BF16_AGGS:
-            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
-        a.aggr[i] = _lib.AGG_CODES[name]
-    a.out, a.ldo, a.block_stride = _lib.dev_ptr(out, torch.bfloat16, "out"), _ld(out), bs
-    keep = None
-    if heavy is not None and heavy.n_heavy > 0:
-        a.heavy_threshold, a.seg_len, a.n_heavy, a.n_seg = heavy.threshold, heavy.seg_len, heavy.n_heavy, heavy.n_seg
-        a.heavy_rows = _lib.dev_ptr(heavy.heavy_rows, torch.int32, "heavy_rows")
-        a.heavy_segptr = _lib.dev_ptr(heavy.heavy_segptr, torch.int32, "heavy_segptr")
-        a.seg_heavy = _lib.dev_ptr(heavy.seg_heavy, torch.int32, "seg_heavy")
-        nbytes = _lib.lib().pna_segreduce_bf16_partials_bytes(heavy.n_seg, F)
-        keep = workspace(nbytes) if workspace is not None else torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-        a.partials = _lib.dev_ptr(keep, torch.float32, "partials")
-    rc = _lib.lib().pna_gather_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
-    _lib.check(rc, "pna_gather_bf16")
-    if keep is not None and workspace is None:
-        keep.record_stream(torch.cuda.current_stream(dev))
-    return out
+    return _run_gather_bf16(a, "pna_gather_bf16", rowptr, col, x, F, aggregators, out, bs, heavy, workspace)
 
 
 def contract_image_bf16(blocks: torch.Tensor):
@@ -814,11 +799,7 @@ def contract_bf16(a: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_scal
         raise ValueError(f"pna_contract_bf16: operand {tuple(a.shape)} / image {tuple(w_img.shape)} do not fit K={K}, N={N}, {S} blocks")
     g = _lib.PnaContractBf16Args()
     g.a, g.lda, g.M, g.K, g.N, g.n_scaler = _lib.dev_ptr(a, torch.bfloat16, "a"), _ld(a), M, K, N, S
-    for i, rs in enumerate(row_scales):
-        if rs is not None:
-            if rs.numel() != M:
-                raise ValueError("row scale must have one entry per row")
-            g.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+    _fill_row_scales(g, row_scales, M)
     g.w_img = _lib.dev_ptr(w_img, torch.bfloat16, "w_img")
     if h_self is not None:
         Kh = h_self.shape[1]
@@ -891,11 +872,7 @@ def tower_layer_bf16(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *
         xc = torch.empty(V, xw, dtype=torch.bfloat16, device=dev)
         a.x_cat, a.ldx = _lib.dev_ptr(xc, torch.bfloat16, "x_cat"), xw
         a.proj_img, a.proj_bias = _lib.dev_ptr(proj_img, torch.bfloat16, "proj_img"), _lib.dev_ptr(proj_bias, torch.bfloat16, "proj_bias")
-    for i, rs in enumerate(row_scales):
-        if rs is not None:
-            if rs.numel() != V:
-                raise ValueError("row scale must have one entry per row")
-            a.row_scale[i] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+    _fill_row_scales(a, row_scales, V)
     a.post_img, a.post_bias = _lib.dev_ptr(post_img, torch.bfloat16, "post_img"), _lib.dev_ptr(post_bias, torch.bfloat16, "post_bias")
     for name, t, n in (("row_post", row_post, V), ("col_scale", col_scale, n_tower * Fo), ("col_shift", col_shift, n_tower * Fo)):
         if t is not None:

@@ -13,6 +13,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pna_amd", "csrc")
 
 
+# The bf16 gather (pna_bf16_gather.hip), per instantiation <V8, VOUT, MSG> / <V8, MSG>: the plain gather of big graphs (MSG = false)
+# keeps >= 5 wavefronts per SIMD (<= 96 registers) and must not inherit the message fold's ~144; the message gather stays on its
+# step of 3 wavefronts per SIMD (<= 168).
+_B = ("Lb0E", "Lb1E")
+BF16_GATHER_CAPS = {f"k_gather_bf16{kern}Lb{msg}EEE": cap for msg, cap in ((0, 96), (1, 168))
+                    for kern in [f"I{v}{o}" for v in _B for o in _B] + [f"_segI{v}" for v in _B]}
+
+
 # (the grouped one-block kernel runs two 8-wavefront workgroups per CU: above 128 registers it would silently drop to one; the
 #  three-block grouped kernel runs 12 wavefronts per CU: 168)
 @pytest.mark.parametrize("src,max_vgpr", [("pna_posttrans_x3.hip", {"k_posttrans_x3": 256, "k_posttrans_x3ILi1ELb0ELi80ELi5ELi1ELi8ELi3ELb0ELb1EEE": 128,
@@ -31,7 +39,12 @@ CSRC = os.path.join(ROOT, "pna_amd", "csrc")
                                           # the one-kernel layer: two 4-wavefront workgroups per CU (the production instantiations: DUMP = false)
                                           # (incl. the tower instantiations ...ELb0ELb1ELb0EEE of the two-full-block shapes)
                                           ("pna_fused_degree.hip", {"k_fused_degreeILi1ELb0ELb0E": 256, "k_fused_degreeILi1ELb1ELb0E": 256,
-                                                                    "k_fused_degreeILi2ELb0ELb0E": 256, "k_fused_degreeILi2ELb1ELb0E": 256})])
+                                                                    "k_fused_degreeILi2ELb0ELb0E": 256, "k_fused_degreeILi2ELb1ELb0E": 256}),
+                                          # the bf16 inference family (new entries go LAST: the test ids carry the position); the
+                                          # contraction has no cap (its accumulators sit in AGPRs), the one-call layer stays at 3
+                                          # wavefronts per SIMD
+                                          ("pna_bf16_gather.hip", BF16_GATHER_CAPS), ("pna_bf16_contract.hip", {}),
+                                          ("pna_bf16_small.hip", {"k_tower_rows_bf16": 168})])
 def test_no_kernel_uses_scratch(src, max_vgpr, tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -52,6 +65,7 @@ def test_no_kernel_uses_scratch(src, max_vgpr, tmp_path):
            if s != 0 and "k_heavy_finalize" not in n and not (tail_128.search(n) and s <= 32)]
     assert not bad, f"kernels using scratch: {bad[:5]}"
     for key, lim in max_vgpr.items():
+        assert any(key in n for n in names), f"no kernel named {key}"
         over = [(n, v) for n, v in zip(names, vgprs) if key in n and v > lim]
         assert not over, over[:5]
     # every inline-asm memory instruction of every kernel: no SGPR operand written by a VALU instruction (an SGPR-spill reload)

@@ -1,4 +1,4 @@
-"""bf16 inference of PNASimpleLayer (pna_bf16.hip: pna_segreduce_fwd_bf16 + pna_posttrans_bf16) against the accuracy contract.
+"""bf16 inference of PNASimpleLayer (pna_bf16_gather.hip: pna_segreduce_fwd_bf16, pna_bf16_contract.hip: pna_posttrans_bf16) against the accuracy contract.
 
 The reference value is the layer evaluated in float64 on the exact bf16 values of the features and of every parameter
 (oracle/torch_oracle.py).  With u = 2^-8 and z the scaled aggregates, per output element of a one-layer posttrans:

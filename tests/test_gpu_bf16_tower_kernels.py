@@ -1,4 +1,4 @@
-"""Kernel-level checks of pna_bf16_tower.hip (pna_gather_bf16, pna_contract_bf16): one rounding each, inputs exact bf16,
+"""Kernel-level checks of pna_bf16_gather.hip (pna_gather_bf16) and pna_bf16_contract.hip (pna_contract_bf16): one rounding each, inputs exact bf16,
 reference float64 on those values.  The bar is the merged contract of the bf16 simple layer,
 
     |got - ref64| <= 2u |ref64| + 4u M_j,      u = 2^-8,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Same-box timing of the fp32 and the bf16 PNASimpleLayer forward (inference) on the bench graph, and the kernel means of the two
-bf16 kernels from a separate rocprofv3 kernel-trace run.
+"""Same-box timing of the fp32 and the bf16 PNASimpleLayer forward (inference) on the bench graph, and the kernel means of the
+bf16 kernels (k_gather_bf16*, k_posttrans_bf16) from a separate rocprofv3 kernel-trace run.
 
     python tools/bench_bf16.py [--shapes C3,C5] [--steps 20] [--warmup 5] [--out profiles/bf16_layer.json] [--no-trace]
 
@@ -102,7 +102,7 @@ def trace(shape, steps):
     out = {}
     for row in csv.DictReader(open(files[0])):
         name = row.get("Name", "")
-        for key in ("k_segreduce_bf16_seg", "k_segreduce_bf16_fin", "k_segreduce_bf16", "k_posttrans_bf16"):
+        for key in ("k_gather_bf16_seg", "k_gather_bf16_fin", "k_gather_bf16", "k_posttrans_bf16"):
             if key in name:
                 ent = out.setdefault(key, {"calls": 0, "total_ns": 0.0})
                 ent["calls"] += int(row["Calls"])
@@ -133,15 +133,15 @@ def main():
         ms16 = time_forward(l16, g, h16, args.steps, args.warmup)
         gb, pb = algorithmic_bytes(shape)
         ent = {"V_E_F": SHAPES[shape], "fp32_ms_per_step": ms32, "bf16_ms_per_step": ms16, "bf16_over_fp32": ms16 / ms32,
-               "bytes": {"k_segreduce_bf16": gb, "k_posttrans_bf16": pb}}
+               "bytes": {"k_gather_bf16": gb, "k_posttrans_bf16": pb}}
         del g, l32, l16, h32, h16
         torch.cuda.empty_cache()
         if not args.no_trace:
             k = trace(shape, args.steps)
             ent["kernels"] = k
-            if "k_segreduce_bf16" in k:
-                seg_us = sum(k[n]["mean_us"] for n in ("k_segreduce_bf16", "k_segreduce_bf16_seg", "k_segreduce_bf16_fin") if n in k)
-                ent["roofline_fraction"] = {"k_segreduce_bf16 (+ heavy segments)": gb / (seg_us * 1e-6) / HBM_PEAK}
+            if "k_gather_bf16" in k:
+                seg_us = sum(k[n]["mean_us"] for n in ("k_gather_bf16", "k_gather_bf16_seg", "k_gather_bf16_fin") if n in k)
+                ent["roofline_fraction"] = {"k_gather_bf16 (+ heavy segments)": gb / (seg_us * 1e-6) / HBM_PEAK}
                 if "k_posttrans_bf16" in k:
                     ent["roofline_fraction"]["k_posttrans_bf16"] = pb / (k["k_posttrans_bf16"]["mean_us"] * 1e-6) / HBM_PEAK
         res["shapes"][shape] = ent
