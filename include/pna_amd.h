@@ -30,6 +30,9 @@ extern "C" {
                                   pna_gather_bf16_args, pna_contract_bf16_args).
                                   23, additive: + pna_tower_layer_bf16 / pna_tower_layer_bf16_args (the bf16 tower layer of molecule batches
                                   as one call); no existing struct or entry point changed.
+                                  23, additive: + pna_edge_mlp_bf16 / pna_edge_mlp_bf16_args (the hidden layers of a deep pre_nn per edge: bf16
+                                  inference of the PyG front end) and PNA_AGG_STD_PYG, which the three bf16 statistics entry points accept
+                                  beside PNA_AGG_VAR_RAW; no existing struct changed.
                               22: + pna_segreduce_fwd_bf16 / pna_segreduce_bf16_partials_bytes, pna_posttrans_bf16 / pna_posttrans_bf16_tiles
                                   (bf16 inference of PNASimpleLayer; pna_segreduce_bf16_args, pna_posttrans_bf16_args).
                               21: the GUARDED fp16 x 2 contraction of the one-kernel layer (round 6): + pna_fused_degree_args.{w_img_x3,
@@ -91,7 +94,8 @@ enum {
   PNA_AGG_MIN = 3,  /* dgl/aggregators.py:14-15                                            */
   PNA_AGG_STD = 4,  /* dgl/aggregators.py:18-19  sqrt(relu(E[x^2]-E[x]^2) + 1e-5)          */
   PNA_AGG_VAR = 5,  /* dgl/aggregators.py:22-26  relu(E[x^2]-E[x]^2)                       */
-  PNA_AGG_VAR_RAW = 6 /* pytorch_geometric/aggregators.py:25-28  E[x^2]-E[x]^2, NOT clamped (forward only) */
+  PNA_AGG_VAR_RAW = 6, /* pytorch_geometric/aggregators.py:25-28  E[x^2]-E[x]^2, NOT clamped (forward only) */
+  PNA_AGG_STD_PYG = 7  /* pytorch_geometric/aggregators.py:31-32  std whose row without in-edges is sqrtf(1e-5f), not 0 (bf16 entry points only) */
 };
 #define PNA_MAX_AGGR 8
 #define PNA_MAX_SCALER 8
@@ -1001,7 +1005,7 @@ typedef struct pna_segreduce_bf16_args {
   int64_t ldx;
   int32_t x_tail_readable; /* 1 = columns [F, round8(F)) of every row of x may be read */
   int32_t n_aggr;
-  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_VAR */
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_STD_PYG */
   void* out;               /* bf16 (V, ldo), 16-byte aligned, ldo a multiple of 8 and >= (n_aggr - 1) * block_stride + F */
   int64_t ldo;
   int32_t block_stride;    /* columns between aggregator blocks (>= F); 0 = F */
@@ -1092,7 +1096,7 @@ typedef struct pna_gather_bf16_args {
   int32_t tails_readable;  /* 1 = columns [F, round8(F)) of every row of x, dst_term and edge_rows may be read */
   int32_t n_aggr;
   int32_t block_stride;    /* columns between aggregator blocks (>= F); 0 = F */
-  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_VAR */
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_STD_PYG */
   void* out;               /* bf16 (V, ldo), 16-byte aligned, ldo a multiple of 8 and >= (n_aggr - 1) * block_stride + F */
   int64_t ldo;
   int32_t heavy_threshold; /* the heavy-row schedule of pna_segreduce_bf16_args */
@@ -1193,7 +1197,7 @@ typedef struct pna_tower_layer_bf16_args {
   int32_t n_scaler;        /* 1..3 */
   int32_t n_aggr;          /* 1..PNA_MAX_AGGR */
   int32_t no_self_panel;   /* != 0: the PNASimpleLayer form */
-  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_VAR */
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_STD_PYG */
   const void* h;           /* bf16 (V, ldh) node features */
   int64_t ldh;
   void* x_cat;             /* bf16 (V, ldx) workspace, 2 T Fp columns, 16-byte aligned, ldx a multiple of 8 */
@@ -1222,6 +1226,51 @@ typedef struct pna_tower_layer_bf16_args {
 } pna_tower_layer_bf16_args;
 
 int pna_tower_layer_bf16(const pna_tower_layer_bf16_args* args, pna_stream_t stream);
+
+/* ---- the per-edge MLP of a deep pre_nn on bf16 messages (ABI 23, additive) --------------------------------------------------------
+ *
+ * pna_edge_mlp_bf16 -- the layers 2..L of PNAConv.pre_nns[t] = Linear, (ReLU, Linear) x (L - 1), models/pytorch_geometric/pna.py:
+ * 135-149, for every CSR edge and tower, from the node-level terms of the FIRST Linear (pna_contract_bf16) and without the
+ * (E, 2-3 F) concatenation.  With R = round to bf16 once, everything in between fp32, k = (j -> i) a CSR edge, j = col[k], i = row[k]:
+ *     z_1(k)  = R(relu((x_src[j] + x_dst[i]) + edge term(k)))              the three rows are added in this order
+ *     z_l(k)  = R(relu(W_l z_(l-1)(k) + b_l))        1 < l < L
+ *     out[k]  = R(W_L z_(L-1)(k) + b_L)                                    n_hidden = L - 1 >= 1 matrix layers in all
+ * Tower t lives at columns [t Fp, t Fp + F) of x_src, x_dst, edge_rows and out, Fp = round8(F): every 8-feature piece is one aligned
+ * 16-byte access; the columns [F, Fp) of the inputs are ignored and those of out are written as zeros.  edge term(k) = row
+ * edge_type[k] of edge_rows (values outside [0, n_edge_rows) read the nearest row) or, with edge_type NULL, row k; edge_rows NULL
+ * = no term.  Tiles of 16 consecutive CSR edges per wavefront on v_mfma_f32_16x16x32_bf16; the hidden weights of one tower stay in
+ * LDS.  No atomics, a fixed order of every sum: identical bits on every run.
+ *     w_img   bf16 [T][n_hidden][round16(F)][round32(Fp)], 16-byte aligned: element [t][l][n][k] = W_(l+2),t[n][k], zero elsewhere
+ *     bias    bf16 [T][n_hidden][F], required
+ * Returns PNA_E_INVALID for F outside 1..128 and when one tower's weights and the four 16-edge tiles of a workgroup --
+ * 2 (n_hidden round16(F) (round32(Fp) + 16) + 64 (round32(Fp) + 8)) bytes -- exceed 160 KiB of LDS. */
+typedef struct pna_edge_mlp_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_edge_mlp_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  int32_t E;               /* CSR edges */
+  int32_t T;               /* towers, 1..64 */
+  int32_t F;               /* width of every hidden layer per tower, 1..128 */
+  int32_t n_hidden;        /* L - 1 >= 1 */
+  const int32_t* col;      /* [E] source node of each CSR edge */
+  const int32_t* row;      /* [E] destination node of each CSR edge */
+  const void* x_src;       /* bf16 (nodes, ld_src), 16-byte aligned, ld_src a multiple of 8 and >= T Fp */
+  int64_t ld_src;
+  const void* x_dst;       /* bf16 (nodes, ld_dst), likewise */
+  int64_t ld_dst;
+  const void* edge_rows;   /* bf16 (n_edge_rows or E, ld_edge), likewise; nullable */
+  int64_t ld_edge;
+  const int32_t* edge_type; /* nullable [E] in CSR order */
+  int32_t n_edge_rows;     /* rows of edge_rows (>= 1 with edge_type) */
+  int32_t _pad0;
+  const void* w_img;
+  const void* bias;
+  void* out;               /* bf16 (E, ld_out), 16-byte aligned, ld_out a multiple of 8 and >= T Fp */
+  int64_t ld_out;
+} pna_edge_mlp_bf16_args;
+
+int pna_edge_mlp_bf16(const pna_edge_mlp_bf16_args* args, pna_stream_t stream);
+/* LDS bytes of one workgroup of pna_edge_mlp_bf16 (the formula above); -1 when F or n_hidden is out of range. */
+int64_t pna_edge_mlp_bf16_lds_bytes(int32_t F, int32_t n_hidden);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -17,7 +17,8 @@ PNA_ABI_VERSION = 23
 PNA_MAX_AGGR = 8
 PNA_MAX_SCALER = 8
 
-AGG_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5, "var_raw": 6}
+# (std_pyg: the bf16 entry points only -- the PyG std, whose row without in-edges is sqrt(1e-5) in the device code)
+AGG_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5, "var_raw": 6, "std_pyg": 7}
 
 
 class _Args(ctypes.Structure):
@@ -283,6 +284,19 @@ class PnaTowerLayerBf16Args(_Args):
     ]
 
 
+class PnaEdgeMlpBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("E", ctypes.c_int32), ("T", ctypes.c_int32), ("F", ctypes.c_int32), ("n_hidden", ctypes.c_int32),
+        ("col", ctypes.c_void_p), ("row", ctypes.c_void_p),
+        ("x_src", ctypes.c_void_p), ("ld_src", ctypes.c_int64), ("x_dst", ctypes.c_void_p), ("ld_dst", ctypes.c_int64),
+        ("edge_rows", ctypes.c_void_p), ("ld_edge", ctypes.c_int64), ("edge_type", ctypes.c_void_p),
+        ("n_edge_rows", ctypes.c_int32), ("_pad0", ctypes.c_int32),
+        ("w_img", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+        ("out", ctypes.c_void_p), ("ld_out", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -413,6 +427,10 @@ def lib():
         L.pna_contract_bf16_tiles.restype = ctypes.c_int
         L.pna_tower_layer_bf16.argtypes = [ctypes.POINTER(PnaTowerLayerBf16Args), ctypes.c_void_p]
         L.pna_tower_layer_bf16.restype = ctypes.c_int
+        L.pna_edge_mlp_bf16.argtypes = [ctypes.POINTER(PnaEdgeMlpBf16Args), ctypes.c_void_p]
+        L.pna_edge_mlp_bf16.restype = ctypes.c_int
+        L.pna_edge_mlp_bf16_lds_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        L.pna_edge_mlp_bf16_lds_bytes.restype = ctypes.c_int64
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

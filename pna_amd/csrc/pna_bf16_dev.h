@@ -1,5 +1,5 @@
 // pna_bf16_dev.h -- device helpers shared by the bf16 inference kernels (pna_bf16_gather.hip, pna_bf16_contract.hip,
-// pna_bf16_small.hip): the bf16 <-> fp32 conversions, the per-lane statistics of a gather (8 features per lane, fp32), the ONE fold
+// pna_bf16_small.hip, pna_bf16_edge_mlp.hip): the bf16 <-> fp32 conversions, the per-lane statistics of a gather (8 features per lane, fp32), the ONE fold
 // over a row's in-edges (fold_edges) and the ONE finalisation of a row's statistics (finish_stats).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -145,7 +145,8 @@ __device__ __forceinline__ void fold_edges(const int32_t* col, const u16* xb, in
 }
 
 // One row's statistics of nf <= 8 features finalized (pna_rowstats.h: the fp32 kernel's formulas): store(ai, r) receives the eight
-// values of aggregator block ai, each rounded to bf16 once (zeros for deg <= 0 and for the features beyond nf).
+// values of aggregator block ai, each rounded to bf16 once (zeros for the features beyond nf; for deg <= 0 zeros too, except
+// PNA_AGG_STD_PYG, whose empty row is sqrtf(1e-5f): the PyG rule).  PNA_AGG_VAR_RAW is the variance without the clamp at 0.
 template <class Store>
 __device__ __forceinline__ void finish_stats(int deg, int nf, const Acc& c, int n_aggr, const int* aggr, Store store) {
   float mean[8], msq[8];
@@ -161,17 +162,21 @@ __device__ __forceinline__ void finish_stats(int deg, int nf, const Acc& c, int 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float val;
-      if (deg <= 0 || j >= nf) {
+      if (j >= nf) {
         val = 0.f;
+      } else if (deg <= 0) {
+        val = code == PNA_AGG_STD_PYG ? sqrtf(1e-5f) : 0.f;
       } else {
-        float var = msq[j] - mean[j] * mean[j];
-        var = var < 0.f ? 0.f : var;
+        const float raw = msq[j] - mean[j] * mean[j];
+        const float var = raw < 0.f ? 0.f : raw;
         switch (code) {
           case PNA_AGG_MEAN: val = mean[j]; break;
           case PNA_AGG_SUM: val = c.s[j]; break;
           case PNA_AGG_MAX: val = c.q[j] != c.q[j] ? c.q[j] : c.mx[j]; break;
           case PNA_AGG_MIN: val = c.q[j] != c.q[j] ? c.q[j] : c.mn[j]; break;
-          case PNA_AGG_STD: val = sqrtf(var + 1e-5f); break;
+          case PNA_AGG_STD:
+          case PNA_AGG_STD_PYG: val = sqrtf(var + 1e-5f); break;
+          case PNA_AGG_VAR_RAW: val = raw; break;
           default: val = var; break;                   // PNA_AGG_VAR
         }
       }

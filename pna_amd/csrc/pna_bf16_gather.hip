@@ -122,7 +122,7 @@ int run_gather(const char* who, const pna_gather_bf16_args* p, bool msg, pna_str
   if (!p->rowptr || !p->col || !p->x || !p->out) return fail(who, "rowptr/col/x/out must be non-null");
   if (p->n_aggr < 1 || p->n_aggr > PNA_MAX_AGGR) return fail(who, "n_aggr out of range");
   for (int i = 0; i < p->n_aggr; ++i)
-    if (p->aggr[i] < PNA_AGG_MEAN || p->aggr[i] > PNA_AGG_VAR) return fail(who, "aggregator code must be mean/sum/max/min/std/var");
+    if (p->aggr[i] < PNA_AGG_MEAN || p->aggr[i] > PNA_AGG_STD_PYG) return fail(who, "aggregator code must be mean/sum/max/min/std/var/var_raw/std_pyg");
   const int bs = p->block_stride > 0 ? p->block_stride : p->F;
   if (bs < p->F || p->ldx < p->F || p->ldo < (int64_t)(p->n_aggr - 1) * bs + p->F || p->ldo % 8 != 0 || ((uintptr_t)p->out & 15) != 0)
     return fail(who, "leading dimensions too small, or out / ldo not 16-byte aligned");

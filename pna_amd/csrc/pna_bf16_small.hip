@@ -204,8 +204,8 @@ extern "C" int pna_tower_layer_bf16(const pna_tower_layer_bf16_args* p, pna_stre
   if (p->V < 0 || T < 1 || T > 64 || Fi < 1 || Fi > 2048 || Fo < 1 || Fo > 2048 || S < 1 || S > 3 || A < 1 || A > PNA_MAX_AGGR)
     return pna_set_error(PNA_E_INVALID, "pna_tower_layer_bf16: need V >= 0, 1 <= n_tower <= 64, 1 <= Fi, Fo <= 2048, 1 <= n_scaler <= 3, 1 <= n_aggr <= 8");
   for (int i = 0; i < A; ++i)
-    if (p->aggr[i] < PNA_AGG_MEAN || p->aggr[i] > PNA_AGG_VAR)
-      return pna_set_error(PNA_E_INVALID, "pna_tower_layer_bf16: aggregator code must be mean/sum/max/min/std/var");
+    if (p->aggr[i] < PNA_AGG_MEAN || p->aggr[i] > PNA_AGG_STD_PYG)
+      return pna_set_error(PNA_E_INVALID, "pna_tower_layer_bf16: aggregator code must be mean/sum/max/min/std/var/var_raw/std_pyg");
   const bool simple = p->no_self_panel != 0;
   if (simple && (T != 1 || p->mix_img || p->edge_type || p->divide_input))
     return pna_set_error(PNA_E_INVALID, "pna_tower_layer_bf16: no_self_panel is the one-tower form without mixing network and edge table");

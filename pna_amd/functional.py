@@ -1333,6 +1333,54 @@ def simple_layer_bf16(layer, graph, h):
     return y
 
 
+def _build_tower_images_bf16(pre, post, Fi, ed, scalers, A, divide_input, bns, dst_first=False, tower_pitch=None):
+    """The images of _tower_images_bf16 from the towers' first pretrans (`pre`) and posttrans (`post`) Linear modules.  ed: columns
+    of the edge part of a pretrans weight (0: none).  dst_first: the pretrans weight's columns are [destination | source | edge]
+    (the PyG order of PNAConv.pre_nns) rather than [source | destination | edge] (the DGL order).  tower_pitch: columns between the
+    towers' blocks in x_src / x_dst / the edge rows / every aggregator block (default Fi: packed; round8(Fi): the per-tower padded
+    layout pna_edge_mlp_bf16 reads and writes), P = round8(T tower_pitch)."""
+    T, No, S = len(pre), post[0].out_features, len(scalers)
+    Fs = Fi if tower_pitch is None else tower_pitch
+    P = (T * Fs + 7) // 8 * 8
+    Kin = T * Fi if divide_input else Fi
+    dev, bf = pre[0].weight.device, torch.bfloat16
+    cs, cd = (slice(Fi, 2 * Fi), slice(0, Fi)) if dst_first else (slice(0, Fi), slice(Fi, 2 * Fi))
+    perm = sorted(range(S), key=lambda s: scalers[s] != "identity")           # stable: an identity scaler first
+    proj = torch.zeros(1, 2 * P, Kin, dtype=bf, device=dev)
+    pbias = torch.zeros(2 * P, dtype=bf, device=dev)
+    edge = torch.zeros(1, P, max(ed, 1), dtype=bf, device=dev)
+    wpost = torch.zeros(S, T * No, A * P, dtype=bf, device=dev)
+    wself = torch.zeros(1, T * No, Kin, dtype=bf, device=dev)
+    for t in range(T):
+        r = slice(t * Fs, t * Fs + Fi)
+        c = slice(t * Fi, (t + 1) * Fi) if divide_input else slice(0, Fi)
+        W = pre[t].weight
+        proj[0, r, c] = W[:, cs]
+        proj[0, P + t * Fs:P + t * Fs + Fi, c] = W[:, cd]
+        pbias[P + t * Fs:P + t * Fs + Fi] = pre[t].bias
+        if ed:
+            edge[0, r, :ed] = W[:, 2 * Fi:]
+        Wp = post[t].weight                                                    # (No, (S A + 1) Fi): [h | scaler-major aggregates]
+        o = slice(t * No, (t + 1) * No)
+        wself[0, o, c] = Wp[:, :Fi]
+        blocks = Wp[:, Fi:].reshape(No, S, A, Fi)
+        for j, s in enumerate(perm):
+            wpost[j, o].view(No, A, P)[:, :, r] = blocks[:, s]
+    res = {
+        "P": P, "perm": perm,
+        "proj": ops.contract_image_bf16(proj), "proj_bias": pbias,
+        "edge": ops.contract_image_bf16(edge) if ed else None,
+        "post": ops.contract_image_bf16(wpost), "self": ops.contract_image_bf16(wself),
+        "post_bias": torch.cat([l.bias for l in post]).contiguous(),
+        "cs": None, "ct": None,
+    }
+    if bns:
+        folds = [_fold_batchnorm_f32(bn) for bn in bns]
+        res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
+        res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
+    return res
+
+
 def _tower_images_bf16(towers, divide_input):
     """The weight images of the bf16 tower layer (ops.contract_image_bf16), built once per version of EVERY tensor they are made
     from -- the pretrans and first posttrans Linear and the BatchNorm tensors of every tower -- and cached on the first tower.
@@ -1350,46 +1398,20 @@ def _tower_images_bf16(towers, divide_input):
     def build():
         pre = [t.pretrans.fully_connected[0].linear for t in towers]
         post = [t.posttrans.fully_connected[0].linear for t in towers]
-        T, Fi, ed, No = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
-        A, S = len(t0.aggregators), len(t0.scalers)
-        P = (T * Fi + 7) // 8 * 8
-        Kin = T * Fi if divide_input else Fi
-        dev, bf = pre[0].weight.device, torch.bfloat16
-        perm = sorted(range(S), key=lambda s: t0.scalers[s] != "identity")           # stable: an identity scaler first
-        proj = torch.zeros(1, 2 * P, Kin, dtype=bf, device=dev)
-        pbias = torch.zeros(2 * P, dtype=bf, device=dev)
-        edge = torch.zeros(1, P, max(ed, 1), dtype=bf, device=dev)
-        wpost = torch.zeros(S, T * No, A * P, dtype=bf, device=dev)
-        wself = torch.zeros(1, T * No, Kin, dtype=bf, device=dev)
-        for t in range(T):
-            r = slice(t * Fi, (t + 1) * Fi)
-            c = r if divide_input else slice(0, Fi)
-            W = pre[t].weight
-            proj[0, r, c] = W[:, :Fi]
-            proj[0, P + t * Fi:P + (t + 1) * Fi, c] = W[:, Fi:2 * Fi]
-            pbias[P + t * Fi:P + (t + 1) * Fi] = pre[t].bias
-            if ed:
-                edge[0, r, :ed] = W[:, 2 * Fi:]
-            Wp = post[t].weight                                                    # (No, (S A + 1) Fi): [h | scaler-major aggregates]
-            o = slice(t * No, (t + 1) * No)
-            wself[0, o, c] = Wp[:, :Fi]
-            blocks = Wp[:, Fi:].reshape(No, S, A, Fi)
-            for j, s in enumerate(perm):
-                wpost[j, o].view(No, A, P)[:, :, r] = blocks[:, s]
-        res = {
-            "P": P, "perm": perm,
-            "proj": ops.contract_image_bf16(proj), "proj_bias": pbias,
-            "edge": ops.contract_image_bf16(edge) if ed else None,
-            "post": ops.contract_image_bf16(wpost), "self": ops.contract_image_bf16(wself),
-            "post_bias": torch.cat([l.bias for l in post]).contiguous(),
-            "cs": None, "ct": None,
-        }
-        if bns:
-            folds = [_fold_batchnorm_f32(bn) for bn in bns]
-            res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
-            res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
-        return res
+        return _build_tower_images_bf16(pre, post, t0.in_dim, t0.edge_dim, t0.scalers, len(t0.aggregators), divide_input, bns)
     return memo(t0, "_pna_amd_bf16_images", ts, (divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns)), build)
+
+
+def _build_small_simple_images_bf16(lin, bn, A, S, F):
+    """The images of _small_simple_images_bf16 from the posttrans Linear `lin` (N, S A F) and the BatchNorm `bn` (None: none)."""
+    N = lin.out_features
+    Fp, Kp = (F + 7) // 8 * 8, (A * ((F + 7) // 8 * 8) + 31) // 32 * 32
+    blk = torch.zeros(S, N, A, Fp, dtype=torch.bfloat16, device=lin.weight.device)
+    blk[..., :F] = lin.weight.reshape(N, S, A, F).permute(1, 0, 2, 3)
+    post = torch.zeros(1, S, (N + 15) // 16 * 16, Kp, dtype=torch.bfloat16, device=lin.weight.device)
+    post[0, :, :N, :A * Fp] = blk.reshape(S, N, A * Fp)
+    cs, ct = _fold_batchnorm_f32(bn) if bn else (None, None)
+    return {"post": post, "post_bias": lin.bias, "cs": cs, "ct": ct}
 
 
 def _small_simple_images_bf16(layer):
@@ -1397,17 +1419,55 @@ def _small_simple_images_bf16(layer):
     reference-layout posttrans weight (N, S A F), the bias and the fp32-folded BatchNorm; cached per version of every source tensor."""
     lin, bn = layer.posttrans.fully_connected[0].linear, layer.batchnorm_h if layer.batch_norm else None
     ts = [lin.weight, lin.bias] + (_bn_tensors(bn) if bn else [])
-    A, S, F, N = len(layer.aggregators), len(layer.scalers), layer.in_dim, lin.out_features
+    A, S, F = len(layer.aggregators), len(layer.scalers), layer.in_dim
+    return memo(layer, "_pna_amd_bf16_small", ts, (A, S, bn.eps if bn else None),
+                lambda: _build_small_simple_images_bf16(lin, bn, A, S, F))
 
-    def build():
-        Fp, Kp = (F + 7) // 8 * 8, (A * ((F + 7) // 8 * 8) + 31) // 32 * 32
-        blk = torch.zeros(S, N, A, Fp, dtype=torch.bfloat16, device=lin.weight.device)
-        blk[..., :F] = lin.weight.reshape(N, S, A, F).permute(1, 0, 2, 3)
-        post = torch.zeros(1, S, (N + 15) // 16 * 16, Kp, dtype=torch.bfloat16, device=lin.weight.device)
-        post[0, :, :N, :A * Fp] = blk.reshape(S, N, A * Fp)
-        cs, ct = _fold_batchnorm_f32(bn) if bn else (None, None)
-        return {"post": post, "post_bias": lin.bias, "cs": cs, "ct": ct}
-    return memo(layer, "_pna_amd_bf16_small", ts, (A, S, bn.eps if bn else None), build)
+
+def _build_small_images_bf16(pre, post, Fi, ed, S, A, divide_input, bns, mix_lin, dst_first=False):
+    """The images of _small_images_bf16 from the towers' first pretrans / posttrans Linear modules and the mixing Linear (None: none);
+    ed and dst_first as in _build_tower_images_bf16."""
+    T, Fo = len(pre), post[0].out_features
+    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
+    Fp, Fop, Kp, Khp = r(Fi, 8), r(Fo, 16), r(A * r(Fi, 8), 32), r(Fi, 32)
+    Kin = T * Fi if divide_input else Fi
+    dev, bf = pre[0].weight.device, torch.bfloat16
+    cs, cd = (slice(Fi, 2 * Fi), slice(0, Fi)) if dst_first else (slice(0, Fi), slice(Fi, 2 * Fi))
+    proj = torch.zeros(1, 2 * T * Fp, Kin, dtype=bf, device=dev)
+    pbias = torch.zeros(2 * T * Fp, dtype=bf, device=dev)
+    edge = torch.zeros(1, T * Fp, max(ed, 1), dtype=bf, device=dev)
+    wpost = torch.zeros(T, S, Fop, Kp, dtype=bf, device=dev)
+    wself = torch.zeros(T, Fop, Khp, dtype=bf, device=dev)
+    for t in range(T):
+        c = slice(t * Fi, (t + 1) * Fi) if divide_input else slice(0, Fi)
+        W = pre[t].weight
+        proj[0, t * Fp:t * Fp + Fi, c] = W[:, cs]
+        proj[0, (T + t) * Fp:(T + t) * Fp + Fi, c] = W[:, cd]
+        pbias[(T + t) * Fp:(T + t) * Fp + Fi] = pre[t].bias
+        if ed:
+            edge[0, t * Fp:t * Fp + Fi, :ed] = W[:, 2 * Fi:]
+        Wp = post[t].weight                                                    # (Fo, (S A + 1) Fi): [h | scaler-major aggregates]
+        wself[t, :Fo, :Fi] = Wp[:, :Fi]
+        blk = torch.zeros(S, Fo, A, Fp, dtype=bf, device=dev)
+        blk[..., :Fi] = Wp[:, Fi:].reshape(Fo, S, A, Fi).permute(1, 0, 2, 3)
+        wpost[t, :, :Fo, :A * Fp] = blk.reshape(S, Fo, A * Fp)
+    res = {
+        "proj": ops.contract_image_bf16(proj), "proj_bias": pbias,
+        "edge": ops.contract_image_bf16(edge) if ed else None,
+        "post": torch.cat([wpost.reshape(-1), wself.reshape(-1)]),
+        "post_bias": torch.cat([l.bias for l in post]).contiguous(),
+        "cs": None, "ct": None, "mix": None, "mix_bias": None, "etab": None,
+    }
+    if bns:
+        folds = [_fold_batchnorm_f32(bn) for bn in bns]
+        res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
+        res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
+    if mix_lin is not None:
+        No = mix_lin.weight.shape[0]
+        res["mix"] = torch.zeros(r(No, 16), r(T * Fo, 32), dtype=bf, device=dev)
+        res["mix"][:No, :T * Fo] = mix_lin.weight
+        res["mix_bias"] = mix_lin.bias
+    return res
 
 
 def _small_images_bf16(towers, mix, divide_input):
@@ -1425,47 +1485,8 @@ def _small_images_bf16(towers, mix, divide_input):
     def build():
         pre = [t.pretrans.fully_connected[0].linear for t in towers]
         post = [t.posttrans.fully_connected[0].linear for t in towers]
-        T, Fi, ed, Fo = len(towers), t0.in_dim, t0.edge_dim, post[0].out_features
-        A, S = len(t0.aggregators), len(t0.scalers)
-        r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
-        Fp, Fop, Kp, Khp = r(Fi, 8), r(Fo, 16), r(A * r(Fi, 8), 32), r(Fi, 32)
-        Kin = T * Fi if divide_input else Fi
-        dev, bf = pre[0].weight.device, torch.bfloat16
-        proj = torch.zeros(1, 2 * T * Fp, Kin, dtype=bf, device=dev)
-        pbias = torch.zeros(2 * T * Fp, dtype=bf, device=dev)
-        edge = torch.zeros(1, T * Fp, max(ed, 1), dtype=bf, device=dev)
-        wpost = torch.zeros(T, S, Fop, Kp, dtype=bf, device=dev)
-        wself = torch.zeros(T, Fop, Khp, dtype=bf, device=dev)
-        for t in range(T):
-            c = slice(t * Fi, (t + 1) * Fi) if divide_input else slice(0, Fi)
-            W = pre[t].weight
-            proj[0, t * Fp:t * Fp + Fi, c] = W[:, :Fi]
-            proj[0, (T + t) * Fp:(T + t) * Fp + Fi, c] = W[:, Fi:2 * Fi]
-            pbias[(T + t) * Fp:(T + t) * Fp + Fi] = pre[t].bias
-            if ed:
-                edge[0, t * Fp:t * Fp + Fi, :ed] = W[:, 2 * Fi:]
-            Wp = post[t].weight                                                    # (Fo, (S A + 1) Fi): [h | scaler-major aggregates]
-            wself[t, :Fo, :Fi] = Wp[:, :Fi]
-            blk = torch.zeros(S, Fo, A, Fp, dtype=bf, device=dev)
-            blk[..., :Fi] = Wp[:, Fi:].reshape(Fo, S, A, Fi).permute(1, 0, 2, 3)
-            wpost[t, :, :Fo, :A * Fp] = blk.reshape(S, Fo, A * Fp)
-        res = {
-            "proj": ops.contract_image_bf16(proj), "proj_bias": pbias,
-            "edge": ops.contract_image_bf16(edge) if ed else None,
-            "post": torch.cat([wpost.reshape(-1), wself.reshape(-1)]),
-            "post_bias": torch.cat([l.bias for l in post]).contiguous(),
-            "cs": None, "ct": None, "mix": None, "mix_bias": None, "etab": None,
-        }
-        if bns:
-            folds = [_fold_batchnorm_f32(bn) for bn in bns]
-            res["cs"] = torch.cat([f[0] for f in folds]).contiguous()
-            res["ct"] = torch.cat([f[1] for f in folds]).contiguous()
-        if mix is not None:
-            No = mix.linear.weight.shape[0]
-            res["mix"] = torch.zeros(r(No, 16), r(T * Fo, 32), dtype=bf, device=dev)
-            res["mix"][:No, :T * Fo] = mix.linear.weight
-            res["mix_bias"] = mix.linear.bias
-        return res
+        return _build_small_images_bf16(pre, post, t0.in_dim, t0.edge_dim, len(t0.scalers), len(t0.aggregators), divide_input, bns,
+                                        mix.linear if mix is not None else None)
     return memo(t0, "_pna_amd_bf16_small", ts,
                 (divide_input, tuple(t0.scalers), tuple(t0.aggregators), tuple(bn.eps for bn in bns), mix is not None), build)
 
@@ -1598,3 +1619,212 @@ def tower_layer_bf16(layer, graph, h, e, snorm_n):
     slope = 1.0 if mix.activation is None else 0.0 if isinstance(mix.activation, torch.nn.ReLU) else mix.activation.negative_slope
     return ops.contract_bf16(h_cat, N, img, N, (None,), mix.linear.bias, slope=slope,
                              residual=(h if h.stride(-1) == 1 else h.contiguous()) if layer.residual else None, out=out)
+
+
+# ---- bf16 inference of the PyG front end (pytorch_geometric/pna.py: PNAConv, PNAConvSimple) ---------------------------------------
+# kernel names of the PyG aggregators in bf16: `var` is not clamped, `std` of a row without in-edges is sqrt(1e-5) (both in the device code)
+_PYG_BF16_AGG = {"sum": "sum", "mean": "mean", "min": "min", "max": "max", "var": "var_raw", "std": "std_pyg"}
+
+
+def pyg_row_factors(graph, scalers, avg_deg):
+    """fp32 [V] row factors of the PyG scalers (None = identity), computed by pytorch_geometric.scalers.row_factor once per graph,
+    scaler name and avg_deg value and kept on the graph: no device-to-host step on a later call."""
+    cache = graph.__dict__.setdefault("_pyg_row_factors", {})
+    out, deg = [], None
+    for s in scalers:
+        if s == "identity":
+            out.append(None)
+            continue
+        key = (s, avg_deg["lin"], avg_deg["log"])
+        f = cache.get(key)
+        if f is None:
+            from .pytorch_geometric.scalers import row_factor
+            if deg is None:
+                deg = graph.in_degrees().to(torch.float32)
+            f = cache[key] = row_factor(s, deg, avg_deg).contiguous()
+        out.append(f)
+    return out
+
+
+def _edge_ids(graph):
+    """int32 arange(E) on the graph's device, cached on the graph: the identity `col` under which the gather kernels aggregate
+    messages that are stored one row per CSR edge."""
+    ids = graph.__dict__.get("_edge_ids")
+    if ids is None:
+        ids = graph.__dict__["_edge_ids"] = torch.arange(graph.csr.col.numel(), dtype=torch.int32, device=graph.csr.col.device)
+    return ids
+
+
+def pyg_simple_bf16(conv, graph, x):
+    """PNAConvSimple.forward (models/pytorch_geometric/pna.py:232-253) in inference on bf16 features and parameters: the structure of
+    simple_layer_bf16 without BatchNorm, ReLU and residual -- pna_tower_layer_bf16 (slope 1) for molecule batches, else
+    pna_segreduce_fwd_bf16 and pna_posttrans_bf16 without epilogue -- under the PyG statistics rules.  A deeper post_nn runs its first
+    Linear on the kernel and the rest as the module's own bf16 ops."""
+    F, N = conv.F_in, conv.F_out
+    if x.dim() != 2 or x.shape[1] != F:
+        raise ValueError(f"expected features of shape (V, {F}), got {tuple(x.shape)}")
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    names = [_PYG_BF16_AGG[a] for a in conv.aggregator_names]
+    A, S = len(names), len(conv.scaler_names)
+    post = list(conv.post_nn)
+    lin = post[0]
+    scales = pyg_row_factors(graph, conv.scaler_names, conv.avg_deg)
+    csr = graph.csr
+    if bf16_small_applies(graph, x.shape[0], T=1, Fi=F, Fo=N, A=A, divide_input=False, posttrans_affine=len(post) == 1, no_self_panel=True):
+        im = memo(conv, "_pna_amd_bf16_small", [lin.weight, lin.bias], (A, S), lambda: _build_small_simple_images_bf16(lin, None, A, S, F))
+        return ops.tower_layer_bf16(csr.rowptr, csr.col, x, n_tower=1, Fi=F, Fo=N, divide_input=False, aggregators=names, row_scales=scales,
+                                    post_img=im["post"], post_bias=im["post_bias"], slope=1.0, no_self_panel=True)
+    Fb = (F + 7) // 8 * 8
+    agg = ops.segreduce_bf16(csr.rowptr, csr.col, x, F, names, block_stride=Fb, heavy=graph.heavy_schedule(), workspace=graph.workspace)
+    w_img = ops.pack_posttrans_weight_bf16(lin.weight, S, A, F, Fb)
+    y = ops.posttrans_bf16(agg, A * Fb, w_img, N, scales, lin.bias)
+    for m in post[1:]:
+        y = m(y)
+    return y
+
+
+def _pyg_conv_linears(conv):
+    """(first pre_nn Linear, hidden pre_nn Linears, first post_nn Linear) of every tower of a PNAConv."""
+    pre = [list(nn) for nn in conv.pre_nns]
+    return [p[0] for p in pre], [p[2::2] for p in pre], [nn[0] for nn in conv.post_nns]
+
+
+def _pyg_conv_tensors(conv, hidden):
+    """The keyed tensor list of the PNAConv image builders: every Linear they read -- edge_encoder, the first (and, `hidden`, every
+    later) pre_nn Linear and the first post_nn Linear of every tower, lin."""
+    pre, hid, post = _pyg_conv_linears(conv)
+    lins = pre + post + [conv.lin] + ([conv.edge_encoder] if conv.edge_dim is not None else [])
+    if hidden:
+        lins += [l for h in hid for l in h]
+    return [p for l in lins for p in (l.weight, l.bias)]
+
+
+def _pyg_conv_images_bf16(conv):
+    """The images of the multi-launch bf16 PNAConv, cached on the module per version of every source tensor: _build_tower_images_bf16
+    over the PyG column order [x_i (destination) | x_j (source) | enc] of pre_nns[t][0].weight -- packed towers with pre_layers = 1,
+    the per-tower padded layout with the image of pna_edge_mlp_bf16 (`mlp`, `mlp_bias`) for a deeper pre_nn -- plus the contraction
+    images of edge_encoder (`enc`, `enc_bias`) and of lin (`mix`)."""
+    deep = len(conv.pre_nns[0]) > 1
+    ts = _pyg_conv_tensors(conv, deep)
+
+    def build():
+        pre, hid, post = _pyg_conv_linears(conv)
+        Fi, use_edge = conv.F_in, conv.edge_dim is not None
+        im = _build_tower_images_bf16(pre, post, Fi, Fi if use_edge else 0, conv.scaler_names, len(conv.aggregator_names),
+                                      conv.divide_input, [], dst_first=True, tower_pitch=(Fi + 7) // 8 * 8 if deep else None)
+        im["mix"] = ops.contract_image_bf16(conv.lin.weight.unsqueeze(0))
+        im["enc"] = ops.contract_image_bf16(conv.edge_encoder.weight.unsqueeze(0)) if use_edge else None
+        im["enc_bias"] = conv.edge_encoder.bias if use_edge else None
+        if deep:
+            im["mlp"], im["mlp_bias"] = ops.edge_mlp_image_bf16([[l.weight for l in h] for h in hid], [[l.bias for l in h] for h in hid])
+        return im
+    return memo(conv, "_pna_amd_bf16_images", ts, (conv.divide_input, tuple(conv.scaler_names), tuple(conv.aggregator_names)), build)
+
+
+def _pyg_conv_small_images_bf16(conv):
+    """The images of pna_tower_layer_bf16 for a PNAConv with 1-layer pre_nns and post_nns (lin is the mixing network, slope 1), plus the
+    contraction image of edge_encoder; cached on the module per version of every source tensor."""
+    ts = _pyg_conv_tensors(conv, False)
+
+    def build():
+        pre, _, post = _pyg_conv_linears(conv)
+        Fi, use_edge = conv.F_in, conv.edge_dim is not None
+        im = _build_small_images_bf16(pre, post, Fi, Fi if use_edge else 0, len(conv.scaler_names), len(conv.aggregator_names),
+                                      conv.divide_input, [], conv.lin, dst_first=True)
+        im["enc"] = ops.contract_image_bf16(conv.edge_encoder.weight.unsqueeze(0)) if use_edge else None
+        im["enc_bias"] = conv.edge_encoder.bias if use_edge else None
+        return im
+    return memo(conv, "_pna_amd_bf16_small", ts, (conv.divide_input, tuple(conv.scaler_names), tuple(conv.aggregator_names)), build)
+
+
+def _pyg_edge_rows_bf16(im, ef, edge_dim, Fi, width):
+    """x_edge = R(W_e R(W_enc ef + b_enc)) for the rows of ef (CSR edges, or the rows of an edge-type table): two pna_contract_bf16
+    launches, no matmul per edge in torch."""
+    enc = ops.contract_bf16(ef.contiguous(), edge_dim, im["enc"], Fi, (None,), im["enc_bias"])
+    return ops.contract_bf16(enc, Fi, im["edge"], width)
+
+
+def _pyg_small_edge_table_bf16(im, rows, edge_dim, Fi, width):
+    """_pyg_edge_rows_bf16 of the <= 4 rows of Graph.edge_type_table, kept with the images while the rows are the same storage at the
+    same version (the key of _small_edge_table_bf16)."""
+    key = (rows.data_ptr(), rows._version, rows.shape, rows.dtype, rows.device)
+    hit = im["etab"]
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = im["etab"] = (key, _pyg_edge_rows_bf16(im, rows, edge_dim, Fi, width), rows)
+    return hit[1]
+
+
+def pyg_conv_bf16(conv, graph, x, edge_attr):
+    """PNAConv.forward (models/pytorch_geometric/pna.py:121-165) in inference on bf16 features and parameters: the structure of
+    tower_layer_bf16 without graph norm, BatchNorm and residual, with `lin` as the mixing network, under the PyG statistics rules.
+      pre_layers = 1   the node-level projections x_src = W_j x, x_dst = W_i x + b (pna_contract_bf16), the edge term
+                       W_e R(W_enc e + b_enc) per edge-type row or per edge (two more launches), pna_gather_bf16, the post_nns of all
+                       towers in one contraction, lin -- or ONE call, pna_tower_layer_bf16, when bf16_small_applies
+      pre_layers >= 2  the same projections in the per-tower padded layout, pna_edge_mlp_bf16 for the hidden layers (messages
+                       materialised in bf16, one row per CSR edge), pna_segreduce_fwd_bf16 over them under an identity `col`
+    A deeper post_nn runs its first Linear on the kernel and the rest as the module's own bf16 ops."""
+    T, Fi, Fo, N = conv.towers, conv.F_in, conv.F_out, conv.out_channels
+    Kin = T * Fi if conv.divide_input else Fi
+    if x.dim() != 2 or x.shape[1] != Kin:
+        raise ValueError(f"expected features of shape (V, {Kin}), got {tuple(x.shape)}")
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    names = [_PYG_BF16_AGG[a] for a in conv.aggregator_names]
+    A = len(names)
+    deep, post_affine = len(conv.pre_nns[0]) > 1, len(conv.post_nns[0]) == 1
+    use_edge = conv.edge_dim is not None
+    csr = graph.csr
+    etab = None
+    if use_edge:
+        # while a stream is capturing the table is taken only from register_edge_types: a table hashed from the VALUES of edge_attr
+        # would freeze the captured example's types into the replay (towers_bf16)
+        if not torch.cuda.is_current_stream_capturing() or graph.edge_types_registered(edge_attr):
+            etab = graph.edge_type_table(edge_attr)
+    scales = pyg_row_factors(graph, conv.scaler_names, conv.avg_deg)
+    if not deep and bf16_small_applies(graph, x.shape[0], T=T, Fi=Fi, Fo=Fo, A=A, divide_input=conv.divide_input, posttrans_affine=post_affine,
+                                       edge_features=use_edge, etab=etab, No=N):
+        im = _pyg_conv_small_images_bf16(conv)
+        if use_edge and not graph.edge_types_registered(edge_attr):
+            # a capture that follows these warm-up calls takes the per-edge multi-launch route for the first time: its images exist by
+            # then.  Both image sets are keyed on the same tensors, so the key just computed tells whether they are current.
+            d = conv.__dict__
+            hit = d.get("_pna_amd_bf16_images")
+            if hit is None or hit[0] != d["_pna_amd_bf16_small"][0]:
+                _pyg_conv_images_bf16(conv)
+        edge_type = edge_table = None
+        if etab is not None:
+            edge_type, edge_table = etab[0], _pyg_small_edge_table_bf16(im, etab[1], conv.edge_dim, Fi, T * ((Fi + 7) // 8 * 8))
+        return ops.tower_layer_bf16(csr.rowptr, csr.col, x, n_tower=T, Fi=Fi, Fo=Fo, divide_input=conv.divide_input, aggregators=names,
+                                    row_scales=scales, post_img=im["post"], post_bias=im["post_bias"], proj_img=im["proj"],
+                                    proj_bias=im["proj_bias"], mix_img=im["mix"], mix_bias=im["mix_bias"], No=N, slope=1.0,
+                                    edge_type=edge_type, edge_table=edge_table)
+    im = _pyg_conv_images_bf16(conv)
+    P = im["P"]
+    x_cat = ops.contract_bf16(x, Kin, im["proj"], 2 * P, (None,), im["proj_bias"])
+    edge_rows = edge_type = None
+    if use_edge:
+        if etab is not None:
+            edge_type, ef = etab
+        else:
+            ef = edge_attr[csr.eid]                       # per-edge features in CSR (destination-sorted) order
+        edge_rows = _pyg_edge_rows_bf16(im, ef, conv.edge_dim, Fi, P)
+    if deep:
+        msgs = ops.edge_mlp_bf16(csr.col, csr.row, x_cat[:, :P], x_cat[:, P:], n_tower=T, F=Fi, w_img=im["mlp"], bias=im["mlp_bias"],
+                                 edge_rows=edge_rows, edge_type=edge_type)
+        agg = ops.segreduce_bf16(csr.rowptr, _edge_ids(graph), msgs, P, names, block_stride=P, heavy=graph.heavy_schedule(),
+                                 workspace=graph.workspace)
+    else:
+        agg = ops.gather_bf16(csr.rowptr, csr.col, x_cat[:, :T * Fi], T * Fi, names, dst_term=x_cat[:, P:P + T * Fi], edge_rows=edge_rows,
+                              edge_type=edge_type, block_stride=P, heavy=graph.heavy_schedule(), workspace=graph.workspace)
+    y = ops.contract_bf16(agg, A * P, im["post"], T * Fo, [scales[s] for s in im["perm"]], im["post_bias"], h_self=x, w_self=im["self"])
+    if not post_affine:
+        outs = []
+        for t, nn in enumerate(conv.post_nns):
+            z = y[:, t * Fo:(t + 1) * Fo]
+            for m in list(nn)[1:]:
+                z = m(z)
+            outs.append(z)
+        y = torch.cat(outs, dim=1) if T > 1 else outs[0]
+    return ops.contract_bf16(y, N, im["mix"], N, (None,), conv.lin.bias, slope=1.0)

@@ -612,7 +612,8 @@ def tower_layer(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *, n_t
 
 
 # ---- bf16 inference of PNASimpleLayer (pna_bf16_gather.hip, pna_bf16_contract.hip) ------------------------------------------------
-_BF16_AGGS = ("mean", "sum", "max", "min", "std", "var")
+_BF16_AGGS = ("mean", "sum", "max", "min", "std", "var")        # the DGL registry's names (the DGL layers' predicate)
+_BF16_KERNEL_AGGS = _BF16_AGGS + ("var_raw", "std_pyg")         # + the PyG statistics rules: the unclamped var, std of an empty row = sqrt(1e-5)
 
 
 def _tail_readable(t: torch.Tensor, F: int) -> bool:
@@ -633,8 +634,8 @@ def _run_gather_bf16(a, entry: str, rowptr, col, x, F, aggregators, out, bs, hea
     a.x, a.ldx = _lib.dev_ptr(x, torch.bfloat16, "x"), _ld(x)
     a.n_aggr = len(aggregators)
     for i, name in enumerate(aggregators):
-        if name not in _BF16_AGGS:
-            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
+        if name not in _BF16_KERNEL_AGGS:
+            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_KERNEL_AGGS}, not {name!r}")
         a.aggr[i] = _lib.AGG_CODES[name]
     a.out, a.ldo, a.block_stride = _lib.dev_ptr(out, torch.bfloat16, "out"), _ld(out), bs
     keep = None
@@ -860,8 +861,8 @@ def tower_layer_bf16(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *
     a.V, a.n_tower, a.Fi, a.Fo, a.divide_input, a.n_scaler = V, n_tower, Fi, Fo, int(divide_input), len(row_scales)
     a.n_aggr, a.no_self_panel = len(aggregators), int(no_self_panel)
     for i, name in enumerate(aggregators):
-        if name not in _BF16_AGGS:
-            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_AGGS}, not {name!r}")
+        if name not in _BF16_KERNEL_AGGS:
+            raise ValueError(f"pna_amd: the bf16 aggregate supports {_BF16_KERNEL_AGGS}, not {name!r}")
         a.aggr[i] = _lib.AGG_CODES[name]
     a.h, a.ldh = _lib.dev_ptr(h, torch.bfloat16, "h"), _ld(h)
     xc = None
@@ -896,4 +897,69 @@ def tower_layer_bf16(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *
     rc = _lib.lib().pna_tower_layer_bf16(ctypes.byref(a), _lib.stream_ptr(dev))
     _lib.check(rc, "pna_tower_layer_bf16")
     del xc                                                   # (stream-ordered allocator: safe to release after the launch)
+    return out
+
+
+# ---- the hidden layers of a deep pre_nn per edge (pna_bf16_edge_mlp.hip: bf16 inference of the PyG PNAConv) -----------------------
+def edge_mlp_bf16_lds_bytes(F: int, n_hidden: int) -> int:
+    """Host mirror of pna_edge_mlp_bf16's LDS check: one tower's hidden weights (rows padded by 16 elements) and the four 16-edge tiles
+    of a workgroup; the entry point refuses more than 160 KiB."""
+    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
+    Kp = r(r(F, 8), 32)
+    return 2 * (n_hidden * r(F, 16) * (Kp + 16) + 64 * (Kp + 8))
+
+
+def edge_mlp_image_bf16(weights: Sequence[Sequence[torch.Tensor]], biases: Sequence[Sequence[torch.Tensor]]):
+    """(w_img, bias) of pna_edge_mlp_bf16 from weights[t][l] (F, F) and biases[t][l] (F), the hidden Linear l of tower t:
+    bf16 [T][L-1][round16(F)][round32(round8(F))] with zeros elsewhere, and bf16 [T][L-1][F]."""
+    T, nh, F = len(weights), len(weights[0]), weights[0][0].shape[0]
+    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
+    img = torch.zeros(T, nh, r(F, 16), r(r(F, 8), 32), dtype=torch.bfloat16, device=weights[0][0].device)
+    for t in range(T):
+        for l in range(nh):
+            if tuple(weights[t][l].shape) != (F, F) or biases[t][l].numel() != F:
+                raise ValueError("pna_edge_mlp_bf16: every hidden layer is a square Linear of one width with a bias")
+            img[t, l, :F, :F] = weights[t][l]
+    bias = torch.stack([torch.stack([b.reshape(F) for b in bt]) for bt in biases]).to(torch.bfloat16).contiguous()
+    return img, bias
+
+
+def edge_mlp_bf16(col: torch.Tensor, row: torch.Tensor, x_src: torch.Tensor, x_dst: torch.Tensor, *, n_tower: int, F: int,
+                  w_img: torch.Tensor, bias: torch.Tensor, edge_rows: Optional[torch.Tensor] = None,
+                  edge_type: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """bf16 (E, n_tower * round8(F)) messages of a deep pre_nn through pna_edge_mlp_bf16: per CSR edge k = (col[k] -> row[k]) and tower,
+    z_1 = R(relu((x_src[col] + x_dst[row]) + edge row)) and the hidden layers of w_img / bias (edge_mlp_image_bf16) on the bf16 matrix
+    pipe; see include/pna_amd.h.  Tower t lives at columns t round8(F) of every operand; the padding columns of the result are zeros."""
+    E = col.numel()
+    Fp = (F + 7) // 8 * 8
+    W = n_tower * Fp
+    nh = w_img.shape[1]
+    if tuple(w_img.shape) != (n_tower, nh, (F + 15) // 16 * 16, (Fp + 31) // 32 * 32) or not w_img.is_contiguous() or \
+            tuple(bias.shape) != (n_tower, nh, F) or not bias.is_contiguous():
+        raise ValueError(f"pna_edge_mlp_bf16: image {tuple(w_img.shape)} / bias {tuple(bias.shape)} do not fit T={n_tower}, F={F}")
+    if row.numel() != E or x_src.shape[1] < W or x_dst.shape[1] < W:
+        raise ValueError("pna_edge_mlp_bf16: row needs one entry per edge, x_src / x_dst n_tower * round8(F) columns")
+    if out is None:
+        out = torch.empty(E, W, dtype=torch.bfloat16, device=x_src.device)
+    a = _lib.PnaEdgeMlpBf16Args()
+    a.E, a.T, a.F, a.n_hidden = E, n_tower, F, nh
+    a.col, a.row = _lib.dev_ptr(col, torch.int32, "col"), _lib.dev_ptr(row, torch.int32, "row")
+    a.x_src, a.ld_src = _lib.dev_ptr(x_src, torch.bfloat16, "x_src"), _ld(x_src)
+    a.x_dst, a.ld_dst = _lib.dev_ptr(x_dst, torch.bfloat16, "x_dst"), _ld(x_dst)
+    if edge_rows is not None:
+        if edge_rows.shape[1] < W or (edge_type is None and edge_rows.shape[0] != E):
+            raise ValueError(f"edge_rows must be (E or n_types, >= {W}), got {tuple(edge_rows.shape)}")
+        a.edge_rows, a.ld_edge, a.n_edge_rows = _lib.dev_ptr(edge_rows, torch.bfloat16, "edge_rows"), _ld(edge_rows), edge_rows.shape[0]
+        if edge_type is not None:
+            if edge_type.numel() != E:
+                raise ValueError("edge_type must have one entry per edge")
+            a.edge_type = _lib.dev_ptr(edge_type, torch.int32, "edge_type")
+    elif edge_type is not None:
+        raise ValueError("edge_type without edge_rows")
+    a.w_img, a.bias = _lib.dev_ptr(w_img, torch.bfloat16, "w_img"), _lib.dev_ptr(bias, torch.bfloat16, "bias")
+    if out.shape[0] != E or out.shape[1] < W:
+        raise ValueError("out must be (E, >= n_tower * round8(F))")
+    a.out, a.ld_out = _lib.dev_ptr(out, torch.bfloat16, "out"), _ld(out)
+    rc = _lib.lib().pna_edge_mlp_bf16(ctypes.byref(a), _lib.stream_ptr(x_src.device))
+    _lib.check(rc, "pna_edge_mlp_bf16")
     return out

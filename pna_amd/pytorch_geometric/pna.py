@@ -17,6 +17,10 @@ the same `avg_deg` dictionary computed from the degree histogram `deg` (pna.py:8
 `edge_index[0]` = source j, `edge_index[1]` = target i (flow source_to_target).  Nodes without in-edges follow the
 reference's PyG rules (scalers.py:16-19,:26-29; 0 for sum/mean/min/max/var, sqrt(1e-5) for std).  The CSR of an
 `edge_index` tensor is cached on the tensor object.  GPU tensors only.
+
+bf16 inference (`layer.eval().to(torch.bfloat16)`, bf16 `x` / `edge_attr`, no gradient): `_bf16_path` hands the call to
+functional.pyg_conv_bf16 / pyg_simple_bf16 -- the bf16 kernels of the DGL layers with the PyG statistics rules in the device code (no
+`fix_empty_std`, no host synchronisation) and, for pre_layers > 1, pna_edge_mlp_bf16 for the hidden layers per edge.
 """
 from typing import Dict, List, Optional
 
@@ -24,7 +28,7 @@ import torch
 from torch import Tensor
 from torch.nn import Linear, ModuleList, ReLU, Sequential
 
-from .. import functional as PF
+from .. import functional as PF, ops
 from ..graph import Graph
 from .aggregators import AGGREGATORS, _KERNEL_NAME, fix_empty_std
 from .scalers import SCALERS, row_factor
@@ -70,6 +74,31 @@ def _row_factors(graph: Graph, scalers: List[str], avg_deg):
     return [None if s == "identity" else row_factor(s, deg, avg_deg).contiguous() for s in scalers], deg
 
 
+def _bf16_inference(module, x, edge_attr, reads_edges):
+    """The part of the bf16 predicates both layers share (dgl/pna_layer.py::_bf16_towers_path, flat and cheap: it runs on every call):
+    bf16 features on the GPU, every floating-point parameter and buffer bf16, eval mode, no gradient required, and bf16 edge
+    features on the GPU exactly when the layer reads them."""
+    if x.dtype != torch.bfloat16 or module.training or not x.is_cuda:
+        return False
+    params = []
+    for m in module.modules():
+        for t in m._parameters.values():
+            if t is not None:
+                if t.dtype != torch.bfloat16 and t.is_floating_point():
+                    return False
+                params.append(t)
+        for t in m._buffers.values():
+            if t is not None and t.dtype != torch.bfloat16 and t.is_floating_point():
+                return False
+    if reads_edges != (edge_attr is not None):
+        return False
+    if reads_edges and (edge_attr.dtype != torch.bfloat16 or not edge_attr.is_cuda):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or (reads_edges and edge_attr.requires_grad) or any(p.requires_grad for p in params)):
+        return False
+    return True
+
+
 class PNAConv(PF.DropsCachesOnConversion, torch.nn.Module):
     """The full layer (pre_nns on [x_i, x_j, edge], towers, post_nns on [x, aggregate], final mixing Linear)."""
 
@@ -105,9 +134,25 @@ class PNAConv(PF.DropsCachesOnConversion, torch.nn.Module):
             if isinstance(m, Linear):
                 m.reset_parameters()
 
+    def _bf16_path(self, x, edge_attr=None):
+        """Whether a call is served by the bf16 inference kernels (functional.pyg_conv_bf16): _bf16_inference and what the kernels
+        hold -- at most 128 output columns, towers * round8(F_in) <= 512 (one gathered row), at most 3 scalers, and a pre_nn that
+        is one Linear or whose hidden layers fit pna_edge_mlp_bf16 (F_in <= 128, one tower's hidden weights in LDS).  Every other
+        call takes the fp32 code and fails there as before."""
+        if not _bf16_inference(self, x, edge_attr, self.edge_dim is not None):
+            return False
+        if self.out_channels > 128 or self.towers * ((self.F_in + 7) // 8 * 8) > 512 or len(self.scaler_names) > 3:
+            return False
+        hidden = len(self.pre_nns[0]) // 2
+        if hidden and (self.F_in > 128 or ops.edge_mlp_bf16_lds_bytes(self.F_in, hidden) > 160 * 1024):
+            return False
+        return True
+
     def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None) -> Tensor:
         V, T, Fi = x.shape[0], self.towers, self.F_in
         graph = _graph_of(edge_index, V)
+        if self._bf16_path(x, edge_attr):
+            return PF.pyg_conv_bf16(self, graph, x, edge_attr)
         csr = graph.csr
         names = [_KERNEL_NAME[a] for a in self.aggregator_names]
         A, S = len(names), len(self.scaler_names)
@@ -180,8 +225,17 @@ class PNAConvSimple(PF.DropsCachesOnConversion, torch.nn.Module):
         out = PF.aggregate(graph, graph.source_features(x), self.F_in, names, row_scales=factors)
         return fix_empty_std(out, names, len(factors), self.F_in, deg, factors)
 
+    def _bf16_path(self, x):
+        """Whether a call is served by the bf16 inference kernels (functional.pyg_simple_bf16): _bf16_inference, at most 128 output
+        columns, F_in <= 512 and at most 3 scalers.  Every other call takes the fp32 code and fails there as before."""
+        if not _bf16_inference(self, x, None, False):
+            return False
+        return self.out_channels <= 128 and (self.F_in + 7) // 8 * 8 <= 512 and len(self.scaler_names) <= 3
+
     def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None) -> Tensor:
         graph = _graph_of(edge_index, x.shape[0])
+        if self._bf16_path(x):
+            return PF.pyg_simple_bf16(self, graph, x)
         names = [_KERNEL_NAME[a] for a in self.aggregator_names]
         agg = PF.aggregate(graph, graph.source_features(x), self.F_in, names)       # identity scaler only
         factors, deg = _row_factors(graph, self.scaler_names, self.avg_deg)
