@@ -33,6 +33,9 @@ extern "C" {
                                   23, additive: + pna_edge_mlp_bf16 / pna_edge_mlp_bf16_args (the hidden layers of a deep pre_nn per edge: bf16
                                   inference of the PyG front end) and PNA_AGG_STD_PYG, which the three bf16 statistics entry points accept
                                   beside PNA_AGG_VAR_RAW; no existing struct changed.
+                                  23, additive: + pna_pack_rows_bf16, pna_gather_rows_bf16 / pna_gather_rows_bf16_args (bf16 inference on the
+                                  shards of a destination-sharded graph: the halo pack on bf16 rows and the row-list, split-table member of
+                                  the bf16 gather family); no existing struct or entry point changed.
                               22: + pna_segreduce_fwd_bf16 / pna_segreduce_bf16_partials_bytes, pna_posttrans_bf16 / pna_posttrans_bf16_tiles
                                   (bf16 inference of PNASimpleLayer; pna_segreduce_bf16_args, pna_posttrans_bf16_args).
                               21: the GUARDED fp16 x 2 contraction of the one-kernel layer (round 6): + pna_fused_degree_args.{w_img_x3,
@@ -1271,6 +1274,69 @@ typedef struct pna_edge_mlp_bf16_args {
 int pna_edge_mlp_bf16(const pna_edge_mlp_bf16_args* args, pna_stream_t stream);
 /* LDS bytes of one workgroup of pna_edge_mlp_bf16 (the formula above); -1 when F or n_hidden is out of range. */
 int64_t pna_edge_mlp_bf16_lds_bytes(int32_t F, int32_t n_hidden);
+
+/* ---- bf16 inference on sharded graphs (ABI 23, additive) -------------------------------------------------------------------------
+ *
+ * pna_pack_rows_bf16 -- replaces the send-side pack of pna_amd/shard.py (pna_pack_rows_f32 on the GPU, Tensor.index_select on the
+ * host) for bf16 rows:   out[i * ldo + f] = x[idx[i] * ldx + f] for f < F,   0 for F <= f < ldo,   i < n.
+ * The send buffer leaves as whole rows of ldo elements with a defined tail (HaloGraph.start_halo sends rows of round8(F) elements:
+ * the receiver gathers them in 16-byte pieces).  16-byte moves when x and out are 16-byte aligned and ldx, ldo are multiples of 8
+ * (nothing beyond the F columns of a source row is read), 2-byte moves otherwise; non-temporal stores.  Strides in ELEMENTS. */
+int pna_pack_rows_bf16(const void* x, int64_t ldx, const int32_t* idx, int64_t n, int32_t F, void* out, int64_t ldo,
+                       pna_stream_t stream);
+
+/* pna_gather_rows_bf16 -- the row-list, split-table member of the bf16 gather family: on a shard it replaces the two-launch split
+ * of pna_amd.functional.aggregate (interior work list while the halo exchange is in flight, boundary rows and hub segments after
+ * it: pna_segreduce_fwd_f32 over HaloGraph.split_work_lists) and the concatenated [local | halo] table that split reads.  Every
+ * operand of pna_gather_bf16_args means what it means there; three additions:
+ *   rows, n_rows   lane group i reduces destination row rows[i] and writes out[rows[i]]; a row that is not listed is not touched
+ *                  (ids outside [0, V) are skipped).  rows NULL = every row of [0, V), n_rows is ignored.
+ *   x_halo, ld_halo, n_local   a source id c < n_local reads x + c * ldx, an id >= n_local reads x_halo + (c - n_local) * ld_halo.
+ *                  x_halo NULL = one table.  16-byte pieces need BOTH tables (and the term operands) 16-byte aligned with
+ *                  pitches that are multiples of 8, and F a multiple of 8 or tails_readable = 1, which covers x_halo too.
+ *   heavy rows     the segment and finalize kernels of the heavy-row schedule run in this call exactly when n_heavy > 0, whatever
+ *                  `rows` lists; listed rows above heavy_threshold are then left to them.  CONTRACT: a call with n_heavy = 0 is
+ *                  given light rows only (a listed hub row would be reduced by one lane group: correct sums in another order
+ *                  than the schedule's).  pna_amd.functional guarantees it: HaloGraph.split_rows() lists no hub row.
+ * For every listed row the bits of out equal those of the whole-V entry points on the concatenated table: pna_gather_bf16 when
+ * dst_term or edge_rows is given, pna_segreduce_fwd_bf16 when neither is (no zero term is added to the gathered rows). */
+typedef struct pna_gather_rows_bf16_args {
+  uint32_t struct_size;    /* sizeof(pna_gather_rows_bf16_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* rowptr;   /* [V+1] */
+  const int32_t* col;      /* [E] source id of each CSR edge, in [0, n_local + halo rows) */
+  int32_t V;
+  int32_t F;
+  const void* x;           /* bf16 (n_local, ldx): the source-side term of the local rows */
+  int64_t ldx;
+  const void* x_halo;      /* bf16 (halo rows, ld_halo), nullable */
+  int64_t ld_halo;
+  const int32_t* rows;     /* [n_rows] destination rows of this call, nullable */
+  int32_t n_rows;
+  int32_t n_local;         /* rows of x (>= 1 with x_halo) */
+  const void* dst_term;    /* bf16 (V, ld_dst), nullable */
+  int64_t ld_dst;
+  const void* edge_rows;   /* bf16 (n_types or E, ld_edge), nullable */
+  int64_t ld_edge;
+  const int32_t* edge_type; /* [E] in CSR order, values in [0, n_edge_rows); NULL = edge_rows has one row per CSR edge */
+  int32_t n_edge_rows;     /* rows of edge_rows */
+  int32_t tails_readable;  /* 1 = columns [F, round8(F)) of every row of x, x_halo, dst_term and edge_rows may be read */
+  int32_t n_aggr;
+  int32_t block_stride;    /* columns between aggregator blocks (>= F); 0 = F */
+  int32_t aggr[PNA_MAX_AGGR]; /* PNA_AGG_MEAN .. PNA_AGG_STD_PYG */
+  void* out;               /* bf16 (V, ldo), 16-byte aligned, ldo a multiple of 8 and >= (n_aggr - 1) * block_stride + F */
+  int64_t ldo;
+  int32_t heavy_threshold; /* the heavy-row schedule of pna_segreduce_bf16_args */
+  int32_t seg_len;
+  int32_t n_heavy;
+  int32_t n_seg;
+  const int32_t* heavy_rows;   /* [n_heavy] */
+  const int32_t* heavy_segptr; /* [n_heavy+1] */
+  const int32_t* seg_heavy;    /* [n_seg] */
+  float* partials;             /* pna_segreduce_bf16_partials_bytes(n_seg, F) bytes */
+} pna_gather_rows_bf16_args;
+
+int pna_gather_rows_bf16(const pna_gather_rows_bf16_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -253,6 +253,22 @@ class PnaGatherBf16Args(_Args):
     ]
 
 
+class PnaGatherRowsBf16Args(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("V", ctypes.c_int32), ("F", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("x_halo", ctypes.c_void_p), ("ld_halo", ctypes.c_int64),
+        ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int32), ("n_local", ctypes.c_int32),
+        ("dst_term", ctypes.c_void_p), ("ld_dst", ctypes.c_int64),
+        ("edge_rows", ctypes.c_void_p), ("ld_edge", ctypes.c_int64), ("edge_type", ctypes.c_void_p),
+        ("n_edge_rows", ctypes.c_int32), ("tails_readable", ctypes.c_int32), ("n_aggr", ctypes.c_int32), ("block_stride", ctypes.c_int32),
+        ("aggr", ctypes.c_int32 * PNA_MAX_AGGR),
+        ("out", ctypes.c_void_p), ("ldo", ctypes.c_int64),
+        ("heavy_threshold", ctypes.c_int32), ("seg_len", ctypes.c_int32), ("n_heavy", ctypes.c_int32), ("n_seg", ctypes.c_int32),
+        ("heavy_rows", ctypes.c_void_p), ("heavy_segptr", ctypes.c_void_p), ("seg_heavy", ctypes.c_void_p), ("partials", ctypes.c_void_p),
+    ]
+
+
 class PnaContractBf16Args(_Args):
     _fields_ = [
         ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
@@ -431,6 +447,11 @@ def lib():
         L.pna_edge_mlp_bf16.restype = ctypes.c_int
         L.pna_edge_mlp_bf16_lds_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
         L.pna_edge_mlp_bf16_lds_bytes.restype = ctypes.c_int64
+        L.pna_pack_rows_bf16.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        L.pna_pack_rows_bf16.restype = ctypes.c_int
+        L.pna_gather_rows_bf16.argtypes = [ctypes.POINTER(PnaGatherRowsBf16Args), ctypes.c_void_p]
+        L.pna_gather_rows_bf16.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

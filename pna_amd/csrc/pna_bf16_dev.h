@@ -1,4 +1,4 @@
-// pna_bf16_dev.h -- device helpers shared by the bf16 inference kernels (pna_bf16_gather.hip, pna_bf16_contract.hip,
+// pna_bf16_dev.h -- device helpers shared by the bf16 inference kernels (pna_bf16_gather.hip, pna_bf16_shard.hip, pna_bf16_contract.hip,
 // pna_bf16_small.hip, pna_bf16_edge_mlp.hip): the bf16 <-> fp32 conversions, the per-lane statistics of a gather (8 features per lane, fp32), the ONE fold
 // over a row's in-edges (fold_edges) and the ONE finalisation of a row's statistics (finish_stats).
 #pragma once
@@ -78,12 +78,27 @@ struct MsgTerm {
   const u16* dst; const u16* er; int64_t lde; const int32_t* et; int n_er;
 };
 
+// The two source tables of a split gather (fold_edges<..., SPLIT = true>): a source id c < n_local reads row c of the first table,
+// any other id row c - n_local of the second.  far: this lane's 8 columns of the second table's row 0 moved back by n_local rows, so
+// that both tables are addressed by the id itself; pitches in BYTES as 32-bit values (base + id * pitch is one 32 x 32 -> 64 bit
+// multiply-add per gathered edge behind the compare and the select of base and pitch).
+struct HaloTab {
+  const char* far; unsigned pitch_far, pitch_near; int n_local;
+};
+
 // The in-edges [beg, end) of one destination row folded in CSR order for the 8 features at xb of every source row (nf of them
 // exist); four edges in flight per lane.  V8 / VT: 16-byte loads of the source rows / of the term rows.  MSG = false: no term is
 // read or added (not even a zero: -0.0 + 0.0 is +0.0, and max / min would see it).  TYPED: edge rows always come from the type table.
-template <bool V8, bool VT, bool MSG, bool TYPED = false>
+// SPLIT: the source rows live in two tables (HaloTab); one compare and a select of base and pitch per gathered edge.
+template <bool V8, bool VT, bool MSG, bool TYPED = false, bool SPLIT = false>
 __device__ __forceinline__ void fold_edges(const int32_t* col, const u16* xb, int64_t ldx, int beg, int end, int nf, const MsgTerm& t,
-                                           Acc& c) {
+                                           Acc& c, const HaloTab& hb = HaloTab{}) {
+  auto src_row = [&](int id) __attribute__((always_inline)) {
+    if (!SPLIT) return xb + (size_t)id * ldx;
+    const bool far = id >= hb.n_local;
+    const char* base = far ? hb.far : reinterpret_cast<const char*>(xb);
+    return reinterpret_cast<const u16*>(base + (uint64_t)(unsigned)id * (far ? hb.pitch_far : hb.pitch_near));
+  };
   float d[8];
   if (MSG) {
     if (t.dst) {
@@ -107,7 +122,7 @@ __device__ __forceinline__ void fold_edges(const int32_t* col, const u16* xb, in
     for (int u = 0; u < 4; ++u) id[u] = col[k + u];
     float v[4][8];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) load8<V8>(xb + (size_t)id[u] * ldx, nf, v[u]);
+    for (int u = 0; u < 4; ++u) load8<V8>(src_row(id[u]), nf, v[u]);
     if (MSG) {
       if (eb) {
         float w[4][8];
@@ -129,7 +144,7 @@ __device__ __forceinline__ void fold_edges(const int32_t* col, const u16* xb, in
   }
   for (; k < end; ++k) {
     float v[8];
-    load8<V8>(xb + (size_t)col[k] * ldx, nf, v);
+    load8<V8>(src_row(col[k]), nf, v);
     if (MSG) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = v[j] + d[j];

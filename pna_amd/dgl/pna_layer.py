@@ -28,6 +28,7 @@ from .. import functional as PF
 from .. import ops
 from ..graph import Graph
 from ..layers import MLP, FCLayer
+from ..shard import HaloGraph
 from .aggregators import AGGREGATORS
 from .scalers import SCALERS
 
@@ -85,11 +86,11 @@ def _row_scales(graph, scalers, avg_d, device):
 def _bf16_towers_path(module, towers, mix, graph, h, e, out_dim):
     """Whether a PNATower / PNALayer call is served by the bf16 inference kernels (functional.towers_bf16 / tower_layer_bf16): the
     predicate of PNASimpleLayer._bf16_path -- bf16 features, every floating-point parameter and buffer bf16, inference (eval mode, no
-    gradient required), features on the GPU, exactly a Graph -- and: a 1-layer (affine) pretrans, bf16 edge features on the GPU
+    gradient required), features on the GPU, exactly a Graph or a HaloGraph (a shard: DESIGN.md 4.15) -- and: a 1-layer (affine) pretrans, bf16 edge features on the GPU
     when the towers read them, at most 128 output columns, aggregators and scalers the kernels know (mean / sum / max / min / std /
     var, at most 3 scalers) and a mixing network that is Linear + (Leaky)ReLU.  Every other call takes the fp32 code and fails
     there as before.  (A stream capture in progress is served: functional.towers_bf16 keeps host synchronisation out of it.)"""
-    if h.dtype != torch.bfloat16 or module.training or not h.is_cuda or type(graph) is not Graph:
+    if h.dtype != torch.bfloat16 or module.training or not h.is_cuda or type(graph) not in (Graph, HaloGraph):
         return False
     params = []                                            # (a flat walk: this predicate runs on every call of a 0.1 ms layer)
     for m in module.modules():
@@ -500,9 +501,9 @@ class PNASimpleLayer(PF.DropsCachesOnConversion, nn.Module):
 
     def _bf16_path(self, graph, h):
         """Whether this call is served by the bf16 inference kernels (functional.simple_layer_bf16): bf16 features and every
-        floating-point parameter and buffer bf16, inference (eval mode, no gradient required), features on the GPU and a whole
-        Graph.  Every other call -- fp32, bf16 training, sharded graphs -- takes the fp32 code below."""
-        if h.dtype != torch.bfloat16 or self.training or not h.is_cuda or type(graph) is not Graph:
+        floating-point parameter and buffer bf16, inference (eval mode, no gradient required), features on the GPU and exactly a
+        Graph or a HaloGraph (a shard of shard_graph).  Every other call -- fp32, bf16 training -- takes the fp32 code below."""
+        if h.dtype != torch.bfloat16 or self.training or not h.is_cuda or type(graph) not in (Graph, HaloGraph):
             return False
         if any(t.dtype != torch.bfloat16 for t in list(self.parameters()) + list(self.buffers()) if t.is_floating_point()):
             return False

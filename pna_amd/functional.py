@@ -8,6 +8,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, degree_groups as DG, ops
+from .shard import HaloGraph
 from ._cache import DropsCachesOnConversion, drop_weight_caches, memo, tensor_key  # noqa: F401  (PF.drop_weight_caches, PF.DropsCachesOnConversion)
 
 
@@ -1124,7 +1125,6 @@ def simple_layer_degree_grouped(layer, graph, h):
     # pays depends on how many rows the overlap covers: on a graph without locality (the benchmark graph: 1 % interior rows) the
     # overlap hides next to nothing and the one-kernel layer saves a third of the compute, so: exchange, then ONE kernel over the
     # extended table (features in the shard's resident table at a 16-byte aligned pitch); with many interior rows, the overlap.
-    from .shard import HaloGraph
     two = DG.two_kernel_applies(layer.out_dim, len(layer.scalers), aggs)
     if (isinstance(graph, HaloGraph) and DG.FUSED and graph._resident(h) and graph._pending is None
             and (graph.interior_fraction() < DG.FUSED_HALO_MAX_INTERIOR or not two)):
@@ -1287,6 +1287,31 @@ class SimpleLayerRows:
                           col_scale=cs, col_shift=ct, relu=True, residual=x[r0:r1] if layer.residual else None)
 
 
+def _shard_gather_bf16(graph, x, F, aggregators, bs, **terms):
+    """The bf16 aggregate of a shard's local rows from the local source rows x (n_local, >= F; any pitch) and the halo rows of the
+    peers: HaloGraph.start_halo posts the exchange of x's rows, pna_gather_rows_bf16 reduces the interior rows (local sources only,
+    no hub) while it is in flight and, after finish_exchange(), the boundary rows and the hub segments into the same aggregate,
+    reading the halo rows from the receive buffer (no concatenated table).  `terms`: dst_term / edge_rows / edge_type of
+    ops.gather_rows_bf16.  Every row is reduced by one lane group (or the heavy schedule) in its edge order: the bits of the
+    unsharded ops.segreduce_bf16 / ops.gather_bf16."""
+    csr, n = graph.csr, graph.num_nodes
+    A = len(aggregators)
+    width = A * bs if bs % 8 == 0 else (A - 1) * bs + F
+    agg = torch.empty(n, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=x.device)[:, :width]
+    interior, boundary = graph.split_rows()
+    halo = graph.start_halo(x, F)
+    if not graph.any_exchange or graph.n_halo == 0:
+        halo = None                               # no rank exchanges, or this rank reads local rows only
+    common = dict(block_stride=bs, out=agg, **terms)
+    if interior.numel():
+        ops.gather_rows_bf16(csr.rowptr, csr.col, x, F, aggregators, rows=interior, **common)
+    graph.finish_exchange()
+    # (run also with an empty boundary list: the hub rows belong to this call)
+    ops.gather_rows_bf16(csr.rowptr, csr.col, x, F, aggregators, rows=boundary, x_halo=halo, n_local=n,
+                         heavy=graph.heavy_schedule(), workspace=graph.workspace, **common)
+    return agg
+
+
 def simple_layer_bf16(layer, graph, h):
     """PNASimpleLayer.forward (models/dgl/pna_layer.py:197-216) in inference on bf16 features and parameters: the bf16 aggregate of
     pna_segreduce_fwd_bf16 (blocks round8(F) columns apart, fp32 statistics), then pna_posttrans_bf16 with the degree scalers,
@@ -1301,7 +1326,8 @@ def simple_layer_bf16(layer, graph, h):
     A = len(layer.aggregators)
     Fb = (F + 7) // 8 * 8
     csr = graph.csr
-    if (not layer.residual or F == layer.out_dim) and bf16_small_applies(
+    sharded = isinstance(graph, HaloGraph)
+    if not sharded and (not layer.residual or F == layer.out_dim) and bf16_small_applies(
             graph, h.shape[0], T=1, Fi=F, Fo=layer.out_dim, A=A, divide_input=False, posttrans_affine=layer.posttrans.is_affine,
             no_self_panel=True):
         im = _small_simple_images_bf16(layer)
@@ -1309,8 +1335,11 @@ def simple_layer_bf16(layer, graph, h):
                                     aggregators=layer.aggregators, row_scales=_row_scales(graph, layer.scalers, layer.avg_d, h.device),
                                     post_img=im["post"], post_bias=im["post_bias"], col_scale=im["cs"], col_shift=im["ct"], slope=0.0,
                                     residual=h if layer.residual else None, no_self_panel=True)
-    agg = ops.segreduce_bf16(csr.rowptr, csr.col, h, F, layer.aggregators, block_stride=Fb, heavy=graph.heavy_schedule(),
-                             workspace=graph.workspace)
+    if sharded:
+        agg = _shard_gather_bf16(graph, h, F, layer.aggregators, Fb)
+    else:
+        agg = ops.segreduce_bf16(csr.rowptr, csr.col, h, F, layer.aggregators, block_stride=Fb, heavy=graph.heavy_schedule(),
+                                 workspace=graph.workspace)
     scales = _row_scales(graph, layer.scalers, layer.avg_d, h.device)
     lin = layer.posttrans.fully_connected[0].linear
     w_img = ops.pack_posttrans_weight_bf16(lin.weight, len(scales), A, F, Fb)
@@ -1567,7 +1596,8 @@ def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
         raise ValueError(f"expected features of shape (V, {Kin}), got {tuple(h.shape)}")
     if h.stride(-1) != 1:
         h = h.contiguous()
-    out = _towers_small_bf16(towers, None, graph, h, e, snorm_n, divide_input, False)
+    sharded = isinstance(graph, HaloGraph)
+    out = None if sharded else _towers_small_bf16(towers, None, graph, h, e, snorm_n, divide_input, False)
     if out is not None:
         return out
     im = _tower_images_bf16(towers, divide_input)
@@ -1585,9 +1615,13 @@ def towers_bf16(towers, graph, h, e, snorm_n, divide_input):
         else:
             ef = e[csr.eid.long()]                       # per-edge features in CSR (dst-sorted) order
         edge_rows = ops.contract_bf16(ef.contiguous(), ed, im["edge"], P)
-    agg = ops.gather_bf16(csr.rowptr, csr.col, x_cat[:, :T * Fi], T * Fi, t0.aggregators, dst_term=x_cat[:, P:P + T * Fi],
-                          edge_rows=edge_rows, edge_type=edge_type, block_stride=P, heavy=graph.heavy_schedule(),
-                          workspace=graph.workspace)
+    if sharded:                                          # the halo exchanges PROJECTED rows, as the fp32 route does
+        agg = _shard_gather_bf16(graph, x_cat[:, :P], T * Fi, t0.aggregators, P, dst_term=x_cat[:, P:P + T * Fi],
+                                 edge_rows=edge_rows, edge_type=edge_type)
+    else:
+        agg = ops.gather_bf16(csr.rowptr, csr.col, x_cat[:, :T * Fi], T * Fi, t0.aggregators, dst_term=x_cat[:, P:P + T * Fi],
+                              edge_rows=edge_rows, edge_type=edge_type, block_stride=P, heavy=graph.heavy_schedule(),
+                              workspace=graph.workspace)
     scales = _row_scales(graph, t0.scalers, t0.avg_d, h.device)
     scales = [scales[s] for s in im["perm"]]
     A = len(t0.aggregators)
@@ -1609,7 +1643,7 @@ def tower_layer_bf16(layer, graph, h, e, snorm_n):
     Kin = len(towers) * towers[0].in_dim if layer.divide_input else towers[0].in_dim
     if h.dim() == 2 and h.shape[1] == Kin:
         hs = h if h.stride(-1) == 1 else h.contiguous()
-        out = _towers_small_bf16(towers, mix, graph, hs, e, snorm_n, layer.divide_input, layer.residual)
+        out = None if isinstance(graph, HaloGraph) else _towers_small_bf16(towers, mix, graph, hs, e, snorm_n, layer.divide_input, layer.residual)
         if out is not None:
             return out
     h_cat = towers_bf16(towers, graph, h, e, snorm_n, layer.divide_input)

@@ -405,9 +405,23 @@ def fused_simple(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: in
 
 
 def pack_rows(x: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[i] = x[idx[i]] for fp32 rows of any 4-byte aligned pitch (pna_pack_rows_f32): the send-side packing of the halo
-    all-to-all (pna_amd/shard.py).  idx: int32 [n]."""
+    """out[i] = x[idx[i]]: the send-side packing of the halo all-to-all (pna_amd/shard.py).  idx: int32 [n].
+    fp32 rows of any 4-byte aligned pitch: pna_pack_rows_f32.
+    bf16 rows of any pitch: pna_pack_rows_bf16, which also writes the columns behind x's of every packed row as zeros -- without
+    `out` the result is the (n, F) view of a buffer of pitch round8(F); a given `out` (n, W >= F) is filled whole and returned."""
     n, F = idx.numel(), x.shape[1]
+    if x.dtype == torch.bfloat16:
+        if out is None:
+            out = torch.empty(n, (F + 7) // 8 * 8, dtype=torch.bfloat16, device=x.device)
+            res = out[:, :F]
+        else:
+            if out.dim() != 2 or out.shape[0] != n or out.shape[1] < F or (n > 1 and out.stride(0) != out.shape[1]):
+                raise ValueError(f"pack_rows: bf16 `out` must be whole rows ({n}, >= {F}), got {tuple(out.shape)} at pitch {out.stride(0)}")
+            res = out
+        rc = _lib.lib().pna_pack_rows_bf16(_lib.dev_ptr(x, torch.bfloat16, "x"), _ld(x), _lib.dev_ptr(idx, torch.int32, "idx"), n, F,
+                                           _lib.dev_ptr(out, torch.bfloat16, "out"), out.shape[1], _lib.stream_ptr(x.device))
+        _lib.check(rc, "pna_pack_rows_bf16")
+        return res
     if out is None:
         out = torch.empty(n, F, dtype=torch.float32, device=x.device)
     rc = _lib.lib().pna_pack_rows_f32(_lib.dev_ptr(x, torch.float32, "x"), _ld(x), _lib.dev_ptr(idx, torch.int32, "idx"), n, F,
@@ -728,6 +742,30 @@ def posttrans_bf16(agg: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_s
 
 
 # ---- bf16 inference of PNALayer / PNATower (pna_bf16_gather.hip, pna_bf16_contract.hip) ------------------------------------------
+def _fill_gather_terms(a, V, E, x, F, dst_term, edge_rows, edge_type):
+    """The message terms of pna_gather_bf16_args / pna_gather_rows_bf16_args (dst_term, edge_rows, edge_type); returns whether the
+    columns [F, round8(F)) of every row of x and the terms may be read."""
+    tails = _tail_readable(x, F)
+    if dst_term is not None:
+        if dst_term.shape[0] != V or dst_term.shape[1] < F:
+            raise ValueError(f"dst_term must be (V, >= {F}), got {tuple(dst_term.shape)}")
+        a.dst_term, a.ld_dst = _lib.dev_ptr(dst_term, torch.bfloat16, "dst_term"), _ld(dst_term)
+        tails = tails and _tail_readable(dst_term, F)
+    if edge_rows is not None:
+        if edge_rows.shape[1] < F or (edge_type is None and edge_rows.shape[0] != E):
+            raise ValueError(f"edge_rows must be (E or n_types, >= {F}), got {tuple(edge_rows.shape)}")
+        a.edge_rows, a.ld_edge = _lib.dev_ptr(edge_rows, torch.bfloat16, "edge_rows"), _ld(edge_rows)
+        a.n_edge_rows = edge_rows.shape[0]
+        tails = tails and _tail_readable(edge_rows, F)
+        if edge_type is not None:
+            if edge_type.numel() != E:
+                raise ValueError("edge_type must have one entry per edge")
+            a.edge_type = _lib.dev_ptr(edge_type, torch.int32, "edge_type")
+    elif edge_type is not None:
+        raise ValueError("edge_type without edge_rows")
+    return tails
+
+
 def gather_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
                 dst_term: Optional[torch.Tensor] = None, edge_rows: Optional[torch.Tensor] = None,
                 edge_type: Optional[torch.Tensor] = None, block_stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
@@ -744,26 +782,41 @@ def gather_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int
         width = A * bs if bs % 8 == 0 else (A - 1) * bs + F
         out = torch.empty(V, (width + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)[:, :width]
     a = _lib.PnaGatherBf16Args()
-    tails = _tail_readable(x, F)
-    if dst_term is not None:
-        if dst_term.shape[0] != V or dst_term.shape[1] < F:
-            raise ValueError(f"dst_term must be (V, >= {F}), got {tuple(dst_term.shape)}")
-        a.dst_term, a.ld_dst = _lib.dev_ptr(dst_term, torch.bfloat16, "dst_term"), _ld(dst_term)
-        tails = tails and _tail_readable(dst_term, F)
-    if edge_rows is not None:
-        if edge_rows.shape[1] < F or (edge_type is None and edge_rows.shape[0] != col.numel()):
-            raise ValueError(f"edge_rows must be (E or n_types, >= {F}), got {tuple(edge_rows.shape)}")
-        a.edge_rows, a.ld_edge = _lib.dev_ptr(edge_rows, torch.bfloat16, "edge_rows"), _ld(edge_rows)
-        a.n_edge_rows = edge_rows.shape[0]
-        tails = tails and _tail_readable(edge_rows, F)
-        if edge_type is not None:
-            if edge_type.numel() != col.numel():
-                raise ValueError("edge_type must have one entry per edge")
-            a.edge_type = _lib.dev_ptr(edge_type, torch.int32, "edge_type")
-    elif edge_type is not None:
-        raise ValueError("edge_type without edge_rows")
-    a.tails_readable = int(tails)
+    a.tails_readable = int(_fill_gather_terms(a, V, col.numel(), x, F, dst_term, edge_rows, edge_type))
     return _run_gather_bf16(a, "pna_gather_bf16", rowptr, col, x, F, aggregators, out, bs, heavy, workspace)
+
+
+# ---- bf16 inference on a shard (pna_bf16_shard.hip) ------------------------------------------------------------------------------------
+def gather_rows_bf16(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, F: int, aggregators: Sequence[str], *,
+                     rows: Optional[torch.Tensor] = None, x_halo: Optional[torch.Tensor] = None, n_local: Optional[int] = None,
+                     dst_term: Optional[torch.Tensor] = None, edge_rows: Optional[torch.Tensor] = None,
+                     edge_type: Optional[torch.Tensor] = None, block_stride: Optional[int] = None, out: torch.Tensor,
+                     heavy: Optional[HeavySchedule] = None, workspace=None):
+    """gather_bf16 (segreduce_bf16 when neither term is given) for the destination rows listed in `rows` (int32; None: all of them)
+    into `out`, whose other rows are not touched, through pna_gather_rows_bf16.  Source ids below n_local read x, the others row
+    id - n_local of x_halo (any pitch of its own; None: one table).  The heavy-row schedule runs in the call that is given `heavy`;
+    a call without it must list light rows only.  `out`: the layout gather_bf16 returns."""
+    V = rowptr.numel() - 1
+    bs = F if block_stride is None else int(block_stride)
+    a = _lib.PnaGatherRowsBf16Args()
+    tails = _fill_gather_terms(a, V, col.numel(), x, F, dst_term, edge_rows, edge_type)
+    if x_halo is not None:
+        if n_local is None:
+            raise ValueError("x_halo needs n_local, the number of rows of x")
+        if x_halo.dim() != 2 or x_halo.shape[1] < F:
+            raise ValueError(f"x_halo must be (halo rows, >= {F}), got {tuple(x_halo.shape)}")
+        if x_halo.shape[0] > 0:
+            a.x_halo, a.ld_halo, a.n_local = _lib.dev_ptr(x_halo, torch.bfloat16, "x_halo"), _ld(x_halo), int(n_local)
+            tails = tails and _tail_readable(x_halo, F)
+    keep = None
+    if rows is not None:
+        if rows.numel() == 0 and (heavy is None or heavy.n_heavy == 0):
+            return out
+        # (an empty tensor has no address: NULL would list every row)
+        keep = rows if rows.numel() else torch.zeros(1, dtype=torch.int32, device=x.device)
+        a.rows, a.n_rows = _lib.dev_ptr(keep, torch.int32, "rows"), rows.numel()
+    a.tails_readable = int(tails)
+    return _run_gather_bf16(a, "pna_gather_rows_bf16", rowptr, col, x, F, aggregators, out, bs, heavy, workspace)
 
 
 def contract_image_bf16(blocks: torch.Tensor):

@@ -10,7 +10,8 @@ CPU for the tests):
   * the only cross-GPU dependency is reading source rows owned by a peer.  Per peer the sorted,
     de-duplicated list of referenced rows (the halo) is computed once per graph; source ids are
     remapped to [local rows | halo rows of peer 0 | halo rows of peer 1 | ...];
-  * per layer: pack the rows each peer asked for (pna_pack_rows_f32), ONE all_to_all_single with
+  * per layer: pack the rows each peer asked for (pna_pack_rows_f32; pna_pack_rows_bf16 in bf16 inference, where the halo rows are
+    received into a buffer of their own: HaloGraph.start_halo), ONE all_to_all_single with
     per-peer split sizes (direct point-to-point transfers over xGMI -- every peer link is used
     concurrently; a ring would be bound by a single 153 GB/s link), then the ordinary fused
     segment-reduce over the extended feature table -- the rows that only read local sources are
@@ -110,6 +111,8 @@ class HaloGraph(Graph):
         self._pending = None                      # the in-flight exchange started by source_features(defer=True)
         self._split = None                        # (interior mask, interior items, boundary items)
         self._interior_fraction = None
+        self._rows = None                         # int32 (interior rows, boundary light rows) of split_rows()
+        self._halo_bf16 = {}                      # (pitch, device) -> the bf16 receive buffer of start_halo()
 
     def to(self, device):
         g = HaloGraph(self.src.to(device), self.dst.to(device), self.num_nodes, self.n_halo, self.send_idx.to(device),
@@ -144,6 +147,18 @@ class HaloGraph(Graph):
                            self.work_items_subset(~interior, include_heavy=True))
         return self._split
 
+    def split_rows(self):
+        """int32 (interior rows, boundary light rows), ascending, from the mask of split_work_lists(): interior = no remote source and
+        in-degree <= the heavy threshold; boundary light = the other rows up to that degree.  With the rows of the heavy schedule
+        they cover every local row exactly once (the row lists of ops.gather_rows_bf16: neither holds a hub)."""
+        if self._rows is None:
+            interior = self.interior_mask()
+            hs = self.heavy_schedule()
+            deg = self.csr.rowptr[1:] - self.csr.rowptr[:-1]
+            light = deg <= hs.threshold if hs.threshold > 0 else torch.ones_like(interior)
+            self._rows = (torch.nonzero(interior).flatten().to(torch.int32), torch.nonzero(light & ~interior).flatten().to(torch.int32))
+        return self._rows
+
     # -- feature tables ---------------------------------------------------------------------------------
     def alloc_features(self, F: int, pitch: Optional[int] = None, device=None) -> torch.Tensor:
         """A resident extended table [local | halo] of row pitch `pitch` floats (default F: dense rows, so that exactly F
@@ -177,6 +192,36 @@ class HaloGraph(Graph):
             work, keep = self._pending
             work.wait()
             self._pending = None
+
+    def start_halo(self, t: torch.Tensor, width: int) -> torch.Tensor:
+        """The exchange of bf16 rows, started and not waited for: packs columns [0, width) of the rows of the local bf16 tensor `t`
+        (n_local rows of any pitch) that the peers asked for and posts ONE async all_to_all_single into the (n_halo, round8(width))
+        buffer kept on the graph, which is returned; finish_exchange() waits for it.  A halo row travels at round8(width) elements
+        with zeros behind column `width`, so that the receiver gathers it in 16-byte pieces.  Every rank of a group
+        with any_exchange enters the collective, also one without a halo of its own."""
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[0] != self.num_nodes or t.shape[1] < width:
+            raise ValueError(f"start_halo: expected bf16 ({self.num_nodes}, >= {width}), got {t.dtype} {tuple(t.shape)}")
+        self.finish_exchange()
+        P = (width + 7) // 8 * 8
+        key = (P, t.device)
+        recv = self._halo_bf16.get(key)
+        if recv is None:
+            recv = self._halo_bf16[key] = torch.zeros(self.n_halo, P, dtype=torch.bfloat16, device=t.device)
+        if not self.any_exchange:                 # no rank has a halo: nobody enters the collective
+            return recv
+        n_send = sum(self.send_splits)
+        if t.is_cuda:
+            from . import ops
+            if self._send_idx32 is None or self._send_idx32.device != t.device:
+                self._send_idx32 = self.send_idx.to(device=t.device, dtype=torch.int32)
+            send = torch.empty(n_send, P, dtype=torch.bfloat16, device=t.device)
+            ops.pack_rows(t[:, :width], self._send_idx32, out=send)
+        else:
+            send = t.new_zeros(n_send, P)
+            send[:, :width] = t[:, :width].index_select(0, self.send_idx)
+        work = dist.all_to_all_single(recv, send, self.recv_splits, self.send_splits, group=self.group, async_op=True)
+        self._pending = (work, send)              # `send` must outlive the transfer
+        return recv
 
     def source_features(self, h_local: torch.Tensor, defer: bool = False) -> torch.Tensor:
         """[h_local | halo rows] after one all-to-all; differentiable (the backward is the transposed
