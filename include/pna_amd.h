@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23: + pna_gather_bf16 / pna_contract_bf16 / pna_contract_bf16_tiles (bf16 inference of PNALayer / PNATower and the nets;
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_simple_train_fwd_f32 / pna_simple_train_bwd_f32 / pna_simple_train_workspace_bytes /
+                                  pna_simple_train_args (PNASimpleLayer's TRAINING forward and backward on molecule batches, one call each);
+                                  no existing struct or entry point changed.
+                                  23: + pna_gather_bf16 / pna_contract_bf16 / pna_contract_bf16_tiles (bf16 inference of PNALayer / PNATower and the nets;
                                   pna_gather_bf16_args, pna_contract_bf16_args).
                                   23, additive: + pna_tower_layer_bf16 / pna_tower_layer_bf16_args (the bf16 tower layer of molecule batches
                                   as one call); no existing struct or entry point changed.
@@ -1337,6 +1340,88 @@ typedef struct pna_gather_rows_bf16_args {
 } pna_gather_rows_bf16_args;
 
 int pna_gather_rows_bf16(const pna_gather_rows_bf16_args* args, pna_stream_t stream);
+
+/* ---- PNASimpleLayer TRAINING on molecule batches: the layer's forward and its backward as ONE call each -------------------------
+ * replaces: models/dgl/pna_layer.py:197-213 in train mode -- update_all(message, reduce) with mean | max | min | std and the degree
+ * scalers, the 1-layer posttrans Linear, BatchNorm1d with BATCH statistics, ReLU and the residual -- and what autograd derives from
+ * it in loss.backward() (realworld_benchmark/train/train_HIV_graph_classification.py:4-26).
+ *
+ * Scope (PNA_E_INVALID outside it, pna_simple_train_workspace_bytes returns -1): aggregators mean, max, min, std in that order;
+ * 1 <= n_scaler <= 3; 4 <= F <= 128; 1 <= N <= 128; V >= 2; a residual needs F == N; any in-degree (a row is reduced serially in CSR
+ * order: for in-degrees <= 128 the saved aggregate and arg indices carry pna_segreduce_fwd_f32's bits and tie rule); in-degrees
+ * < 65535 in the backward (16-bit ranks of the pull).  fp32 throughout; the contractions are exact-product fp32 MFMAs
+ * (v_mfma_f32_16x16x4_f32) except the weight gradient, which is pna_posttrans_dw_f32's kernel (bf16x3) where that kernel's shape
+ * limits hold (n_scaler * N <= 240, 4 F + 1 <= 384) and a plain fp32 kernel otherwise.  NO float atomics: every sum has a fixed order, repeated
+ * calls give identical bits.
+ *
+ * pna_simple_train_fwd_f32 (three launches):
+ *   1. per 16 destination rows: gather h[col], a = [mean | max | min | std] (V, 4F) and argmax / argmin (V, F) are stored (the saved
+ *      state), z = b + sum_s row_scale[s][v] (W_s a[v]) from the tile in LDS (the (V, n_scaler 4F) scaled aggregate never exists), z
+ *      stored, the tile's BatchNorm column sums of d = z - z[first row of the tile] and d^2 (fp32) to a workspace slot of its own;
+ *   2. per column: the tiles' sums re-based on z[0, c] and added in tile order in float64 (pna_bn_tail's shifted sums); save_mean,
+ *      save_invstd; running_mean / running_var updated as pna_bn_tail_fwd_f32 documents (unbiased variance, momentum; NULL: not kept);
+ *   3. out = residual + relu((z - mean) (gamma invstd) + beta).
+ * pna_simple_train_bwd_f32 (six launches): column sums of g' = grad_out [pre-activation > 0] and g' xhat per 128 rows (fp32), added in
+ *   float64 in slab order by every workgroup of the rows kernel; per 16 rows gz = gamma invstd (g' - mean g' - xhat mean(g' xhat))
+ *   stored to the workspace, G[v] = sum_s row_scale[s][v] (gz[v] W_s) written as [G_mean | G_std | G_max | G_min] into the packed
+ *   rows of pna_segreduce_bwd_pull_f32 (IN PLACE form); that call's rowprep and pull over the transposed graph (grad_h; the residual's
+ *   grad_out is added in the pull's store); the weight gradient (grad_w (N, n_scaler 4F), grad_b).  grad_gamma = sum g' xhat,
+ *   grad_beta = sum g'.
+ * w is the Linear's weight (N, ldw >= n_scaler 4F), scaler block s at columns [s 4F, (s+1) 4F), read directly (no packed image: an
+ * optimiser changes it every step); w 16-byte aligned, ldw a multiple of 4.  The transposed graph (backward only): col_t / rank_t as in
+ * pna_segreduce_bwd_pull_args, items_t = ONE whole-row record {u, beg, end, -1} per source row (n_items_t == V: no hub segments, so
+ * no atomics).  workspace: pna_simple_train_workspace_bytes(V, E, F, N, n_scaler) bytes, 256-byte aligned, no initialisation; the
+ * backward reads nothing the forward left in it. */
+typedef struct pna_simple_train_args {
+  uint32_t struct_size;    /* sizeof(pna_simple_train_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* rowptr;   /* [V+1] */
+  const int32_t* col;      /* [E] (may be NULL when E == 0) */
+  int32_t V;
+  int32_t E;
+  int32_t F;
+  int32_t N;
+  int32_t n_scaler;
+  int32_t residual;        /* != 0: out = h + ..., grad_h += grad_out (needs F == N) */
+  const float* h;          /* (V, ldh >= F) */
+  int64_t ldh;
+  const float* row_scale[PNA_MAX_SCALER];  /* first n_scaler: [V] or NULL = identity */
+  const float* w;
+  int64_t ldw;
+  const float* bias;       /* [N] or NULL */
+  const float* gamma;      /* [N] or NULL (both) */
+  const float* beta;
+  float eps;
+  float momentum;          /* forward: < 0 or running_mean NULL = running statistics not updated */
+  float* running_mean;     /* [N], nullable (both) */
+  float* running_var;
+  float* a;                /* saved (V, 4F) contiguous: [mean | max | min | std]; forward writes, backward reads */
+  int32_t* argmax;         /* saved (V, F) contiguous */
+  int32_t* argmin;
+  float* z;                /* saved (V, N) contiguous: the Linear's output */
+  float* save_mean;        /* saved [N] */
+  float* save_invstd;      /* saved [N] */
+  float* out;              /* forward (V, ld_out >= N) */
+  int64_t ld_out;
+  const float* grad_out;   /* backward (V, ld_go >= N) */
+  int64_t ld_go;
+  const int32_t* col_t;    /* backward: the transposed graph */
+  const int32_t* rank_t;
+  const int32_t* items_t;
+  int32_t n_items_t;
+  int32_t _pad0;
+  float* grad_h;           /* backward (V, F) contiguous */
+  float* grad_w;           /* backward (N, n_scaler 4F) contiguous */
+  float* grad_b;           /* [N] */
+  float* grad_gamma;       /* [N] */
+  float* grad_beta;        /* [N] */
+  void* workspace;
+  int64_t workspace_bytes;
+} pna_simple_train_args;
+
+int64_t pna_simple_train_workspace_bytes(int64_t V, int64_t E, int32_t F, int32_t N, int32_t n_scaler);
+int pna_simple_train_fwd_f32(const pna_simple_train_args* args, pna_stream_t stream);
+int pna_simple_train_bwd_f32(const pna_simple_train_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -313,6 +313,26 @@ class PnaEdgeMlpBf16Args(_Args):
     ]
 
 
+class PnaSimpleTrainArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("V", ctypes.c_int32), ("E", ctypes.c_int32),
+        ("F", ctypes.c_int32), ("N", ctypes.c_int32), ("n_scaler", ctypes.c_int32), ("residual", ctypes.c_int32),
+        ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64),
+        ("row_scale", ctypes.c_void_p * PNA_MAX_SCALER),
+        ("w", ctypes.c_void_p), ("ldw", ctypes.c_int64), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+        ("eps", ctypes.c_float), ("momentum", ctypes.c_float), ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
+        ("a", ctypes.c_void_p), ("argmax", ctypes.c_void_p), ("argmin", ctypes.c_void_p), ("z", ctypes.c_void_p),
+        ("save_mean", ctypes.c_void_p), ("save_invstd", ctypes.c_void_p),
+        ("out", ctypes.c_void_p), ("ld_out", ctypes.c_int64), ("grad_out", ctypes.c_void_p), ("ld_go", ctypes.c_int64),
+        ("col_t", ctypes.c_void_p), ("rank_t", ctypes.c_void_p), ("items_t", ctypes.c_void_p),
+        ("n_items_t", ctypes.c_int32), ("_pad0", ctypes.c_int32),
+        ("grad_h", ctypes.c_void_p), ("grad_w", ctypes.c_void_p), ("grad_b", ctypes.c_void_p),
+        ("grad_gamma", ctypes.c_void_p), ("grad_beta", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -452,6 +472,11 @@ def lib():
         L.pna_pack_rows_bf16.restype = ctypes.c_int
         L.pna_gather_rows_bf16.argtypes = [ctypes.POINTER(PnaGatherRowsBf16Args), ctypes.c_void_p]
         L.pna_gather_rows_bf16.restype = ctypes.c_int
+        L.pna_simple_train_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        L.pna_simple_train_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_simple_train_fwd_f32, L.pna_simple_train_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaSimpleTrainArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

@@ -686,3 +686,123 @@ class BnTailFn(torch.autograd.Function):
         has_affine = gamma is not None
         return (gy, gwb[0] if has_affine and ctx.needs_input_grad[1] else None, gwb[1] if has_affine and ctx.needs_input_grad[2] else None,
                 go if ctx.has_res else None, None, None, None, None, None)
+
+
+class _SmallTrainPlan:
+    """What one call of SimpleLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays (kept on the graph, like
+    the pull of the generic route keeps them) and the call's workspace -- the graph's reusable scratch (Graph.workspace: allocated once
+    per graph, grown to the widest layer seen; every launch writes what it reads, nothing is carried from the forward to the backward).
+    Nothing here depends on weight values.  One caller at a time per Graph (functional.py's rule for the shared scratch)."""
+
+    def __init__(self, graph, F, N, S, dev):
+        from .graph import Graph
+        csr = graph.csr
+        V, E = graph.num_nodes, int(csr.col.numel())
+        self.V, self.E, self.F, self.N, self.S, self.dev = V, E, F, N, S, dev
+        gT = getattr(graph, "_pna_amd_transposed", None)
+        if gT is None or gT.num_nodes != V:
+            gT = graph._pna_amd_transposed = Graph(csr.row.long(), csr.col.long(), V)     # edge (v -> u): pulls row v into u
+        tcsr = gT.csr
+        rank_t = getattr(gT, "_pna_amd_rank_t", None)
+        if rank_t is None:                                    # position of every transposed edge in its destination's in-edge list
+            rank_t = (tcsr.eid.to(torch.int64) - csr.rowptr.to(torch.int64)[tcsr.col.long()]).to(torch.int32).contiguous()
+            gT._pna_amd_rank_t = rank_t
+        self.col_t, self.rank_t = tcsr.col, rank_t
+        self.items_t = gT.work_items(threshold=1 << 30)       # one whole-row record per source row: no hub segments, no atomics
+        nbytes = _lib.lib().pna_simple_train_workspace_bytes(V, E, F, N, S)
+        if nbytes < 0:
+            raise RuntimeError("SimpleLayerSmallTrainFn: shape outside pna_simple_train_*_f32 (the layer checks it before taking this path)")
+        ws = graph.workspace(nbytes + 256)
+        self.ws = ws[(-ws.data_ptr() // 4) % 64:][:nbytes // 4]                 # 256-byte aligned
+        self.nbytes = nbytes
+
+    def new_saved(self):
+        """The state one forward leaves for its backward -- a (V, 4F) | z (V, N) | save_mean, save_invstd [N] in one buffer, argmax |
+        argmin (V, F) in another.  Per CALL, not per plan: two layers of one shape on one graph are both alive until their backwards."""
+        V, F, N = self.V, self.F, self.N
+        fbuf = torch.empty(V * 4 * F + V * N + 2 * N, dtype=torch.float32, device=self.dev)
+        ibuf = torch.empty(2, V, F, dtype=torch.int32, device=self.dev)
+        return fbuf, ibuf
+
+    def args(self, graph, h, w, bias, bn, scales, residual, saved):
+        csr = graph.csr
+        a = _lib.PnaSimpleTrainArgs()
+        a.rowptr = _lib.dev_ptr(csr.rowptr, torch.int32, "rowptr")
+        a.col = _lib.dev_ptr(csr.col, torch.int32, "col") if self.E else None
+        a.V, a.E, a.F, a.N, a.n_scaler, a.residual = self.V, self.E, self.F, self.N, self.S, int(residual)
+        a.h, a.ldh = _lib.dev_ptr(h, torch.float32, "h"), h.stride(0)
+        for s, rs in enumerate(scales):
+            if rs is not None:
+                a.row_scale[s] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+        a.w, a.ldw = _lib.dev_ptr(w, torch.float32, "weight"), w.stride(0)
+        a.bias = _lib.dev_ptr(bias, torch.float32, "bias")
+        if bn.weight is not None:
+            a.gamma, a.beta = _lib.dev_ptr(bn.weight, torch.float32, "gamma"), _lib.dev_ptr(bn.bias, torch.float32, "beta")
+        a.eps, a.momentum = float(bn.eps), float(bn.momentum)
+        a.running_mean = _lib.dev_ptr(bn.running_mean, torch.float32, "running_mean")
+        a.running_var = _lib.dev_ptr(bn.running_var, torch.float32, "running_var")
+        fbuf, ibuf = saved
+        V, F, N = self.V, self.F, self.N
+        base = fbuf.data_ptr()
+        a.a, a.z = base, base + 4 * V * 4 * F
+        a.save_mean, a.save_invstd = base + 4 * (V * 4 * F + V * N), base + 4 * (V * 4 * F + V * N + N)
+        a.argmax, a.argmin = ibuf.data_ptr(), ibuf.data_ptr() + 4 * V * F
+        a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.nbytes
+        return a
+
+
+class SimpleLayerSmallTrainFn(torch.autograd.Function):
+    """PNASimpleLayer's training forward (gather, scalers, posttrans Linear, batch-statistics BatchNorm, ReLU, residual:
+    models/dgl/pna_layer.py:197-213) on a molecule-sized batch as ONE C call (pna_simple_train_fwd_f32) and its backward as one
+    (pna_simple_train_bwd_f32).  The workspace is the graph's scratch; nothing is cached on weight versions.  The output and the
+    gradients are fresh tensors per call (autograd and the optimiser keep them), and so is the state a forward saves for its backward."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, gamma, beta, layer, graph, scales):
+        bn = layer.batchnorm_h
+        F, N, S = layer.in_dim, layer.out_dim, len(scales)
+        dev = h.device
+        x = h if h.stride(1) == 1 else h.contiguous()
+        w = weight if weight.is_contiguous() else weight.contiguous()
+        plan = _SmallTrainPlan(graph, F, N, S, dev)
+        out = torch.empty(plan.V, N, dtype=torch.float32, device=dev)
+        saved = plan.new_saved()
+        a = plan.args(graph, x, w, bias, bn, scales, layer.residual, saved)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        _lib.check(_lib.lib().pna_simple_train_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_simple_train_fwd_f32")
+        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.state = plan, graph, layer, scales, saved
+        ctx.save_for_backward(x, w, bias, gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, w, bias, gamma, beta = ctx.saved_tensors
+        plan, layer = ctx.plan, ctx.layer
+        F, N, S = plan.F, plan.N, plan.S
+        dev = x.device
+        go = go if go.stride(1) == 1 else go.contiguous()
+        g_h = torch.empty(plan.V, F, dtype=torch.float32, device=dev)
+        g_w = torch.empty(N, S * 4 * F, dtype=torch.float32, device=dev)
+        g_vec = torch.empty(3, N, dtype=torch.float32, device=dev)          # grad_b | grad_gamma | grad_beta
+        a = plan.args(ctx.graph, x, w, bias, layer.batchnorm_h, ctx.scales, layer.residual, ctx.state)
+        a.momentum = -1.0
+        a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
+        a.col_t, a.rank_t = _lib.dev_ptr(plan.col_t, torch.int32, "col_t"), _lib.dev_ptr(plan.rank_t, torch.int32, "rank_t")
+        a.items_t, a.n_items_t = _lib.dev_ptr(plan.items_t, torch.int32, "items_t"), plan.items_t.shape[0]
+        a.grad_h, a.grad_w = _lib.dev_ptr(g_h, torch.float32, "grad_h"), _lib.dev_ptr(g_w, torch.float32, "grad_w")
+        a.grad_b = _lib.dev_ptr(g_vec[0], torch.float32, "grad_b")
+        a.grad_gamma, a.grad_beta = _lib.dev_ptr(g_vec[1], torch.float32, "grad_gamma"), _lib.dev_ptr(g_vec[2], torch.float32, "grad_beta")
+        _lib.check(_lib.lib().pna_simple_train_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_simple_train_bwd_f32")
+        need = ctx.needs_input_grad
+        return (g_h if need[0] else None, g_w if need[1] else None, g_vec[0] if bias is not None and need[2] else None,
+                g_vec[1] if gamma is not None and need[3] else None, g_vec[2] if beta is not None and need[4] else None, None, None, None)
+
+
+def simple_layer_small_train(layer, graph, h, scales):
+    """residual + relu(bn(posttrans(aggregate))) of a training PNASimpleLayer through SimpleLayerSmallTrainFn; num_batches_tracked advances
+    like the module's own forward."""
+    bn = layer.batchnorm_h
+    lin = layer.posttrans.fully_connected[0].linear
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return SimpleLayerSmallTrainFn.apply(h, lin.weight, lin.bias, bn.weight, bn.bias, layer, graph, tuple(scales))

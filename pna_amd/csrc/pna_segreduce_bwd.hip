@@ -441,6 +441,7 @@ struct LArgs {
   const float* table; const float* gmax; const float* gmin; const unsigned short* ranks; const float* x; float* gx;
   long ld_table, ld_g, ld_rank, ldx, ld_gx, ts_g;
   int n_items, F, T, TF, L, G;
+  const float* add; long ld_add;                            // nullable: added to a whole row's result (pna_segreduce_bwd_pull_launch)
 };
 
 __global__ __launch_bounds__(kBlock) void k_bwd_ranks(const int32_t* rowptr, const int32_t* argmax, const int32_t* argmin, long ld_arg, long ts_in,
@@ -516,6 +517,11 @@ __global__ __launch_bounds__(kBlock) void k_bwd_pull(const LArgs a) {
   f4 res;
 #pragma unroll
   for (int q = 0; q < 4; ++q) res[q] = s1[q] + xu[q] * s2[q];
+  if (a.add) {
+    const f4 r = reinterpret_cast<const f4u*>(a.add + (size_t)row * a.ld_add + ot)->v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) res[q] = r[q] + res[q];
+  }
   float* o = a.gx + (size_t)row * a.ld_gx + ot;
   if (slot < 0) {
     reinterpret_cast<f4u*>(o)->v = res;                     // (a row's last, overlapping window recomputes the same values)
@@ -786,6 +792,10 @@ extern "C" int pna_segreduce_bwd_rowprep_f32(const pna_segreduce_bwd_args* p, fl
 }
 
 extern "C" int pna_segreduce_bwd_pull_f32(const pna_segreduce_bwd_pull_args* q, pna_stream_t stream) {
+  return pna_segreduce_bwd_pull_launch(q, nullptr, 0, stream);
+}
+
+int pna_segreduce_bwd_pull_launch(const pna_segreduce_bwd_pull_args* q, const float* add, long ld_add, void* stream) {
   if (!q || !q->base) return pna_set_error(PNA_E_INVALID, "pna_segreduce_bwd_pull_f32: null args");
   if (int rc_ss = pna_check_struct_size("pna_segreduce_bwd_pull_f32", q->struct_size, sizeof(*q))) return rc_ss;
   const pna_segreduce_bwd_args* p = q->base;
@@ -800,6 +810,8 @@ extern "C" int pna_segreduce_bwd_pull_f32(const pna_segreduce_bwd_pull_args* q, 
     return pna_set_error(PNA_E_INVALID, "pna_segreduce_bwd_pull_f32: needs max + min + std/var among aggr[], argmax / argmin, x, grad_x, the rowprep table "
                                         "(ld >= 2 T F), the transposed graph (col_t, rank_t, items_t), a ranks workspace (ld >= 2 T F) and 4 <= F <= 256");
   hipStream_t st = (hipStream_t)stream;
+  if (add && (q->edge_rows || q->n_items_t != p->V || ld_add < TF))
+    return pna_set_error(PNA_E_INVALID, "pna_segreduce_bwd_pull_f32: an added term needs the ranked pull over one whole-row record per source row");
   if (q->edge_rows) {
     // round 6: per-edge rows (see k_bwd_edge_rows): table = the (V, ld_table >= F) rows of R2
     if (T != 1 || p->dst_term || !k.g[PNA_AGG_MEAN] || !k.g[PNA_AGG_STD] || k.g[PNA_AGG_SUM] || k.g[PNA_AGG_VAR] || !p->stdv || !q->pos_t || !q->items ||
@@ -858,7 +870,7 @@ extern "C" int pna_segreduce_bwd_pull_f32(const pna_segreduce_bwd_pull_args* q, 
   a.ranks = q->ranks; a.x = p->x; a.gx = p->grad_x;
   a.ld_table = q->ld_table; a.ld_g = p->ld_g; a.ld_rank = q->ld_rank; a.ldx = p->ldx; a.ld_gx = p->ld_gx; a.ts_g = k.ts_g;
   if (packed) { a.gmax = q->table + 2L * TF; a.gmin = q->table + 3L * TF; a.ld_g = q->ld_table; a.ts_g = F; }
-  a.n_items = q->n_items_t; a.F = F; a.T = T; a.TF = TF;
+  a.n_items = q->n_items_t; a.F = F; a.T = T; a.TF = TF; a.add = add; a.ld_add = ld_add;
   a.L = (F + 3) / 4 > 64 ? 64 : (F + 3) / 4; a.G = 64 / a.L;
   const long groups = (long)kWaves * a.G;
   dim3 grid((unsigned)((q->n_items_t + groups - 1) / groups), (unsigned)T);

@@ -483,6 +483,32 @@ class PNASimpleLayer(PF.DropsCachesOnConversion, nn.Module):
             return False
         return not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters())))
 
+    def _small_train_path(self, graph, h):
+        """Whether this call is served by pna_simple_train_fwd_f32 / _bwd_f32 (autograd.SimpleLayerSmallTrainFn: the training
+        forward and the backward as one C call each): the knob PNA_AMD_SMALL_TRAIN_ROWS is on and covers the batch, the layer and its
+        BatchNorm train, fp32 features on the GPU, a whole graph, a gradient is wanted, and the shape is inside the calls' scope --
+        mean max min std, <= 3 scalers, a 1-layer posttrans, batch_norm, 4 <= in_dim <= 128, out_dim <= 128, at least 2 rows, in-degrees
+        below 65535, a residual only between equal widths, the BatchNorm's running statistics kept the default way."""
+        V = h.shape[0]
+        if not (PF.SMALL_TRAIN_ROWS > 0 and 0 < V <= PF.SMALL_TRAIN_ROWS):
+            return False
+        bn = self.batchnorm_h
+        if not (self.training and self.batch_norm and bn.training and h.is_cuda and h.dtype == torch.float32 and h.dim() == 2
+                and type(graph) is Graph and graph.num_nodes == V and V >= 2 and h.shape[1] == self.in_dim):
+            return False
+        if not (tuple(self.aggregators) == ("mean", "max", "min", "std") and 1 <= len(self.scalers) <= 3 and self.posttrans.is_affine
+                and len(self.posttrans.fully_connected) == 1 and PF.small_train_fits(self.in_dim, self.out_dim)
+                and (not self.residual or self.in_dim == self.out_dim)):
+            return False
+        if not (bn.track_running_stats and bn.momentum is not None and bn.running_mean is not None and (bn.weight is None) == (bn.bias is None)):
+            return False
+        lin = self.posttrans.fully_connected[0].linear
+        if any(t is not None and (t.dtype != torch.float32 or not t.is_cuda) for t in (lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean)):
+            return False
+        if not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return False
+        return graph.csr.max_degree < 65535
+
     def _degree_grouped_path(self, graph, h):
         """Inference on a large whole graph: rows ordered by in-degree, one combined scaler block per degree value
         (pna_amd/degree_groups.py: a third of the posttrans multiply-adds)."""
@@ -524,6 +550,11 @@ class PNASimpleLayer(PF.DropsCachesOnConversion, nn.Module):
                     raise
         lin = self.posttrans.fully_connected[0].linear
         y = None
+        if PF.SMALL_TRAIN_ROWS > 0 and self._small_train_path(graph, h):
+            # training on a molecule batch: the layer's forward as one C call, its backward as another (autograd.SimpleLayerSmallTrainFn)
+            from .. import autograd as AG
+            out = AG.simple_layer_small_train(self, graph, h, _row_scales(graph, self.scalers, self.avg_d, h.device))
+            return F.dropout(out, self.dropout, training=self.training)
         if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters())):
             from .. import autograd as AG
             if AG.simple_layer_plan_applies(self, graph, h):

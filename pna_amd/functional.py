@@ -1184,6 +1184,20 @@ SMALL_SIMPLE_ROWS = int(os.environ.get("PNA_AMD_SMALL_SIMPLE_ROWS", "4096"))   #
 # profiles/r02_small_simple_layer.json)
 
 
+# PNASimpleLayer TRAINING batches up to this many nodes take the one-call route (autograd.SimpleLayerSmallTrainFn:
+# pna_simple_train_fwd_f32 / _bwd_f32).  0 = off (the default: the crossover with the generic route is in DESIGN.md 4.16)
+SMALL_TRAIN_ROWS = int(os.environ.get("PNA_AMD_SMALL_TRAIN_ROWS", "0"))
+
+
+def small_train_fits(F, N):
+    """Mirror of pna_simple_train_fwd_f32's scope and LDS need (one 16 x 4F aggregate tile, one 16 x N output tile, the row scalers):
+    4 <= F <= 128, 1 <= N <= 128 -- at most 42 KB of the CU's 160 KB."""
+    quads = lambda k: (k + 15) // 16   # noqa: E731
+    if not (4 <= F <= 128 and 1 <= N <= 128):
+        return False
+    return 4 * (16 * (quads(4 * F) * 16 + 4) + 16 * (quads(N) * 16 + 1) + 48) <= 160 * 1024
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")
