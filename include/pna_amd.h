@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_simple_train_fwd_f32 / pna_simple_train_bwd_f32 / pna_simple_train_workspace_bytes /
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_train_fwd_f32 / pna_tower_train_bwd_f32 / pna_tower_train_workspace_bytes /
+                                  pna_tower_train_args, PNA_MAX_TOWER (PNALayer's TRAINING forward and backward on molecule batches, one call
+                                  each); no existing struct or entry point changed.
+                                  23, additive: + pna_simple_train_fwd_f32 / pna_simple_train_bwd_f32 / pna_simple_train_workspace_bytes /
                                   pna_simple_train_args (PNASimpleLayer's TRAINING forward and backward on molecule batches, one call each);
                                   no existing struct or entry point changed.
                                   23: + pna_gather_bf16 / pna_contract_bf16 / pna_contract_bf16_tiles (bf16 inference of PNALayer / PNATower and the nets;
@@ -105,6 +108,7 @@ enum {
 };
 #define PNA_MAX_AGGR 8
 #define PNA_MAX_SCALER 8
+#define PNA_MAX_TOWER 8   /* towers of one pna_tower_train_args */
 
 /* Optional launch tuning; all-zero = library defaults. */
 typedef struct pna_tuning {
@@ -1422,6 +1426,110 @@ typedef struct pna_simple_train_args {
 int64_t pna_simple_train_workspace_bytes(int64_t V, int64_t E, int32_t F, int32_t N, int32_t n_scaler);
 int pna_simple_train_fwd_f32(const pna_simple_train_args* args, pna_stream_t stream);
 int pna_simple_train_bwd_f32(const pna_simple_train_args* args, pna_stream_t stream);
+
+/* ---- PNALayer TRAINING on molecule batches: the layer's forward and its backward as ONE call each --------------------------------
+ * replaces: models/dgl/pna_layer.py:55-76, 130-145 in train mode -- per tower the 1-layer pretrans on [h_u | h_v], update_all with
+ * mean | max | min | std and the degree scalers, the 1-layer posttrans on [h | aggregate], graph norm, BatchNorm1d with BATCH
+ * statistics (dropout 0); then the mixing Linear + LeakyReLU and the residual -- and what autograd derives from it in
+ * loss.backward() (realworld_benchmark/train/train_molecules_graph_regression.py:29-32; the ZINC configuration of
+ * realworld_benchmark/README.md:61 without edge features).
+ *
+ * Scope (PNA_E_INVALID outside it, pna_tower_train_workspace_bytes returns -1): 1 <= n_tower <= PNA_MAX_TOWER; aggregators mean, max,
+ * min, std in that order; 1 <= n_scaler <= 3; per-tower widths 4 <= Fi <= 128, n_tower Fi <= 512, 1 <= Fo, n_tower Fo <= 128;
+ * in_dim = n_tower Fi when divide_input, else Fi; V >= 2; a residual needs in_dim == n_tower Fo; no edge features; in-degrees < 65535
+ * in the backward (16-bit ranks of the pull).  Tower t's pretrans weight is (Fi, 2 Fi) = [W_a | W_b], its posttrans weight
+ * (Fo, (1 + 4 n_scaler) Fi) = [W_h | W_s0 | W_s1 | W_s2], w_mix (C, C) with C = n_tower Fo: all CONTIGUOUS, read directly through the
+ * per-tower pointers (no packed image, no alignment beyond 4 bytes: an optimiser changes them every step).  fp32 throughout; the
+ * contractions are exact-product fp32 MFMAs (v_mfma_f32_16x16x4_f32) except the weight gradients, which are pna_posttrans_dw_f32's
+ * kernel (bf16x3) where that kernel's shape limits hold (5 Fi + 1 <= 384, n_scaler Fo <= 240, row_scale[0] == NULL) and a plain
+ * fixed-order fp32 kernel otherwise.  NO float atomics: every sum has a fixed order, repeated calls give identical bits.
+ *
+ * pna_tower_train_fwd_f32 (four launches):
+ *   1. x_cat (V, 2 T Fi) = [x_src | x_dst], x_src,t = W_a,t h_t, x_dst,t = W_b,t h_t + b_t (saved: the backward's pull reads it);
+ *   2. per 16 destination rows, one tower at a time: the messages x_src,t[u] + x_dst,t[v] folded in CSR order (for in-degrees <= 128
+ *      pna_segreduce_fwd_f32's bits and tie rule with dst_term = x_dst) give mean | max | min and argmax / argmin; the std is that of
+ *      x_src,t[u] ALONE (that call's bits without dst_term: a shift does not change a std, and the shifted form loses the variance's
+ *      low digits when x_dst dwarfs the neighbours' spread); a (V, T 4 Fi) = per tower [mean | max | min | std] and argmax / argmin
+ *      (V, T Fi) stored; z_t = (c_t + W_h,t h_t + sum_s row_scale[s][v] (W_s,t a_t[v])) snorm_n[v] from the tile in LDS
+ *      (the scaled (V, 12 Fi) operand never exists); z (V, C) stored; the tile's shifted BatchNorm column sums to a workspace slot;
+ *   3. per column: the tiles' sums re-based on z[0, c] and added in tile order in float64; save_mean, save_invstd; every tower's
+ *      running_mean / running_var updated as pna_bn_tail_fwd_f32 documents (unbiased variance, momentum; NULL or momentum < 0: not kept);
+ *   4. per 16 rows: hcat = (z - mean) (gamma invstd) + beta, p = W_mix hcat + b_mix (saved: the backward's LeakyReLU mask is the
+ *      forward's by construction), out = [h +] leaky(p).
+ * pna_tower_train_bwd_f32 (6 launches + 2 per weight gradient, 3 n_tower + 1 of them): g_p = grad_out leaky'(p), g_hcat = g_p W_mix and
+ *   its column sums per 16-row tile; a finalize launch adds them in float64 (grad_gamma, grad_beta, the two column means); per 16 rows
+ *   gz = snorm_n gamma invstd (g_hcat - mean - xhat mean(g_hcat xhat)) and per tower G = sum_s row_scale[s] (gz_t W_s,t); rowprep and the
+ *   ranked pull of pna_segreduce_bwd_pull_f32 over the transposed graph with n_tower towers and dst_term = x_dst (gx_src; rowprep's
+ *   grad_dst is gx_dst); grad_h = [grad_out +] sum_t (gz_t W_h,t + gx_src,t W_a,t + gx_dst,t W_b,t), tower t's slice when divide_input,
+ *   summed in tower order otherwise; grad_w_post,t = gz_t^T [h_t | row_scale[s] a_t], grad_b_post,t = colsum gz_t, grad_w_pre,t =
+ *   [gx_src,t^T h_t | gx_dst,t^T h_t], grad_b_pre,t = colsum gx_dst,t, grad_w_mix = g_p^T hcat, grad_b_mix = colsum g_p.
+ * The transposed graph (backward only): col_t / rank_t as in pna_segreduce_bwd_pull_args, items_t = ONE whole-row record {u, beg, end, -1}
+ * per source row (n_items_t == V: no hub segments, so no atomics).  workspace: pna_tower_train_workspace_bytes(...) bytes, 256-byte
+ * aligned, no initialisation; the backward reads nothing the forward left in it. */
+typedef struct pna_tower_train_args {
+  uint32_t struct_size;    /* sizeof(pna_tower_train_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* rowptr;   /* [V+1] */
+  const int32_t* col;      /* [E] (may be NULL when E == 0) */
+  int32_t V;
+  int32_t E;
+  int32_t n_tower;
+  int32_t Fi;              /* a tower's input width */
+  int32_t Fo;              /* a tower's output width */
+  int32_t n_scaler;
+  int32_t divide_input;    /* 1: tower t reads columns [t Fi, (t+1) Fi) of h; 0: every tower reads all Fi columns */
+  int32_t residual;        /* != 0: out = h + ..., grad_h += grad_out (needs in_dim == n_tower Fo) */
+  const float* h;          /* (V, ldh >= in_dim) */
+  int64_t ldh;
+  const float* snorm_n;    /* [V] graph-norm factor or NULL = graph norm off */
+  const float* row_scale[PNA_MAX_SCALER];  /* first n_scaler: [V] or NULL = identity */
+  const float* w_pre[PNA_MAX_TOWER];       /* first n_tower of each: (Fi, 2 Fi) */
+  const float* b_pre[PNA_MAX_TOWER];       /* [Fi] */
+  const float* w_post[PNA_MAX_TOWER];      /* (Fo, (1 + 4 n_scaler) Fi) */
+  const float* b_post[PNA_MAX_TOWER];      /* [Fo] */
+  const float* gamma[PNA_MAX_TOWER];       /* [Fo] or NULL (with beta; all towers or none) */
+  const float* beta[PNA_MAX_TOWER];
+  float* running_mean[PNA_MAX_TOWER];      /* [Fo], nullable (with running_var) */
+  float* running_var[PNA_MAX_TOWER];
+  const float* w_mix;      /* (C, C), C = n_tower Fo */
+  const float* b_mix;      /* [C] or NULL */
+  float slope;             /* the LeakyReLU's negative slope */
+  float eps;
+  float momentum;          /* forward: < 0 = running statistics not updated */
+  int32_t _pad0;
+  float* x_cat;            /* saved (V, 2 T Fi) contiguous: [x_src | x_dst]; forward writes, backward reads */
+  float* a;                /* saved (V, T 4 Fi) contiguous: per tower [mean | max | min | std] */
+  int32_t* argmax;         /* saved (V, T Fi) contiguous */
+  int32_t* argmin;
+  float* z;                /* saved (V, C) contiguous: the BatchNorms' input */
+  float* p;                /* saved (V, C) contiguous: the mixing Linear's output */
+  float* save_mean;        /* saved [C] */
+  float* save_invstd;      /* saved [C] */
+  float* out;              /* forward (V, ld_out >= C) */
+  int64_t ld_out;
+  const float* grad_out;   /* backward (V, ld_go >= C) */
+  int64_t ld_go;
+  const int32_t* col_t;    /* backward: the transposed graph */
+  const int32_t* rank_t;
+  const int32_t* items_t;
+  int32_t n_items_t;
+  int32_t _pad1;
+  float* grad_h;           /* backward (V, in_dim) contiguous */
+  float* grad_w_pre[PNA_MAX_TOWER];        /* backward, first n_tower of each: the parameter's shape, contiguous */
+  float* grad_b_pre[PNA_MAX_TOWER];
+  float* grad_w_post[PNA_MAX_TOWER];
+  float* grad_b_post[PNA_MAX_TOWER];
+  float* grad_gamma[PNA_MAX_TOWER];        /* [Fo] (NULL where gamma is) */
+  float* grad_beta[PNA_MAX_TOWER];
+  float* grad_w_mix;       /* (C, C) */
+  float* grad_b_mix;       /* [C] */
+  void* workspace;
+  int64_t workspace_bytes;
+} pna_tower_train_args;
+
+int64_t pna_tower_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input);
+int pna_tower_train_fwd_f32(const pna_tower_train_args* args, pna_stream_t stream);
+int pna_tower_train_bwd_f32(const pna_tower_train_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

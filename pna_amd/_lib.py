@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PNA_AMD_LIB_PATH") or os.path.join(_HERE, "lib", "lib
 PNA_ABI_VERSION = 23
 PNA_MAX_AGGR = 8
 PNA_MAX_SCALER = 8
+PNA_MAX_TOWER = 8
 
 # (std_pyg: the bf16 entry points only -- the PyG std, whose row without in-edges is sqrt(1e-5) in the device code)
 AGG_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5, "var_raw": 6, "std_pyg": 7}
@@ -333,6 +334,27 @@ class PnaSimpleTrainArgs(_Args):
     ]
 
 
+class PnaTowerTrainArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32), ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p),
+        ("V", ctypes.c_int32), ("E", ctypes.c_int32), ("n_tower", ctypes.c_int32), ("Fi", ctypes.c_int32), ("Fo", ctypes.c_int32),
+        ("n_scaler", ctypes.c_int32), ("divide_input", ctypes.c_int32), ("residual", ctypes.c_int32), ("h", ctypes.c_void_p),
+        ("ldh", ctypes.c_int64), ("snorm_n", ctypes.c_void_p), ("row_scale", ctypes.c_void_p * PNA_MAX_SCALER),
+        ("w_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("b_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("w_post", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("b_post", ctypes.c_void_p * PNA_MAX_TOWER), ("gamma", ctypes.c_void_p * PNA_MAX_TOWER), ("beta", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("running_mean", ctypes.c_void_p * PNA_MAX_TOWER), ("running_var", ctypes.c_void_p * PNA_MAX_TOWER), ("w_mix", ctypes.c_void_p),
+        ("b_mix", ctypes.c_void_p), ("slope", ctypes.c_float), ("eps", ctypes.c_float), ("momentum", ctypes.c_float), ("_pad0", ctypes.c_int32),
+        ("x_cat", ctypes.c_void_p), ("a", ctypes.c_void_p), ("argmax", ctypes.c_void_p), ("argmin", ctypes.c_void_p), ("z", ctypes.c_void_p),
+        ("p", ctypes.c_void_p), ("save_mean", ctypes.c_void_p), ("save_invstd", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("ld_out", ctypes.c_int64), ("grad_out", ctypes.c_void_p), ("ld_go", ctypes.c_int64), ("col_t", ctypes.c_void_p),
+        ("rank_t", ctypes.c_void_p), ("items_t", ctypes.c_void_p), ("n_items_t", ctypes.c_int32), ("_pad1", ctypes.c_int32),
+        ("grad_h", ctypes.c_void_p), ("grad_w_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_b_pre", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("grad_w_post", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_b_post", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("grad_gamma", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_beta", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_w_mix", ctypes.c_void_p),
+        ("grad_b_mix", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -476,6 +498,11 @@ def lib():
         L.pna_simple_train_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_simple_train_fwd_f32, L.pna_simple_train_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaSimpleTrainArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_tower_train_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 5
+        L.pna_tower_train_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_tower_train_fwd_f32, L.pna_tower_train_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaTowerTrainArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")

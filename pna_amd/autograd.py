@@ -688,6 +688,24 @@ class BnTailFn(torch.autograd.Function):
                 go if ctx.has_res else None, None, None, None, None, None)
 
 
+def _transposed_whole_rows(graph):
+    """(col_t, rank_t, items_t) of the one-call training backwards' pull: the transposed graph's destinations, the position of every
+    transposed edge in its destination's in-edge list, and one whole-row record per source row (no hub segments: no atomics).  Kept on
+    the graph, like the pull of the generic route keeps them."""
+    from .graph import Graph
+    csr = graph.csr
+    V = graph.num_nodes
+    gT = getattr(graph, "_pna_amd_transposed", None)
+    if gT is None or gT.num_nodes != V:
+        gT = graph._pna_amd_transposed = Graph(csr.row.long(), csr.col.long(), V)     # edge (v -> u): pulls row v into u
+    tcsr = gT.csr
+    rank_t = getattr(gT, "_pna_amd_rank_t", None)
+    if rank_t is None:
+        rank_t = (tcsr.eid.to(torch.int64) - csr.rowptr.to(torch.int64)[tcsr.col.long()]).to(torch.int32).contiguous()
+        gT._pna_amd_rank_t = rank_t
+    return tcsr.col, rank_t, gT.work_items(threshold=1 << 30)
+
+
 class _SmallTrainPlan:
     """What one call of SimpleLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays (kept on the graph, like
     the pull of the generic route keeps them) and the call's workspace -- the graph's reusable scratch (Graph.workspace: allocated once
@@ -695,20 +713,10 @@ class _SmallTrainPlan:
     Nothing here depends on weight values.  One caller at a time per Graph (functional.py's rule for the shared scratch)."""
 
     def __init__(self, graph, F, N, S, dev):
-        from .graph import Graph
         csr = graph.csr
         V, E = graph.num_nodes, int(csr.col.numel())
         self.V, self.E, self.F, self.N, self.S, self.dev = V, E, F, N, S, dev
-        gT = getattr(graph, "_pna_amd_transposed", None)
-        if gT is None or gT.num_nodes != V:
-            gT = graph._pna_amd_transposed = Graph(csr.row.long(), csr.col.long(), V)     # edge (v -> u): pulls row v into u
-        tcsr = gT.csr
-        rank_t = getattr(gT, "_pna_amd_rank_t", None)
-        if rank_t is None:                                    # position of every transposed edge in its destination's in-edge list
-            rank_t = (tcsr.eid.to(torch.int64) - csr.rowptr.to(torch.int64)[tcsr.col.long()]).to(torch.int32).contiguous()
-            gT._pna_amd_rank_t = rank_t
-        self.col_t, self.rank_t = tcsr.col, rank_t
-        self.items_t = gT.work_items(threshold=1 << 30)       # one whole-row record per source row: no hub segments, no atomics
+        self.col_t, self.rank_t, self.items_t = _transposed_whole_rows(graph)
         nbytes = _lib.lib().pna_simple_train_workspace_bytes(V, E, F, N, S)
         if nbytes < 0:
             raise RuntimeError("SimpleLayerSmallTrainFn: shape outside pna_simple_train_*_f32 (the layer checks it before taking this path)")
@@ -806,3 +814,171 @@ def simple_layer_small_train(layer, graph, h, scales):
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return SimpleLayerSmallTrainFn.apply(h, lin.weight, lin.bias, bn.weight, bn.bias, layer, graph, tuple(scales))
+
+
+class _TowerTrainPlan:
+    """What one call of TowerLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays and the call's
+    workspace (Graph.workspace: every launch writes what it reads, nothing is carried from the forward to the backward).  Nothing here
+    depends on weight values.  One caller at a time per Graph."""
+
+    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev):
+        V, E = graph.num_nodes, int(graph.csr.col.numel())
+        self.V, self.E, self.T, self.Fi, self.Fo, self.S, self.div, self.dev = V, E, T, Fi, Fo, S, bool(divide_input), dev
+        self.col_t, self.rank_t, self.items_t = _transposed_whole_rows(graph)
+        nbytes = _lib.lib().pna_tower_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div))
+        if nbytes < 0:
+            raise RuntimeError("TowerLayerSmallTrainFn: shape outside pna_tower_train_*_f32 (the layer checks it before taking this path)")
+        ws = graph.workspace(nbytes + 256)
+        self.ws = ws[(-ws.data_ptr() // 4) % 64:][:nbytes // 4]                 # 256-byte aligned
+        self.nbytes = nbytes
+
+    def new_saved(self):
+        """The state one forward leaves for its backward -- x_cat (V, 2 T Fi) | a (V, T 4 Fi) | z (V, C) | p (V, C) | save_mean,
+        save_invstd [C] in one buffer, argmax | argmin (V, T Fi) in another.  Per CALL, not per plan: two layers of one shape on one
+        graph are both alive until their backwards."""
+        V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
+        fbuf = torch.empty(V * 6 * TFi + 2 * V * C + 2 * C, dtype=torch.float32, device=self.dev)
+        ibuf = torch.empty(2, V, TFi, dtype=torch.int32, device=self.dev)
+        return fbuf, ibuf
+
+    def views(self, saved):
+        """(x_cat, a, z, p, stats (2, C), argmax, argmin) of a saved state."""
+        fbuf, ibuf = saved
+        V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
+        cuts = [V * 2 * TFi, V * 4 * TFi, V * C, V * C, 2 * C]
+        parts, o = [], 0
+        for n in cuts:
+            parts.append(fbuf[o:o + n])
+            o += n
+        return (parts[0].view(V, 2 * TFi), parts[1].view(V, 4 * TFi), parts[2].view(V, C), parts[3].view(V, C), parts[4].view(2, C), ibuf[0], ibuf[1])
+
+    def args(self, graph, h, snorm, scales, towers, mix_w, mix_b, slope, residual, saved):
+        """towers: per tower (w_pre, b_pre, w_post, b_post, gamma, beta, running_mean, running_var, eps, momentum)."""
+        csr = graph.csr
+        a = _lib.PnaTowerTrainArgs()
+        a.rowptr = _lib.dev_ptr(csr.rowptr, torch.int32, "rowptr")
+        a.col = _lib.dev_ptr(csr.col, torch.int32, "col") if self.E else None
+        a.V, a.E, a.n_tower, a.Fi, a.Fo, a.n_scaler = self.V, self.E, self.T, self.Fi, self.Fo, self.S
+        a.divide_input, a.residual = int(self.div), int(residual)
+        a.h, a.ldh = _lib.dev_ptr(h, torch.float32, "h"), h.stride(0)
+        if snorm is not None:
+            a.snorm_n = _lib.dev_ptr(snorm, torch.float32, "snorm_n")
+        for s, rs in enumerate(scales):
+            if rs is not None:
+                a.row_scale[s] = _lib.dev_ptr(rs, torch.float32, "row_scale").value
+        for t, (w_pre, b_pre, w_post, b_post, gamma, beta, rm, rv, eps, mom) in enumerate(towers):
+            a.w_pre[t], a.b_pre[t] = w_pre.data_ptr(), b_pre.data_ptr()
+            a.w_post[t], a.b_post[t] = w_post.data_ptr(), b_post.data_ptr()
+            if gamma is not None:
+                a.gamma[t], a.beta[t] = gamma.data_ptr(), beta.data_ptr()
+            if rm is not None:
+                a.running_mean[t], a.running_var[t] = rm.data_ptr(), rv.data_ptr()
+            a.eps, a.momentum = float(eps), float(mom)
+        a.w_mix = _lib.dev_ptr(mix_w, torch.float32, "w_mix")
+        a.b_mix = _lib.dev_ptr(mix_b, torch.float32, "b_mix")
+        a.slope = float(slope)
+        x_cat, agg, z, p, stats, amx, amn = self.views(saved)
+        a.x_cat, a.a, a.z, a.p = x_cat.data_ptr(), agg.data_ptr(), z.data_ptr(), p.data_ptr()
+        a.save_mean, a.save_invstd = stats[0].data_ptr(), stats[1].data_ptr()
+        a.argmax, a.argmin = amx.data_ptr(), amn.data_ptr()
+        a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.nbytes
+        return a
+
+    def set_backward(self, a, go, g_h, grads, g_mix_w, g_mix_b):
+        """grads: per tower (grad_w_pre, grad_b_pre, grad_w_post, grad_b_post, grad_gamma, grad_beta)."""
+        a.momentum = -1.0
+        a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
+        a.col_t, a.rank_t = _lib.dev_ptr(self.col_t, torch.int32, "col_t"), _lib.dev_ptr(self.rank_t, torch.int32, "rank_t")
+        a.items_t, a.n_items_t = _lib.dev_ptr(self.items_t, torch.int32, "items_t"), self.items_t.shape[0]
+        a.grad_h = _lib.dev_ptr(g_h, torch.float32, "grad_h")
+        for t, (gwp, gbp, gwo, gbo, gg, gb) in enumerate(grads):
+            a.grad_w_pre[t], a.grad_b_pre[t], a.grad_w_post[t], a.grad_b_post[t] = gwp.data_ptr(), gbp.data_ptr(), gwo.data_ptr(), gbo.data_ptr()
+            if gg is not None:
+                a.grad_gamma[t], a.grad_beta[t] = gg.data_ptr(), gb.data_ptr()
+        a.grad_w_mix, a.grad_b_mix = _lib.dev_ptr(g_mix_w, torch.float32, "grad_w_mix"), _lib.dev_ptr(g_mix_b, torch.float32, "grad_b_mix")
+        return a
+
+
+def _tower_train_tensors(layer):
+    """Per tower (w_pre, b_pre, w_post, b_post, gamma, beta, running_mean, running_var, eps, momentum) from the modules' own tensors."""
+    out = []
+    for t in layer.towers:
+        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
+        out.append((pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
+    return out
+
+
+class TowerLayerSmallTrainFn(torch.autograd.Function):
+    """PNALayer's training forward (per tower: pretrans, gather, scalers, posttrans, graph norm, batch-statistics BatchNorm; the mixing
+    Linear + LeakyReLU, the residual: models/dgl/pna_layer.py:55-76, 130-145) on a molecule-sized batch as ONE C call
+    (pna_tower_train_fwd_f32) and its backward as one (pna_tower_train_bwd_f32).  The weights are the modules' own tensors (no stack, no
+    packed image); the output, the gradients and the state a forward saves for its backward are fresh tensors per call.  `params`: per
+    tower w_pre, b_pre, w_post, b_post, gamma, beta; then the mixing weight and bias."""
+
+    @staticmethod
+    def forward(ctx, h, layer, graph, scales, snorm, *params):
+        T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
+        dev = h.device
+        x = h if h.stride(1) == 1 else h.contiguous()
+        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev)
+        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
+        saved = plan.new_saved()
+        mix = layer.mixing_network
+        slope = mix.activation.negative_slope
+        a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer), mix.linear.weight, mix.linear.bias, slope, layer.residual, saved)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        _lib.check(_lib.lib().pna_tower_train_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_tower_train_fwd_f32")
+        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope = plan, graph, layer, scales, snorm, saved, slope
+        ctx.save_for_backward(x, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, *params = ctx.saved_tensors
+        plan, layer = ctx.plan, ctx.layer
+        T, Fi, Fo, S = plan.T, plan.Fi, plan.Fo, plan.S
+        C = T * Fo
+        dev = x.device
+        go = go if go.stride(1) == 1 else go.contiguous()
+        g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
+        # one buffer per kind of parameter: (T, ...) blocks the towers' gradients are views of
+        g_wpre = torch.empty(T, Fi, 2 * Fi, dtype=torch.float32, device=dev)
+        g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
+        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
+        g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
+        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
+        towers = []
+        for t in range(T):
+            w_pre, b_pre, w_post, b_post, gamma, beta = params[6 * t:6 * t + 6]
+            bn = layer.towers[t].batchnorm_h
+            towers.append((w_pre, b_pre, w_post, b_post, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
+        mix_w, mix_b = params[6 * T], params[6 * T + 1]
+        a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, towers, mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
+        has_affine = towers[0][4] is not None
+        grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
+                 for t in range(T)]
+        plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
+        _lib.check(_lib.lib().pna_tower_train_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_tower_train_bwd_f32")
+        need = ctx.needs_input_grad
+        res = [g_h if need[0] else None, None, None, None, None]
+        for t in range(T):
+            res += [grads[t][0], grads[t][1], grads[t][2], grads[t][3], grads[t][4], grads[t][5]]
+        res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
+        return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
+
+
+def tower_layer_small_train(layer, graph, h, snorm_n, scales):
+    """[h +] leaky(mixing(cat_t bn_t(graph_norm(posttrans_t(...))))) of a training PNALayer through TowerLayerSmallTrainFn; every tower's
+    num_batches_tracked advances like the module's own forward."""
+    params = []
+    for t in layer.towers:
+        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        params += [pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias]
+    mix = layer.mixing_network.linear
+    snorm = None
+    if layer.towers[0].graph_norm:
+        snorm = snorm_n.reshape(-1)
+        snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
+    return TowerLayerSmallTrainFn.apply(h, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)

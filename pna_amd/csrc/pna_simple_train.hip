@@ -20,30 +20,17 @@
 #include "pna_amd.h"
 #include "pna_internal.h"
 #include "pna_rowstats.h"
+#include "pna_train_dev.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
+using namespace pna_train;      // f4, kRows, quads, pitch_of, quad_fma, bn_affine, fold_msg, bn_finalize_column
 
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
-constexpr int kRows = 16;        // destination rows of a workgroup = the M of one MFMA tile
 constexpr int kSlab = 128;       // rows per workgroup of the backward's column sums
 constexpr int kMaxN = 128;
 constexpr int kEU = 4;           // edges of a row whose gathers are issued together
-
-__host__ __device__ constexpr int quads(int k) { return (k + 15) / 16; }
-__host__ __device__ constexpr int pitch_of(int q) { return q * 16 + 4; }   // LDS row pitch (floats): rows 16-byte aligned, banks staggered
-
-__device__ __forceinline__ void quad_fma(f4& acc, const f4 a, const f4 b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-}
-
-// z = (y - mean) (gamma invstd) + beta: pna_bn_tail.hip's expression (the backward recomputes the ReLU mask with it)
-__device__ __forceinline__ float bn_affine(float y, float mean, float a, float b) { return __builtin_fmaf(y - mean, a, b); }
 
 struct KArgs {
   const int32_t* rowptr; const int32_t* col;
@@ -108,14 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_st_rows_fwd(const KArgs g) {
         if (e + u < end) {                                  // (wavefront-uniform)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            const float m = v[u][j];
-            s[j] = s[j] + m;
-            q[j] = q[j] + m * m;
-            // pna_segreduce.hip's arg fold: strict comparison (the FIRST extremal edge wins), NaN sticky
-            const bool gx = m > mx[j] || (m != m && mx[j] == mx[j]);
-            const bool gn = m < mn[j] || (m != m && mn[j] == mn[j]);
-            mx[j] = gx ? m : mx[j]; ax[j] = gx ? e + u : ax[j];
-            mn[j] = gn ? m : mn[j]; an[j] = gn ? e + u : an[j];
+            fold_msg(v[u][j], e + u, s[j], q[j], mx[j], mn[j], ax[j], an[j]);
           }
         }
     }
@@ -185,35 +165,9 @@ __global__ __launch_bounds__(kThreads) void k_st_rows_fwd(const KArgs g) {
 // ---- forward, launch 2: one workgroup per column -- the tiles' sums in float64, the column's constants (pna_bn_tail's finalize) ----
 __global__ __launch_bounds__(256) void k_st_bn_finalize(const KArgs g) {
   __shared__ double red[2][256];
-  const int c = blockIdx.x, N = g.N;
-  const double k0 = (double)g.z[c];                         // the shift of the whole column: z[0, c]
-  double t0 = 0.0, t1 = 0.0;
-  for (int t = threadIdx.x; t < g.n_part; t += 256) {
-    const double nt = (double)min(kRows, g.V - t * kRows);
-    const double dk = (double)g.z[(size_t)t * kRows * N + c] - k0;
-    const double s = (double)g.part[((size_t)t * 2 + 0) * N + c], q = (double)g.part[((size_t)t * 2 + 1) * N + c];
-    t0 += s + nt * dk;                                      // sum (z - k0)   = sum (z - k_t) + n_t (k_t - k0)
-    t1 += q + 2.0 * dk * s + nt * dk * dk;                  // sum (z - k0)^2
-  }
-  red[0][threadIdx.x] = t0; red[1][threadIdx.x] = t1;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x != 0) return;
-  const double Sm = red[0][0], Qm = red[1][0], M = (double)g.V;
-  const double md = Sm / M;
-  double var = Qm / M - md * md;                            // biased, like nn.BatchNorm1d's normalisation
-  if (var < 0.0) var = 0.0;
-  const double mean = k0 + md;
-  g.mean[c] = (float)mean;
-  g.invstd[c] = (float)(1.0 / sqrt(var + (double)g.eps));
-  if (g.rmean && g.momentum >= 0.f) {                       // running statistics: the UNBIASED variance (torch.nn.functional.batch_norm)
-    const double m = (double)g.momentum;
-    g.rmean[c] = (float)((1.0 - m) * (double)g.rmean[c] + m * mean);
-    g.rvar[c] = (float)((1.0 - m) * (double)g.rvar[c] + m * var * (M / (M - 1.0)));
-  }
+  const int c = blockIdx.x;
+  bn_finalize_column(g.z, g.N, c, g.V, g.part, g.n_part, g.eps, g.momentum, g.mean + c, g.invstd + c, g.rmean ? g.rmean + c : nullptr,
+                     g.rmean ? g.rvar + c : nullptr, red);
 }
 
 // ---- forward, launch 3: out = residual + relu((z - mean) (gamma invstd) + beta) ----

@@ -1,0 +1,775 @@
+// pna_tower_train.hip -- PNALayer's TRAINING forward and backward on molecule-sized batches (the ZINC workload:
+// realworld_benchmark/README.md:61, realworld_benchmark/train/train_molecules_graph_regression.py:29-32) as ONE C call each for gfx950.
+// Implements pna_tower_train_{workspace_bytes, fwd_f32, bwd_f32} of include/pna_amd.h (models/dgl/pna_layer.py:130-145 over :55-76 in
+// train mode: T towers of 1-layer pretrans, update_all with mean | max | min | std and the degree scalers, 1-layer posttrans, graph
+// norm, BatchNorm1d with batch statistics; then the mixing Linear + LeakyReLU and the residual).
+//
+// Why: at this size the generic training route (torch.stack of the weights, two projection GEMMs, AggregateFn, then PER TOWER a
+// PosttransFn, a multiply, a library BatchNorm and a dropout node, then cat / Linear / LeakyReLU / residual) is bound by launch and
+// host latency.  As in pna_simple_train.hip the work is cut by destination ROWS: a workgroup owns 16 rows and takes the towers one at a
+// time, so the 16 x 4 Fi aggregate tile of ONE tower is all the LDS has to hold; products are exact fp32 on v_mfma_f32_16x16x4_f32.
+// Every weight is read from the module's own tensor through a per-tower pointer (an optimiser rewrites them every step); tower blocks
+// of 75 or 15 floats are not 16-byte aligned, so caller tensors are read with scalar loads and only LDS tiles with 16-byte ones.
+//
+// Determinism: no float atomics.  A row's messages x_src[u] + x_dst[v] are folded serially in CSR order (pna_segreduce_fwd_f32's order
+// for in-degrees <= 128: same bits, same arg indices; the std block is that kernel's on x_src without the destination term); column
+// sums are fp32 inside a 16-row tile and float64 across the tiles in a fixed order, in launches of their own (one workgroup per
+// column: no row workgroup re-adds the partial sums).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "pna_amd.h"
+#include "pna_internal.h"
+#include "pna_rowstats.h"
+#include "pna_train_dev.h"
+
+namespace {
+
+using namespace pna_train;      // f4, kRows, quads, pitch_of, quad_fma, bn_affine, fold_msg, bn_finalize_column
+
+constexpr int kThreads = 512;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxT = PNA_MAX_TOWER;
+constexpr int kMaxC = 128;       // out_dim = T Fo
+constexpr int kMaxFi = 128;      // a lane of the gather owns columns lane and lane + 64
+constexpr int kMaxIn = 512;      // T Fi
+constexpr int kEU = 4;           // edges of a row whose gathers are issued together
+
+struct KArgs {
+  const int32_t* rowptr; const int32_t* col;
+  int V, T, Fi, Fo, S, C, TFi, div, residual;
+  const float* h; long ldh;
+  const float* snorm;                                       // [V] or NULL (graph norm off)
+  const float* scale[3];
+  const float* w_pre[kMaxT]; const float* b_pre[kMaxT];     // (Fi, 2 Fi) = [W_a | W_b], [Fi]
+  const float* w_post[kMaxT]; const float* b_post[kMaxT];   // (Fo, (1 + 4 S) Fi) = [W_h | W_s0 | ..], [Fo]
+  const float* gamma[kMaxT]; const float* beta[kMaxT];
+  float* rmean[kMaxT]; float* rvar[kMaxT];
+  const float* w_mix; const float* b_mix;                   // (C, C), [C]
+  float slope, eps, momentum;
+  float* xcat; float* a; int32_t* amx; int32_t* amn; float* z; float* p; float* mean; float* invstd;     // the saved state
+  float* out; long ld_out;
+  const float* go; long ld_go;
+  float* part; int n_part;                                  // [tiles][2][C] column sums of a 16-row tile
+  float* cm;                                                // backward [2][C]: mean g, mean g xhat
+  float* gp; float* hcat; float* ghc; float* gz;            // backward (V, C) each
+  float* gagg;                                              // backward (V, T 4 Fi): [G_mean | G_max | G_min | G_std] per tower
+  float* gxs; float* gxd;                                   // backward (V, T Fi): the gradient of x_src, x_dst
+  float* gh;                                                // backward (V, in_dim)
+  float* ggamma[kMaxT]; float* gbeta[kMaxT];
+};
+
+__device__ __forceinline__ float leaky(float p, float slope) { return p > 0.f ? p : p * slope; }
+
+// ---- forward, launch 1: x_cat = [x_src | x_dst], x_src,t = W_a,t h_t, x_dst,t = W_b,t h_t + b_t, of 16 rows ----------------------
+__global__ __launch_bounds__(kThreads) void k_tt_project(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int Fi = g.Fi, T = g.T, TFi = g.TFi, in_dim = g.div ? TFi : Fi, PH = in_dim + 1;
+  float* const H = lds;                                     // [16][PH] the rows' input features
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  for (int i = tid; i < kRows * in_dim; i += kThreads) {
+    const int r = i / in_dim, k = i - r * in_dim;
+    H[r * PH + k] = r < nrows ? g.h[(size_t)(r0 + r) * g.ldh + k] : 0.f;
+  }
+  __syncthreads();
+  const int NT = (2 * Fi + 15) / 16, Q = quads(Fi);
+  for (int u = wave; u < T * NT; u += kWaves) {
+    const int t = u / NT, nt = u - t * NT;
+    const int j = nt * 16 + li;                             // output column of the tower's [x_src | x_dst]
+    const bool jok = j < 2 * Fi;
+    const int half = j >= Fi ? 1 : 0, f = min(j - half * Fi, Fi - 1);
+    const float* const wrow = g.w_pre[t] + (size_t)f * 2 * Fi + half * Fi;
+    const float* const hrow = H + li * PH + (g.div ? t * Fi : 0);
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int qd = 0; qd < Q; ++qd) {
+      const int k = 16 * qd + 4 * lg;
+      f4 a, b;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool ok = k + i < Fi;
+        const int kk = ok ? k + i : 0;
+        const float hv = hrow[kk], wv = wrow[kk];
+        a[i] = ok ? hv : 0.f;
+        b[i] = (ok && jok) ? wv : 0.f;
+      }
+      quad_fma(acc, a, b);
+    }
+    const float bias = (jok && half) ? g.b_pre[t][f] : 0.f;
+    if (jok) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * lg + i;
+        if (r < nrows) g.xcat[(size_t)(r0 + r) * 2 * TFi + half * TFi + t * Fi + f] = half ? acc[i] + bias : acc[i];
+      }
+    }
+  }
+}
+
+// ---- forward, launch 2: per tower gather + reduce + contraction of 16 destination rows; the tile's BatchNorm partial sums --------
+template <int S>
+__global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int Fi = g.Fi, Fo = g.Fo, T = g.T, TFi = g.TFi, C = g.C, K = 4 * Fi, Q = quads(K), P = pitch_of(Q), QH = quads(Fi), PH = pitch_of(QH);
+  const int NT = (Fo + 15) / 16, PZ = C + 1;
+  float* const A = lds;                                     // [16][P]  one tower's aggregate [mean | max | min | std]
+  float* const H = A + kRows * P;                           // [16][PH] the tower's input slice
+  float* const Z = H + kRows * PH;                          // [16][PZ] the rows' z, all towers
+  float* const SC = Z + kRows * PZ;                         // [4][16]  scale_0..2 and the graph-norm factor of the tile's rows
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  if (tid < 4 * kRows) {
+    const int s = tid >> 4, r = tid & 15;
+    const float* p = s == 3 ? g.snorm : (s < S ? g.scale[s] : nullptr);
+    SC[tid] = (p && r < nrows) ? p[r0 + r] : 1.f;
+  }
+  for (int t = 0; t < T; ++t) {
+    // zeros in the K padding columns and in the rows past the matrix's end (they multiply weights; 0 * garbage would not be 0)
+    for (int i = tid; i < kRows * P; i += kThreads) {
+      const int r = i / P, k = i - r * P;
+      if (k >= K || r >= nrows) A[i] = 0.f;
+    }
+    for (int i = tid; i < kRows * PH; i += kThreads) {
+      const int r = i / PH, k = i - r * PH;
+      H[i] = (k < Fi && r < nrows) ? g.h[(size_t)(r0 + r) * g.ldh + (g.div ? t * Fi : 0) + k] : 0.f;
+    }
+    // ---- gather: a wavefront owns rows wave, wave + 8; a lane owns columns lane and lane + 64; the row's edges in CSR order.
+    // mean | max | min and the arg indices are those of the message x_src[u] + x_dst[v], as the standalone gather forms it (the
+    // backward's rowprep subtracts x_dst from that mean); the std is that of x_src[u] alone: the same number, without the
+    // cancellation of E[m^2] - E[m]^2 when x_dst dwarfs the neighbours' spread ----
+    const float* const xs = g.xcat + t * Fi;
+    for (int r = wave; r < nrows; r += kWaves) {
+      const int row = r0 + r;
+      const int beg = g.rowptr[row], end = g.rowptr[row + 1];
+      const int cc[2] = {min(lane, Fi - 1), min(lane + 64, Fi - 1)};      // (lanes past the last column redo it; not stored)
+      float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f}, mx[2] = {-INFINITY, -INFINITY}, mn[2] = {INFINITY, INFINITY}, dt[2];
+      float s0[2] = {0.f, 0.f}, q0[2] = {0.f, 0.f};         // sums of x_src[u] alone: the std does not see the shift
+      int ax[2] = {-1, -1}, an[2] = {-1, -1};
+#pragma unroll
+      for (int j = 0; j < 2; ++j) dt[j] = xs[(size_t)row * 2 * TFi + TFi + cc[j]];
+      for (int e = beg; e < end; e += kEU) {
+        float v[kEU][2];
+#pragma unroll
+        for (int u = 0; u < kEU; ++u) {
+          const size_t o = (size_t)g.col[min(e + u, end - 1)] * 2 * TFi;
+          v[u][0] = xs[o + cc[0]];
+          v[u][1] = xs[o + cc[1]];
+        }
+#pragma unroll
+        for (int u = 0; u < kEU; ++u)
+          if (e + u < end) {                                // (wavefront-uniform)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              fold_msg(v[u][j] + dt[j], e + u, s[j], q[j], mx[j], mn[j], ax[j], an[j]);
+              s0[j] = s0[j] + v[u][j];
+              q0[j] = q0[j] + v[u][j] * v[u][j];
+            }
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j;
+        if (c < Fi) {
+          float mean, omx, omn, sd, m0, x0, n0;
+          pna_dev::row_stats(s[j], q[j], mx[j], mn[j], end - beg, mean, omx, omn, sd);     // mean | max | min of the shifted messages
+          pna_dev::row_stats(s0[j], q0[j], mx[j], mn[j], end - beg, m0, x0, n0, sd);       // std of x_src alone
+          float* const al = A + r * P + c;
+          al[0] = mean; al[Fi] = omx; al[2 * Fi] = omn; al[3 * Fi] = sd;
+          float* const ag = g.a + (size_t)row * T * K + (size_t)t * K + c;
+          ag[0] = mean; ag[Fi] = omx; ag[2 * Fi] = omn; ag[3 * Fi] = sd;
+          g.amx[(size_t)row * TFi + t * Fi + c] = ax[j];
+          g.amn[(size_t)row * TFi + t * Fi + c] = an[j];
+        }
+      }
+    }
+    __syncthreads();
+    // ---- contraction: wavefront nt owns the tower's output columns [16 nt, 16 nt + 16); B fragments from the weight's rows ----
+    for (int nt = wave; nt < NT; nt += kWaves) {
+      const int n = nt * 16 + li;
+      const bool nok = n < Fo;
+      const float* const wrow = g.w_post[t] + (size_t)min(n, Fo - 1) * (1 + 4 * S) * Fi;
+      f4 acch = {0.f, 0.f, 0.f, 0.f}, acc[S];
+#pragma unroll
+      for (int s = 0; s < S; ++s) acc[s] = (f4){0.f, 0.f, 0.f, 0.f};
+      for (int qd = 0; qd < QH; ++qd) {                     // the self panel W_h h_t
+        const int k = 16 * qd + 4 * lg;
+        const f4 a = *reinterpret_cast<const f4*>(H + li * PH + k);
+        f4 b;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const bool ok = nok && k + i < Fi;
+          const float wv = wrow[ok ? k + i : 0];
+          b[i] = ok ? wv : 0.f;
+        }
+        quad_fma(acch, a, b);
+      }
+      for (int qd = 0; qd < Q; ++qd) {
+        const int k = 16 * qd + 4 * lg;
+        const f4 a = *reinterpret_cast<const f4*>(A + li * P + k);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          f4 b;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bool ok = nok && k + i < K;
+            const float wv = wrow[Fi + s * K + (ok ? k + i : 0)];
+            b[i] = ok ? wv : 0.f;
+          }
+          quad_fma(acc[s], a, b);
+        }
+      }
+      const float bn = nok ? g.b_post[t][n] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * lg + i;
+        float zt = bn + acch[i];
+#pragma unroll
+        for (int s = 0; s < S; ++s) zt = zt + SC[s * kRows + r] * acc[s][i];
+        if (g.snorm) zt = zt * SC[3 * kRows + r];
+        if (nok) {
+          Z[r * PZ + t * Fo + n] = zt;
+          if (r < nrows) g.z[(size_t)(r0 + r) * C + t * Fo + n] = zt;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // ---- the tile's BatchNorm column sums, shifted by the tile's first row (the finalize pass re-bases them in float64) ----
+  for (int c = tid; c < C; c += kThreads) {
+    const float kc = Z[c];
+    float s0 = 0.f, s1 = 0.f;
+    for (int r = 0; r < nrows; ++r) {
+      const float d = Z[r * PZ + c] - kc;
+      s0 = s0 + d;
+      s1 = s1 + d * d;
+    }
+    g.part[((size_t)blockIdx.x * 2 + 0) * C + c] = s0;
+    g.part[((size_t)blockIdx.x * 2 + 1) * C + c] = s1;
+  }
+}
+
+// ---- forward, launch 3: one workgroup per column -- the tiles' sums in float64, the column's constants, its tower's running statistics ----
+__global__ __launch_bounds__(256) void k_tt_bn_finalize(const KArgs g) {
+  __shared__ double red[2][256];
+  const int c = blockIdx.x, t = c / g.Fo, n = c - t * g.Fo;
+  bn_finalize_column(g.z, g.C, c, g.V, g.part, g.n_part, g.eps, g.momentum, g.mean + c, g.invstd + c, g.rmean[t] ? g.rmean[t] + n : nullptr,
+                     g.rmean[t] ? g.rvar[t] + n : nullptr, red);
+}
+
+// the BatchNorm's per-column multiplier and offset: gamma invstd, beta
+__device__ __forceinline__ void bn_consts(const KArgs& g, int c, float& cm, float& ci, float& ca, float& cb) {
+  const int t = c / g.Fo, n = c - t * g.Fo;
+  cm = g.mean[c]; ci = g.invstd[c];
+  ca = (g.gamma[t] ? g.gamma[t][n] : 1.f) * ci;
+  cb = g.beta[t] ? g.beta[t][n] : 0.f;
+}
+
+// ---- forward, launch 4: hcat = (z - mean) (gamma invstd) + beta, p = W_mix hcat + b_mix (saved), out = [h +] leaky(p) of 16 rows ----
+__global__ __launch_bounds__(kThreads) void k_tt_mix_fwd(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int C = g.C, Q = quads(C), P = pitch_of(Q), NT = (C + 15) / 16;
+  float* const HC = lds;                                    // [16][P]
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  for (int i = tid; i < kRows * P; i += kThreads) {
+    const int r = i / P, c = i - r * P;
+    float v = 0.f;
+    if (c < C && r < nrows) {
+      float cm, ci, ca, cb;
+      bn_consts(g, c, cm, ci, ca, cb);
+      v = bn_affine(g.z[(size_t)(r0 + r) * C + c], cm, ca, cb);
+    }
+    HC[i] = v;
+  }
+  __syncthreads();
+  for (int nt = wave; nt < NT; nt += kWaves) {
+    const int n = nt * 16 + li;
+    const bool nok = n < C;
+    const float* const wrow = g.w_mix + (size_t)min(n, C - 1) * C;
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int qd = 0; qd < Q; ++qd) {
+      const int k = 16 * qd + 4 * lg;
+      const f4 a = *reinterpret_cast<const f4*>(HC + li * P + k);
+      f4 b;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool ok = nok && k + i < C;
+        const float wv = wrow[ok ? k + i : 0];
+        b[i] = ok ? wv : 0.f;
+      }
+      quad_fma(acc, a, b);
+    }
+    if (nok) {
+      const float bn = g.b_mix ? g.b_mix[n] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * lg + i;
+        if (r < nrows) {
+          const size_t row = (size_t)(r0 + r);
+          const float p = acc[i] + bn;
+          g.p[row * C + n] = p;
+          float o = leaky(p, g.slope);
+          if (g.residual) o = g.h[row * g.ldh + n] + o;
+          g.out[row * g.ld_out + n] = o;
+        }
+      }
+    }
+  }
+}
+
+// ---- backward, launch 1: g_p = grad_out leaky'(p), hcat (both stored for the mixing weight's gradient), g_hcat = g_p W_mix (stored),
+// the tile's column sums of g_hcat and g_hcat xhat ----
+__global__ __launch_bounds__(kThreads) void k_tt_mix_bwd(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int C = g.C, Q = quads(C), P = pitch_of(Q), NT = (C + 15) / 16, PG = C + 1;
+  float* const GP = lds;                                    // [16][P]  g_p
+  float* const GH = GP + kRows * P;                         // [16][PG] g_hcat
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  for (int i = tid; i < kRows * P; i += kThreads) {
+    const int r = i / P, c = i - r * P;
+    float v = 0.f;
+    if (c < C && r < nrows) {
+      const size_t row = (size_t)(r0 + r);
+      const float p = g.p[row * C + c], go = g.go[row * g.ld_go + c];
+      v = p > 0.f ? go : go * g.slope;
+      g.gp[row * C + c] = v;
+      float cm, ci, ca, cb;
+      bn_consts(g, c, cm, ci, ca, cb);
+      g.hcat[row * C + c] = bn_affine(g.z[row * C + c], cm, ca, cb);
+    }
+    GP[i] = v;
+  }
+  __syncthreads();
+  // g_hcat tile (16 rows x 16 columns j): A = g_p (K = the mixing output n), B[k = n][j] = W_mix[n][j]
+  for (int jt = wave; jt < NT; jt += kWaves) {
+    const int j = jt * 16 + li;
+    const bool jok = j < C;
+    const int jj = min(j, C - 1);
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int qd = 0; qd < Q; ++qd) {
+      const int k = 16 * qd + 4 * lg;
+      const f4 a = *reinterpret_cast<const f4*>(GP + li * P + k);
+      f4 b;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float wv = g.w_mix[(size_t)min(k + i, C - 1) * C + jj];
+        b[i] = (jok && k + i < C) ? wv : 0.f;
+      }
+      quad_fma(acc, a, b);
+    }
+    if (jok) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * lg + i;
+        GH[r * PG + j] = acc[i];
+        if (r < nrows) g.ghc[(size_t)(r0 + r) * C + j] = acc[i];
+      }
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += kThreads) {
+    const float cm = g.mean[c], ci = g.invstd[c];
+    float s0 = 0.f, s1 = 0.f;
+    for (int r = 0; r < nrows; ++r) {
+      const float gv = GH[r * PG + c];
+      s0 = s0 + gv;
+      s1 = s1 + gv * ((g.z[(size_t)(r0 + r) * C + c] - cm) * ci);
+    }
+    g.part[((size_t)blockIdx.x * 2 + 0) * C + c] = s0;
+    g.part[((size_t)blockIdx.x * 2 + 1) * C + c] = s1;
+  }
+}
+
+// ---- backward, launch 2: one workgroup per column -- the tiles' sums in float64 in a fixed order: grad_beta, grad_gamma, the two means ----
+__global__ __launch_bounds__(256) void k_tt_bwd_finalize(const KArgs g) {
+  __shared__ double red[2][256];
+  const int c = blockIdx.x, C = g.C;
+  double t0 = 0.0, t1 = 0.0;
+  for (int t = threadIdx.x; t < g.n_part; t += 256) {
+    t0 += (double)g.part[((size_t)t * 2 + 0) * C + c];
+    t1 += (double)g.part[((size_t)t * 2 + 1) * C + c];
+  }
+  red[0][threadIdx.x] = t0; red[1][threadIdx.x] = t1;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const int t = c / g.Fo, n = c - t * g.Fo;
+  g.cm[c] = (float)(red[0][0] / (double)g.V);
+  g.cm[C + c] = (float)(red[1][0] / (double)g.V);
+  if (g.gbeta[t]) g.gbeta[t][n] = (float)red[0][0];
+  if (g.ggamma[t]) g.ggamma[t][n] = (float)red[1][0];
+}
+
+// ---- backward, launch 3: gz = n[v] gamma invstd (g - mean g - xhat mean(g xhat)) (stored) and, per tower, G = sum_s scale_s (gz_t W_s)
+// of 16 rows into gagg's [G_mean | G_max | G_min | G_std] ----
+template <int S>
+__global__ __launch_bounds__(kThreads) void k_tt_rows_bwd(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int Fi = g.Fi, Fo = g.Fo, T = g.T, C = g.C, K = 4 * Fi, QN = quads(Fo), PN = pitch_of(QN), NTJ = (K + 15) / 16;
+  float* const GZ = lds;                                    // [T][16][PN] gz, a padded block per tower
+  float* const SC = GZ + T * kRows * PN;                    // [4][16]
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  if (tid < 4 * kRows) {
+    const int s = tid >> 4, r = tid & 15;
+    const float* p = s == 3 ? g.snorm : (s < S ? g.scale[s] : nullptr);
+    SC[tid] = (p && r < nrows) ? p[r0 + r] : 1.f;
+  }
+  __syncthreads();
+  for (int i = tid; i < T * kRows * PN; i += kThreads) {
+    const int t = i / (kRows * PN), rem = i - t * kRows * PN, r = rem / PN, n = rem - r * PN;
+    float val = 0.f;
+    if (n < Fo && r < nrows) {
+      const int c = t * Fo + n;
+      const size_t row = (size_t)(r0 + r);
+      float cm, ci, ca, cb;
+      bn_consts(g, c, cm, ci, ca, cb);
+      // pna_bn_tail's backward apply, op by op; the graph-norm factor last
+      val = ca * ((g.ghc[row * C + c] - g.cm[c]) - ((g.z[row * C + c] - cm) * ci) * g.cm[C + c]);
+      if (g.snorm) val = val * SC[3 * kRows + r];
+      g.gz[row * C + c] = val;
+    }
+    GZ[i] = val;
+  }
+  __syncthreads();
+  // G tile (16 rows x 16 columns of the tower's 4 Fi) per wavefront: A = gz_t (K = Fo), B[k = n][j] = W_post,t[n][Fi + s 4Fi + j]
+  for (int u = wave; u < T * NTJ; u += kWaves) {
+    const int t = u / NTJ, jt = u - t * NTJ;
+    const int j = jt * 16 + li;
+    const bool jok = j < K;
+    const int jj = min(j, K - 1);
+    const float* const w = g.w_post[t] + Fi + jj;
+    const long ldw = (long)(1 + 4 * S) * Fi;
+    f4 acc[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) acc[s] = (f4){0.f, 0.f, 0.f, 0.f};
+    for (int qd = 0; qd < QN; ++qd) {
+      const int k = 16 * qd + 4 * lg;
+      const f4 a = *reinterpret_cast<const f4*>(GZ + (t * kRows + li) * PN + k);
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        f4 b;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float wv = w[(size_t)min(k + i, Fo - 1) * ldw + (size_t)s * K];
+          b[i] = (jok && k + i < Fo) ? wv : 0.f;
+        }
+        quad_fma(acc[s], a, b);
+      }
+    }
+    if (jok) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * lg + i;
+        if (r < nrows) {
+          float G = SC[r] * acc[0][i];
+#pragma unroll
+          for (int s = 1; s < S; ++s) G = G + SC[s * kRows + r] * acc[s][i];
+          g.gagg[(size_t)(r0 + r) * T * K + (size_t)t * K + j] = G;
+        }
+      }
+    }
+  }
+}
+
+// ---- backward, after the pull: grad_h = [grad_out +] sum_t (gz_t W_h,t + gx_src,t W_a,t + gx_dst,t W_b,t) of 16 rows; a tower's slice
+// when the input is divided, the towers added in tower order (in the accumulator) otherwise ----
+__global__ __launch_bounds__(kThreads) void k_tt_grad_h(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int Fi = g.Fi, Fo = g.Fo, T = g.T, TFi = g.TFi, C = g.C, KK = Fo + 2 * Fi, Q = quads(KK), P = pitch_of(Q);
+  const int NTI = (Fi + 15) / 16;                           // <= 8: a wavefront owns at most one column tile
+  const int in_dim = g.div ? TFi : Fi;
+  float* const A = lds;                                     // [16][P] one tower's [gz_t | gx_src,t | gx_dst,t]
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  const int i0 = wave * 16 + li;                            // this lane's input column inside the tower
+  const bool iok = wave < NTI && i0 < Fi;
+  const int ii = min(i0, Fi - 1);
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < T; ++t) {
+    __syncthreads();
+    for (int i = tid; i < kRows * P; i += kThreads) {
+      const int r = i / P, k = i - r * P;
+      float v = 0.f;
+      if (k < KK && r < nrows) {
+        const size_t row = (size_t)(r0 + r);
+        v = k < Fo ? g.gz[row * C + t * Fo + k] : (k < Fo + Fi ? g.gxs[row * TFi + t * Fi + (k - Fo)] : g.gxd[row * TFi + t * Fi + (k - Fo - Fi)]);
+      }
+      A[i] = v;
+    }
+    __syncthreads();
+    if (wave < NTI) {
+      const float* const wpost = g.w_post[t] + ii;          // W_h,t[k][i]: row k of the posttrans weight, column i
+      const float* const wpre = g.w_pre[t];
+      const long ldpost = (long)(1 + 4 * g.S) * Fi;
+      for (int qd = 0; qd < Q; ++qd) {
+        const int k = 16 * qd + 4 * lg;
+        const f4 a = *reinterpret_cast<const f4*>(A + li * P + k);
+        f4 b;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int kk = min(k + i, KK - 1);
+          float wv;
+          if (kk < Fo) wv = wpost[(size_t)kk * ldpost];
+          else if (kk < Fo + Fi) wv = wpre[(size_t)(kk - Fo) * 2 * Fi + ii];
+          else wv = wpre[(size_t)(kk - Fo - Fi) * 2 * Fi + Fi + ii];
+          b[i] = (iok && k + i < KK) ? wv : 0.f;
+        }
+        quad_fma(acc, a, b);
+      }
+      if (g.div || t == T - 1) {
+        if (iok) {
+          const int col = (g.div ? t * Fi : 0) + i0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int r = 4 * lg + i;
+            if (r < nrows) {
+              const size_t row = (size_t)(r0 + r);
+              g.gh[row * in_dim + col] = g.residual ? g.go[row * g.ld_go + col] + acc[i] : acc[i];
+            }
+          }
+        }
+        acc = (f4){0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+}
+
+// ---- a weight gradient outside pna_posttrans_dw_f32's shape limits: gw[n][k] = sum_v [scale[v]] gy[v][n] a[v][k], one thread per (n, k),
+// the rows in sequence (fp32, a fixed order).  gb[n] = sum_v gy[v][n] from the threads of k = 0. ----
+__global__ __launch_bounds__(256) void k_tt_dw_plain(const float* gy, long ldg, int N, const float* a, long lda, int K, const float* scale, int V,
+                                                     float* gw, long ldw, float* gb) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)N * K) return;
+  const int n = (int)(i / K), k = (int)(i - (long)n * K);
+  float acc = 0.f, sb = 0.f;
+  for (int v = 0; v < V; ++v) {
+    const float gv = gy[(size_t)v * ldg + n], av = a[(size_t)v * lda + k];
+    sb = sb + gv;
+    acc = acc + ((scale ? scale[v] : 1.f) * gv) * av;
+  }
+  gw[(size_t)n * ldw + k] = acc;
+  if (k == 0 && gb) gb[n] = sb;
+}
+
+inline int64_t up64(int64_t floats) { return (floats + 63) / 64 * 64; }     // workspace pieces at 256-byte boundaries
+
+struct Layout {
+  int64_t part_fwd, part_bwd, cm, gp, hcat, ghc, gz, gagg, gxs, gxd, packed, dw, total;      // offsets in floats
+  int64_t pitch, dw_bytes;
+  int n_tile;
+};
+
+bool in_scope(int64_t V, int64_t E, int T, int Fi, int Fo, int S, int div) {
+  return V >= 2 && V < (1ll << 31) - kRows && E >= 0 && E < (1ll << 31) && T >= 1 && T <= kMaxT && Fi >= 4 && Fi <= kMaxFi && (int64_t)T * Fi <= kMaxIn &&
+         Fo >= 1 && (int64_t)T * Fo <= kMaxC && S >= 1 && S <= 3 && (div == 0 || div == 1);
+}
+
+// pna_posttrans_dw_f32's shape limits and workspace (include/pna_amd.h: n_scaler N <= 240, K + Kh + 1 <= 384; one 240 x 384 fp32 partial
+// per slab of >= 256 rows -- how many slabs depends on the device: room for the most it can ask for), restated here so that a call
+// of this route asks the runtime nothing
+bool dw_takes(int N, int S, int K, int Kh) { return S * N <= 240 && K + Kh + 1 <= 384; }
+int64_t dw_bytes_of(int64_t V, int N, int S, int K, int Kh) { return dw_takes(N, S, K, Kh) ? (int64_t)240 * 384 * 4 * ((V + 255) / 256) : 0; }
+
+Layout layout_of(int64_t V, int T, int Fi, int Fo, int S) {
+  Layout l;
+  const int64_t C = (int64_t)T * Fo, TFi = (int64_t)T * Fi;
+  l.n_tile = (int)((V + kRows - 1) / kRows);
+  l.pitch = (5 * TFi + 31) / 32 * 32;
+  l.part_fwd = 0;
+  l.part_bwd = l.part_fwd + up64((int64_t)l.n_tile * 2 * C);
+  l.cm = l.part_bwd + up64((int64_t)l.n_tile * 2 * C);
+  l.gp = l.cm + up64(2 * C);
+  l.hcat = l.gp + up64(V * C);
+  l.ghc = l.hcat + up64(V * C);
+  l.gz = l.ghc + up64(V * C);
+  l.gagg = l.gz + up64(V * C);
+  l.gxs = l.gagg + up64(V * 4 * TFi);
+  l.gxd = l.gxs + up64(V * TFi);
+  l.packed = l.gxd + up64(V * TFi);
+  l.dw = l.packed + up64(V * l.pitch);
+  int64_t b = dw_bytes_of(V, Fo, S, 4 * Fi, Fi);
+  const int64_t b1 = dw_bytes_of(V, Fi, 1, Fi, 0), b2 = dw_bytes_of(V, (int)C, 1, (int)C, 0);
+  b = b > b1 ? b : b1;
+  l.dw_bytes = b > b2 ? b : b2;
+  l.total = l.dw + up64((l.dw_bytes + 3) / 4);
+  return l;
+}
+
+int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const char* who) {
+  if (!p) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(bwd ? "pna_tower_train_bwd_f32" : "pna_tower_train_fwd_f32", p->struct_size, sizeof(*p))) return rc_ss;
+  const int T = p->n_tower, Fi = p->Fi, Fo = p->Fo, S = p->n_scaler;
+  if (!in_scope(p->V, p->E, T, Fi, Fo, S, p->divide_input)) return pna_set_error(PNA_E_INVALID, who);
+  const int in_dim = p->divide_input ? T * Fi : Fi, C = T * Fo;
+  if (p->residual && in_dim != C) return pna_set_error(PNA_E_INVALID, who);
+  if (!p->rowptr || (p->E > 0 && !p->col) || !p->h || p->ldh < in_dim || !p->w_mix || !p->x_cat || !p->a || !p->argmax || !p->argmin || !p->z || !p->p ||
+      !p->save_mean || !p->save_invstd || !p->workspace || ((uintptr_t)p->workspace & 255))
+    return pna_set_error(PNA_E_INVALID, who);
+  for (int t = 0; t < T; ++t)
+    if (!p->w_pre[t] || !p->b_pre[t] || !p->w_post[t] || !p->b_post[t] || (p->gamma[t] == nullptr) != (p->beta[t] == nullptr) ||
+        (p->gamma[t] == nullptr) != (p->gamma[0] == nullptr) || (p->running_mean[t] == nullptr) != (p->running_var[t] == nullptr))
+      return pna_set_error(PNA_E_INVALID, who);
+  if (!bwd && (!p->out || p->ld_out < C)) return pna_set_error(PNA_E_INVALID, who);
+  if (bwd) {
+    if (!p->grad_out || p->ld_go < C || !p->grad_h || !p->grad_w_mix || !p->grad_b_mix || !p->col_t || !p->rank_t || !p->items_t || p->n_items_t != p->V)
+      return pna_set_error(PNA_E_INVALID, who);
+    for (int t = 0; t < T; ++t)
+      if (!p->grad_w_pre[t] || !p->grad_b_pre[t] || !p->grad_w_post[t] || !p->grad_b_post[t] || (p->gamma[t] && (!p->grad_gamma[t] || !p->grad_beta[t])))
+        return pna_set_error(PNA_E_INVALID, who);
+  }
+  l = layout_of(p->V, T, Fi, Fo, S);
+  if (p->workspace_bytes < l.total * 4) return pna_set_error(PNA_E_INVALID, who);
+  memset(&g, 0, sizeof(g));
+  float* const ws = (float*)p->workspace;
+  g.rowptr = p->rowptr; g.col = p->col; g.V = p->V; g.T = T; g.Fi = Fi; g.Fo = Fo; g.S = S; g.C = C; g.TFi = T * Fi;
+  g.div = p->divide_input; g.residual = p->residual != 0;
+  g.h = p->h; g.ldh = (long)p->ldh; g.snorm = p->snorm_n;
+  for (int s = 0; s < 3; ++s) g.scale[s] = s < S ? p->row_scale[s] : nullptr;
+  for (int t = 0; t < T; ++t) {
+    g.w_pre[t] = p->w_pre[t]; g.b_pre[t] = p->b_pre[t]; g.w_post[t] = p->w_post[t]; g.b_post[t] = p->b_post[t];
+    g.gamma[t] = p->gamma[t]; g.beta[t] = p->beta[t]; g.rmean[t] = p->running_mean[t]; g.rvar[t] = p->running_var[t];
+    g.ggamma[t] = p->grad_gamma[t]; g.gbeta[t] = p->grad_beta[t];
+  }
+  g.w_mix = p->w_mix; g.b_mix = p->b_mix; g.slope = p->slope; g.eps = p->eps; g.momentum = p->momentum;
+  g.xcat = p->x_cat; g.a = p->a; g.amx = p->argmax; g.amn = p->argmin; g.z = p->z; g.p = p->p; g.mean = p->save_mean; g.invstd = p->save_invstd;
+  g.out = p->out; g.ld_out = (long)p->ld_out; g.go = p->grad_out; g.ld_go = (long)p->ld_go;
+  g.part = ws + (bwd ? l.part_bwd : l.part_fwd); g.n_part = l.n_tile;
+  g.cm = ws + l.cm; g.gp = ws + l.gp; g.hcat = ws + l.hcat; g.ghc = ws + l.ghc; g.gz = ws + l.gz; g.gagg = ws + l.gagg;
+  g.gxs = ws + l.gxs; g.gxd = ws + l.gxd; g.gh = p->grad_h;
+  return PNA_OK;
+}
+
+// gw (N, ldw) [+ gb] = gy^T [h | scale_s a]: pna_posttrans_dw_f32's kernel where its shape limits hold (and the first scaler is the
+// identity when it forms an h panel or a bias), the plain fp32 kernel otherwise
+int weight_grad(const float* gy, int64_t ldg, int N, const float* a, int64_t lda, int K, const float* h, int64_t ldh, int Kh, int S,
+                const float* const* scale, int64_t V, float* gw, int64_t ldw, float* gb, void* ws, int64_t ws_bytes, hipStream_t st) {
+  if (dw_takes(N, S, K, Kh) && !(scale && scale[0])) {
+    pna_posttrans_dw_args d;
+    memset(&d, 0, sizeof(d));
+    d.struct_size = (uint32_t)sizeof(d);
+    d.gy = gy; d.ldg = ldg; d.M = V; d.N = N; d.n_scaler = S; d.a = a; d.lda = lda; d.K = K; d.Kh = Kh; d.h = h; d.ldh = ldh;
+    for (int s = 0; s < S; ++s) d.row_scale[s] = scale ? scale[s] : nullptr;
+    d.grad_w = gw; d.ldw = ldw; d.grad_b = gb;
+    d.workspace = ws; d.workspace_bytes = ws_bytes;
+    return pna_posttrans_dw_f32(&d, (pna_stream_t)st);
+  }
+  const dim3 bd(256);
+  if (Kh > 0) {
+    const long n = (long)N * Kh;
+    hipLaunchKernelGGL(k_tt_dw_plain, dim3((unsigned)((n + 255) / 256)), bd, 0, st, gy, (long)ldg, N, h, (long)ldh, Kh, (const float*)nullptr, (int)V, gw, (long)ldw, gb);
+  }
+  const long n = (long)N * K;
+  for (int s = 0; s < S; ++s)
+    hipLaunchKernelGGL(k_tt_dw_plain, dim3((unsigned)((n + 255) / 256)), bd, 0, st, gy, (long)ldg, N, a, (long)lda, K, scale ? scale[s] : (const float*)nullptr, (int)V,
+                       gw + Kh + (size_t)s * K, (long)ldw, (Kh == 0 && s == 0) ? gb : (float*)nullptr);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_bwd_f32: launch failed");
+  return PNA_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t pna_tower_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input) {
+  if (!in_scope(V, E, n_tower, Fi, Fo, n_scaler, divide_input)) return -1;
+  return layout_of(V, n_tower, Fi, Fo, n_scaler).total * 4;
+}
+
+extern "C" int pna_tower_train_fwd_f32(const pna_tower_train_args* p, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill(p, g, l, false, "pna_tower_train_fwd_f32: needs V >= 2, 1 <= n_tower <= 8, 4 <= Fi <= 128, n_tower Fi <= 512, 1 <= Fo, n_tower Fo <= 128, "
+                                      "1 <= n_scaler <= 3, divide_input 0 / 1 (a residual: in_dim == n_tower Fo), rowptr / col, h (ld >= in_dim), every tower's "
+                                      "w_pre / b_pre / w_post / b_post, gamma and beta together (all towers or none), running_mean and running_var together, w_mix, "
+                                      "the saved tensors x_cat / a / argmax / argmin / z / p / save_mean / save_invstd, out (ld >= n_tower Fo), a 256-byte aligned "
+                                      "workspace of pna_tower_train_workspace_bytes(V, E, n_tower, Fi, Fo, n_scaler, divide_input)");
+  if (rc != PNA_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int Fi = g.Fi, C = g.C, in_dim = g.div ? g.TFi : Fi;
+  const dim3 grid((unsigned)l.n_tile), block(kThreads);
+  hipLaunchKernelGGL(k_tt_project, grid, block, (size_t)kRows * (in_dim + 1) * sizeof(float), st, g);                   // <= 33 KB
+  const size_t lds = ((size_t)kRows * pitch_of(quads(4 * Fi)) + (size_t)kRows * pitch_of(quads(Fi)) + (size_t)kRows * (C + 1) + 4 * kRows) * sizeof(float);   // <= 50 KB
+  if (g.S == 1) hipLaunchKernelGGL(k_tt_rows_fwd<1>, grid, block, lds, st, g);
+  else if (g.S == 2) hipLaunchKernelGGL(k_tt_rows_fwd<2>, grid, block, lds, st, g);
+  else hipLaunchKernelGGL(k_tt_rows_fwd<3>, grid, block, lds, st, g);
+  hipLaunchKernelGGL(k_tt_bn_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
+  hipLaunchKernelGGL(k_tt_mix_fwd, grid, block, (size_t)kRows * pitch_of(quads(C)) * sizeof(float), st, g);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_fwd_f32: launch failed");
+  return PNA_OK;
+}
+
+extern "C" int pna_tower_train_bwd_f32(const pna_tower_train_args* p, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill(p, g, l, true, "pna_tower_train_bwd_f32: needs the forward's arguments and saved tensors, grad_out (ld >= n_tower Fo), grad_h, every tower's "
+                                     "grad_w_pre / grad_b_pre / grad_w_post / grad_b_post (grad_gamma / grad_beta where it has gamma), grad_w_mix / grad_b_mix, the "
+                                     "transposed graph (col_t, rank_t, one whole-row record per source row in items_t: n_items_t == V) and the forward's workspace size");
+  if (rc != PNA_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int T = g.T, Fi = g.Fi, Fo = g.Fo, S = g.S, C = g.C, TFi = g.TFi, K = 4 * Fi;
+  const dim3 grid((unsigned)l.n_tile), block(kThreads);
+  // 1. the mixing network, 2. the column sums, 3. gz and the aggregate's gradient
+  hipLaunchKernelGGL(k_tt_mix_bwd, grid, block, ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float), st, g);
+  hipLaunchKernelGGL(k_tt_bwd_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
+  const size_t lds = ((size_t)T * kRows * pitch_of(quads(Fo)) + 4 * kRows) * sizeof(float);
+  if (S == 1) hipLaunchKernelGGL(k_tt_rows_bwd<1>, grid, block, lds, st, g);
+  else if (S == 2) hipLaunchKernelGGL(k_tt_rows_bwd<2>, grid, block, lds, st, g);
+  else hipLaunchKernelGGL(k_tt_rows_bwd<3>, grid, block, lds, st, g);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_bwd_f32: launch failed");
+  // 4. rowprep + ranked pull over the transposed graph, all towers: gx_src; rowprep's grad_dst is gx_dst
+  float* const ws = (float*)p->workspace;
+  pna_segreduce_bwd_args b;
+  memset(&b, 0, sizeof(b));
+  b.struct_size = (uint32_t)sizeof(b);
+  b.rowptr = p->rowptr; b.col = p->col; b.V = p->V; b.F = Fi;
+  b.x = p->x_cat; b.ldx = 2 * (int64_t)TFi;
+  b.dst_term = p->x_cat + TFi; b.ld_dst = 2 * (int64_t)TFi;
+  b.n_tower = T; b.n_aggr = 4; b.tower_stride_in = Fi;
+  b.aggr[0] = PNA_AGG_MEAN; b.aggr[1] = PNA_AGG_MAX; b.aggr[2] = PNA_AGG_MIN; b.aggr[3] = PNA_AGG_STD;
+  b.gagg = g.gagg; b.ld_g = (int64_t)T * K; b.tower_stride_g = K;
+  b.mean = p->a; b.stdv = p->a + 3 * (size_t)Fi; b.ld_stat = (int64_t)T * K; b.tower_stride_stat = K;
+  b.argmax = p->argmax; b.argmin = p->argmin; b.ld_arg = TFi;
+  b.grad_x = g.gxs; b.ld_gx = TFi;
+  b.grad_dst = g.gxd; b.ld_gd = TFi;
+  pna_segreduce_bwd_pull_args q;
+  memset(&q, 0, sizeof(q));
+  q.struct_size = (uint32_t)sizeof(q);
+  float* const packed = ws + l.packed;
+  q.base = &b; q.table = packed; q.ld_table = l.pitch;
+  q.col_t = p->col_t; q.rank_t = p->rank_t; q.items_t = p->items_t; q.n_items_t = p->n_items_t; q.run_rowprep = 1;
+  q.ranks = (uint16_t*)(packed + 4 * (size_t)TFi); q.ld_rank = 2 * l.pitch;
+  int rc2 = pna_segreduce_bwd_pull_launch(&q, nullptr, 0, stream);
+  if (rc2 != PNA_OK) return rc2;
+  // 5. grad_h
+  hipLaunchKernelGGL(k_tt_grad_h, grid, block, (size_t)kRows * pitch_of(quads(Fo + 2 * Fi)) * sizeof(float), st, g);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_bwd_f32: launch failed");
+  // 6. the weight and bias gradients, tower by tower, then the mixing network's
+  void* const dws = ws + l.dw;
+  for (int t = 0; t < T; ++t) {
+    const float* const ht = p->h + (g.div ? t * Fi : 0);
+    rc2 = weight_grad(g.gz + t * Fo, C, Fo, p->a + (size_t)t * K, (int64_t)T * K, K, ht, p->ldh, Fi, S, p->row_scale, p->V, p->grad_w_post[t], (int64_t)(1 + 4 * S) * Fi,
+                      p->grad_b_post[t], dws, l.dw_bytes, st);
+    if (rc2 != PNA_OK) return rc2;
+    rc2 = weight_grad(g.gxs + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t], 2 * (int64_t)Fi, nullptr, dws, l.dw_bytes, st);
+    if (rc2 != PNA_OK) return rc2;
+    rc2 = weight_grad(g.gxd + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t] + Fi, 2 * (int64_t)Fi, p->grad_b_pre[t], dws, l.dw_bytes, st);
+    if (rc2 != PNA_OK) return rc2;
+  }
+  return weight_grad(g.gp, C, C, g.hcat, C, C, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_mix, C, p->grad_b_mix, dws, l.dw_bytes, st);
+}

@@ -378,6 +378,50 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
         """Whether this call is served by the bf16 inference kernels: see _bf16_towers_path."""
         return _bf16_towers_path(self, list(self.towers), self.mixing_network, graph, h, e, self.out_dim)
 
+    def _small_tower_train_path(self, graph, h, snorm_n=None):
+        """Whether this call is served by pna_tower_train_fwd_f32 / _bwd_f32 (autograd.TowerLayerSmallTrainFn: the training forward and
+        the backward as one C call each): the knob PNA_AMD_SMALL_TOWER_TRAIN_ROWS is on and covers the batch; the layer, every tower and
+        every tower's BatchNorm train; fp32 features on the GPU, a whole graph, a gradient is wanted; and the structure is inside the
+        calls' scope -- 1..8 towers without edge features, 1-layer pretrans and posttrans (plain Linear), mean max min std, 1..3 scalers,
+        batch_norm with the default running statistics and one eps and momentum for all towers, graph_norm the same for every tower, no dropout inside the towers, a mixing
+        network that is Linear + LeakyReLU without batch-norm or active dropout, widths pna_amd.functional.small_tower_train_fits
+        accepts, at least 2 rows, in-degrees below 65535, snorm_n (V, 1) or (V,) fp32 when graph_norm is on."""
+        V = h.shape[0]
+        if not (PF.SMALL_TOWER_TRAIN_ROWS > 0 and 0 < V <= PF.SMALL_TOWER_TRAIN_ROWS):
+            return False
+        towers = list(self._modules["towers"]._modules.values())
+        t0, mix = towers[0], self.mixing_network
+        if not (self.training and not self.edge_features and h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and type(graph) is Graph
+                and graph.num_nodes == V and V >= 2 and h.shape[1] == self.in_dim):
+            return False
+        if not (tuple(t0.aggregators) == ("mean", "max", "min", "std") and 1 <= len(t0.scalers) <= 3
+                and PF.small_tower_train_fits(len(towers), self.input_tower, self.output_tower, len(t0.scalers))):
+            return False
+        for t in towers:
+            bn = t.batchnorm_h
+            if not (t.training and bn.training and t.batch_norm and not t.edge_features and t.dropout == 0 and t.graph_norm == t0.graph_norm
+                    and tuple(t.aggregators) == tuple(t0.aggregators) and tuple(t.scalers) == tuple(t0.scalers)
+                    and len(t.pretrans.fully_connected) == 1 and len(t.posttrans.fully_connected) == 1):
+                return False
+            for fc in (t.pretrans.fully_connected[0], t.posttrans.fully_connected[0]):
+                if fc.activation is not None or fc.b_norm is not None or fc.linear.bias is None or (fc.dropout is not None and fc.dropout.p > 0):
+                    return False
+            if not (bn.track_running_stats and bn.momentum is not None and bn.running_mean is not None and (bn.weight is None) == (bn.bias is None)
+                    and (bn.weight is None) == (t0.batchnorm_h.weight is None) and bn.eps == t0.batchnorm_h.eps
+                    and bn.momentum == t0.batchnorm_h.momentum):             # (the calls carry one eps and one momentum)
+                return False
+        if not (isinstance(mix.activation, nn.LeakyReLU) and mix.b_norm is None and (mix.dropout is None or mix.dropout.p == 0)
+                and mix.training == self.training):
+            return False
+        if t0.graph_norm and (snorm_n is None or not (snorm_n.is_cuda and snorm_n.dtype == torch.float32 and snorm_n.numel() == V)):
+            return False
+        for t in list(self.parameters()) + list(self.buffers()):
+            if t.is_floating_point() and (t.dtype != torch.float32 or not t.is_cuda):
+                return False
+        if not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return False
+        return graph.csr.max_degree < 65535
+
     def forward(self, g, h, e, snorm_n):
         graph = as_graph(g)
         if self._bf16_path(graph, h, e):
@@ -427,6 +471,11 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
                 x_cat = PF.linear_act(h, Wcat, bcat)
                 x_src, x_dst = x_cat[:, :T * Fi], x_cat[:, T * Fi:]
             return PF.tower_layer_degree_grouped(self, graph, h, snorm_n, x_src, x_dst)
+        if PF.SMALL_TOWER_TRAIN_ROWS > 0 and self._small_tower_train_path(graph, h, snorm_n):
+            # training on a molecule batch: the layer's forward as one C call, its backward as another (autograd.TowerLayerSmallTrainFn)
+            from .. import autograd as AG
+            t0 = self.towers[0]
+            return AG.tower_layer_small_train(self, graph, h, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
         h_cat = _towers_forward(list(self.towers), graph, h, e, snorm_n, self.divide_input)
         mix = self.mixing_network
         if (h_cat.shape[1] >= 4 and isinstance(mix.activation, nn.LeakyReLU) and mix.b_norm is None and (mix.dropout is None or not self.training)

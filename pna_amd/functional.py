@@ -1198,6 +1198,18 @@ def small_train_fits(F, N):
     return 4 * (16 * (quads(4 * F) * 16 + 4) + 16 * (quads(N) * 16 + 1) + 48) <= 160 * 1024
 
 
+# PNALayer TRAINING batches up to this many nodes take the one-call route (autograd.TowerLayerSmallTrainFn:
+# pna_tower_train_fwd_f32 / _bwd_f32).  0 = off, the default
+SMALL_TOWER_TRAIN_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_ROWS", "0"))
+
+
+def small_tower_train_fits(T, Fi, Fo, S=3):
+    """Mirror of pna_tower_train_fwd_f32's scope: 1 <= T <= 8 towers, 4 <= Fi <= 128 (a lane of the gather owns two columns), T Fi <= 512,
+    1 <= Fo, T Fo <= 128, 1 <= S <= 3 scalers -- the widest tile set (one tower's 16 x 4 Fi aggregate, its 16 x Fi input slice, the
+    16 x T Fo output) is 50 KB of the CU's 160 KB."""
+    return 1 <= T <= 8 and 4 <= Fi <= 128 and T * Fi <= 512 and 1 <= Fo and T * Fo <= 128 and 1 <= S <= 3
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")
