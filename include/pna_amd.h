@@ -29,6 +29,9 @@ extern "C" {
 #define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_train_fwd_f32 / pna_tower_train_bwd_f32 / pna_tower_train_workspace_bytes /
                                   pna_tower_train_args, PNA_MAX_TOWER (PNALayer's TRAINING forward and backward on molecule batches, one call
                                   each); no existing struct or entry point changed.
+                                  23, additive: + pna_tower_edge_train_fwd_f32 / pna_tower_edge_train_bwd_f32 / pna_tower_edge_train_workspace_bytes /
+                                  pna_tower_edge_train_args (the same with per-edge features, edge_features=True: grad_e returned); no existing
+                                  struct or entry point changed.
                                   23, additive: + pna_simple_train_fwd_f32 / pna_simple_train_bwd_f32 / pna_simple_train_workspace_bytes /
                                   pna_simple_train_args (PNASimpleLayer's TRAINING forward and backward on molecule batches, one call each);
                                   no existing struct or entry point changed.
@@ -1530,6 +1533,49 @@ typedef struct pna_tower_train_args {
 int64_t pna_tower_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input);
 int pna_tower_train_fwd_f32(const pna_tower_train_args* args, pna_stream_t stream);
 int pna_tower_train_bwd_f32(const pna_tower_train_args* args, pna_stream_t stream);
+
+/* ---- PNALayer TRAINING with EDGE FEATURES on molecule batches: forward and backward as ONE call each ----------------------------
+ * replaces: models/dgl/pna_layer.py:35-40 (pretrans_edges with edge_features: the pretrans on [h_u | h_v | ef]), :55-76 and :130-145 in
+ * train mode, and what autograd derives from them in loss.backward() (realworld_benchmark/train/train_molecules_graph_regression.py:
+ * 29-32), the gradient of the edge features included (nets/molecules_graph_regression/pna_net.py:72-73: e = embedding_e(bond type));
+ * the ZINC configuration of realworld_benchmark/README.md:62 (--edge_feat=True --edge_dim=50, 5 towers, hidden 70, out 60).
+ *
+ * The message of CSR edge k = (u -> v) is (W_a h_u + (W_b h_v + b)) + W_e e[eid[k]] -- pna_segreduce_fwd_f32's order with dst_term and
+ * edge_term.  Scope: that of pna_tower_train_*_f32 (`base`), and 1 <= edge_dim <= 64.  Differences to the base call: w_pre[t] and
+ * grad_w_pre[t] are (Fi, 2 Fi + edge_dim) = [W_a | W_b | W_e], contiguous; the workspace has
+ * pna_tower_edge_train_workspace_bytes(...) bytes; col_t / rank_t are not read (the pull reads pos_t).  NO float atomics, fixed
+ * summation orders: repeated calls give identical bits, grad_e included.  E == 0: both calls succeed, launch no zero-sized grid, the
+ * W_e block of grad_w_pre is zero.
+ *
+ * pna_tower_edge_train_fwd_f32 (five launches): the base forward with, after its projection, x_edge (E, T Fi) = W_e,t e[eid[k]] per 16
+ *   CSR edges on exact fp32 MFMAs (saved); the rows launch takes mean | max | min and the arg indices (absolute CSR positions, the first
+ *   extremal edge wins) of the message above -- for in-degrees <= 128 pna_segreduce_fwd_f32's bits with x = x_src, dst_term = x_dst,
+ *   edge_term = x_edge -- and the std of x_src[u] + x_edge[k] WITHOUT x_dst (that call's bits without dst_term).
+ * pna_tower_edge_train_bwd_f32: the base backward with rowprep + the ranked pull replaced by
+ *   dm[k] = G_mean[v] / D + [std^2 - 1e-5 > 0] G_std[v] / (std[v] D) ((x_src[u] + x_edge[k]) - (mean[v] - x_dst[v]))
+ *           + [k = argmax[v]] G_max[v] + [k = argmin[v]] G_min[v]                  per edge, in CSR order, to the workspace,
+ *   gx_dst[v] = G_mean + G_max + G_min (0 for a row without in-edges), gx_src[u] = sum of dm[pos_t[j]] over the whole-row record of u in
+ *   items_t in list order, grad_e[eid[k]] = sum_t dm_t[k] W_e,t (when grad_e != NULL; every row written exactly once) and one more
+ *   weight gradient per tower, grad_W_e,t = dm_t^T e[eid] over the E edges, into columns [2 Fi, 2 Fi + edge_dim) of grad_w_pre[t]. */
+typedef struct pna_tower_edge_train_args {
+  uint32_t struct_size;    /* sizeof(pna_tower_edge_train_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const pna_tower_train_args* base;  /* everything pna_tower_train_*_f32 takes, with the differences above */
+  int32_t edge_dim;        /* 1 <= edge_dim <= 64 */
+  int32_t _pad0;
+  const float* e;          /* (E, ld_e >= edge_dim), ORIGINAL edge order (may be NULL when E == 0) */
+  int64_t ld_e;
+  const int32_t* eid;      /* [E] original edge id of CSR edge k (a permutation) */
+  float* x_edge;           /* saved (E, T Fi) contiguous, CSR order: x_edge,t[k] = W_e,t e[eid[k]]; forward writes, backward reads */
+  const int32_t* pos_t;    /* backward: [E] position in the forward CSR of transposed edge j */
+  float* grad_e;           /* backward (E, ld_ge >= edge_dim), original edge order; NULL = not wanted */
+  int64_t ld_ge;
+} pna_tower_edge_train_args;
+
+int64_t pna_tower_edge_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input,
+                                             int32_t edge_dim);   /* -1 outside the scope */
+int pna_tower_edge_train_fwd_f32(const pna_tower_edge_train_args* args, pna_stream_t stream);
+int pna_tower_edge_train_bwd_f32(const pna_tower_edge_train_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

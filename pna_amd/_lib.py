@@ -355,6 +355,14 @@ class PnaTowerTrainArgs(_Args):
     ]
 
 
+class PnaTowerEdgeTrainArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32), ("base", ctypes.c_void_p), ("edge_dim", ctypes.c_int32),
+        ("_pad0", ctypes.c_int32), ("e", ctypes.c_void_p), ("ld_e", ctypes.c_int64), ("eid", ctypes.c_void_p), ("x_edge", ctypes.c_void_p),
+        ("pos_t", ctypes.c_void_p), ("grad_e", ctypes.c_void_p), ("ld_ge", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -503,6 +511,11 @@ def lib():
         L.pna_tower_train_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_tower_train_fwd_f32, L.pna_tower_train_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaTowerTrainArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_tower_edge_train_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 6
+        L.pna_tower_edge_train_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_tower_edge_train_fwd_f32, L.pna_tower_edge_train_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaTowerEdgeTrainArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")

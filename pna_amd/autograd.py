@@ -819,13 +819,24 @@ def simple_layer_small_train(layer, graph, h, scales):
 class _TowerTrainPlan:
     """What one call of TowerLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays and the call's
     workspace (Graph.workspace: every launch writes what it reads, nothing is carried from the forward to the backward).  Nothing here
-    depends on weight values.  One caller at a time per Graph."""
+    depends on weight values.  One caller at a time per Graph.  edge_dim > 0: the plan of TowerLayerEdgeSmallTrainFn
+    (pna_tower_edge_train_*_f32) -- its larger workspace, the int32 edge ids and the transposed edges' CSR positions (both kept on the
+    graph), x_edge in the saved state."""
 
-    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev):
+    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev, edge_dim=0):
         V, E = graph.num_nodes, int(graph.csr.col.numel())
         self.V, self.E, self.T, self.Fi, self.Fo, self.S, self.div, self.dev = V, E, T, Fi, Fo, S, bool(divide_input), dev
+        self.edge_dim = int(edge_dim)
         self.col_t, self.rank_t, self.items_t = _transposed_whole_rows(graph)
-        nbytes = _lib.lib().pna_tower_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div))
+        if self.edge_dim:
+            nbytes = _lib.lib().pna_tower_edge_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div), self.edge_dim)
+            self.eid = graph.edge_ids32()
+            gT = graph._pna_amd_transposed
+            self.pos_t = getattr(gT, "_pna_amd_pos_t", None)      # position of every transposed edge in the forward CSR
+            if self.pos_t is None:
+                self.pos_t = gT._pna_amd_pos_t = gT.csr.eid.to(torch.int32).contiguous()
+        else:
+            nbytes = _lib.lib().pna_tower_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div))
         if nbytes < 0:
             raise RuntimeError("TowerLayerSmallTrainFn: shape outside pna_tower_train_*_f32 (the layer checks it before taking this path)")
         ws = graph.workspace(nbytes + 256)
@@ -837,7 +848,7 @@ class _TowerTrainPlan:
         save_invstd [C] in one buffer, argmax | argmin (V, T Fi) in another.  Per CALL, not per plan: two layers of one shape on one
         graph are both alive until their backwards."""
         V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
-        fbuf = torch.empty(V * 6 * TFi + 2 * V * C + 2 * C, dtype=torch.float32, device=self.dev)
+        fbuf = torch.empty(V * 6 * TFi + 2 * V * C + 2 * C + (self.E * TFi if self.edge_dim else 0), dtype=torch.float32, device=self.dev)
         ibuf = torch.empty(2, V, TFi, dtype=torch.int32, device=self.dev)
         return fbuf, ibuf
 
@@ -851,6 +862,27 @@ class _TowerTrainPlan:
             parts.append(fbuf[o:o + n])
             o += n
         return (parts[0].view(V, 2 * TFi), parts[1].view(V, 4 * TFi), parts[2].view(V, C), parts[3].view(V, C), parts[4].view(2, C), ibuf[0], ibuf[1])
+
+    def x_edge(self, saved):
+        """The (E, T Fi) x_edge of an edge plan's saved state (behind the pieces views() returns)."""
+        V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
+        o = V * 6 * TFi + 2 * V * C + 2 * C
+        return saved[0][o:o + self.E * TFi].view(self.E, TFi)
+
+    def edge_args(self, base, e, saved, grad_e=None, backward=False):
+        """The pna_tower_edge_train_args around `base` (args() of this plan, set_backward() applied for a backward)."""
+        q = _lib.PnaTowerEdgeTrainArgs()
+        q.base = ctypes.cast(ctypes.pointer(base), ctypes.c_void_p)
+        q.edge_dim = self.edge_dim
+        if self.E:
+            q.e, q.ld_e = _lib.dev_ptr(e, torch.float32, "e"), e.stride(0)
+            q.eid = _lib.dev_ptr(self.eid, torch.int32, "eid")
+            q.x_edge = self.x_edge(saved).data_ptr()
+            if backward:
+                q.pos_t = _lib.dev_ptr(self.pos_t, torch.int32, "pos_t")
+        if grad_e is not None:
+            q.grad_e, q.ld_ge = _lib.dev_ptr(grad_e, torch.float32, "grad_e"), max(grad_e.stride(0), self.edge_dim)
+        return q
 
     def args(self, graph, h, snorm, scales, towers, mix_w, mix_b, slope, residual, saved):
         """towers: per tower (w_pre, b_pre, w_post, b_post, gamma, beta, running_mean, running_var, eps, momentum)."""
@@ -982,3 +1014,81 @@ def tower_layer_small_train(layer, graph, h, snorm_n, scales):
         snorm = snorm_n.reshape(-1)
         snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
     return TowerLayerSmallTrainFn.apply(h, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)
+
+
+class TowerLayerEdgeSmallTrainFn(torch.autograd.Function):
+    """TowerLayerSmallTrainFn for a PNALayer with edge features (models/dgl/pna_layer.py:35-40: the pretrans on [h_u | h_v | ef]): the
+    training forward as ONE C call (pna_tower_edge_train_fwd_f32) and the backward as one (pna_tower_edge_train_bwd_f32).  `e` (E,
+    edge_dim), in the graph's original edge order, is an input: its gradient comes back when it needs one.  `params` as in
+    TowerLayerSmallTrainFn; a tower's pretrans weight is (Fi, 2 Fi + edge_dim)."""
+
+    @staticmethod
+    def forward(ctx, h, e, layer, graph, scales, snorm, *params):
+        T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
+        dev = h.device
+        x = h if h.stride(1) == 1 else h.contiguous()
+        ef = e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous()
+        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=layer.towers[0].edge_dim)
+        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
+        saved = plan.new_saved()
+        mix = layer.mixing_network
+        slope = mix.activation.negative_slope
+        a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer), mix.linear.weight, mix.linear.bias, slope, layer.residual, saved)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        q = plan.edge_args(a, ef, saved)
+        _lib.check(_lib.lib().pna_tower_edge_train_fwd_f32(ctypes.byref(q), _lib.stream_ptr(dev)), "pna_tower_edge_train_fwd_f32")
+        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope = plan, graph, layer, scales, snorm, saved, slope
+        ctx.save_for_backward(x, ef, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, ef, *params = ctx.saved_tensors
+        plan, layer = ctx.plan, ctx.layer
+        T, Fi, Fo, S, ed = plan.T, plan.Fi, plan.Fo, plan.S, plan.edge_dim
+        C = T * Fo
+        dev = x.device
+        go = go if go.stride(1) == 1 else go.contiguous()
+        need = ctx.needs_input_grad
+        g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
+        g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if need[1] else None
+        g_wpre = torch.empty(T, Fi, 2 * Fi + ed, dtype=torch.float32, device=dev)
+        g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
+        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
+        g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
+        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
+        towers = []
+        for t in range(T):
+            w_pre, b_pre, w_post, b_post, gamma, beta = params[6 * t:6 * t + 6]
+            bn = layer.towers[t].batchnorm_h
+            towers.append((w_pre, b_pre, w_post, b_post, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
+        mix_w, mix_b = params[6 * T], params[6 * T + 1]
+        a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, towers, mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
+        has_affine = towers[0][4] is not None
+        grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
+                 for t in range(T)]
+        plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
+        q = plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True)
+        _lib.check(_lib.lib().pna_tower_edge_train_bwd_f32(ctypes.byref(q), _lib.stream_ptr(dev)), "pna_tower_edge_train_bwd_f32")
+        res = [g_h if need[0] else None, g_e, None, None, None, None]
+        for t in range(T):
+            res += [grads[t][0], grads[t][1], grads[t][2], grads[t][3], grads[t][4], grads[t][5]]
+        res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
+        return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
+
+
+def tower_layer_edge_small_train(layer, graph, h, e, snorm_n, scales):
+    """tower_layer_small_train for a layer with edge features, through TowerLayerEdgeSmallTrainFn; every tower's num_batches_tracked
+    advances like the module's own forward."""
+    params = []
+    for t in layer.towers:
+        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        params += [pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias]
+    mix = layer.mixing_network.linear
+    snorm = None
+    if layer.towers[0].graph_norm:
+        snorm = snorm_n.reshape(-1)
+        snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
+    return TowerLayerEdgeSmallTrainFn.apply(h, e, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)

@@ -19,6 +19,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <string>
+
 #include "pna_amd.h"
 #include "pna_internal.h"
 #include "pna_rowstats.h"
@@ -35,6 +37,7 @@ constexpr int kMaxC = 128;       // out_dim = T Fo
 constexpr int kMaxFi = 128;      // a lane of the gather owns columns lane and lane + 64
 constexpr int kMaxIn = 512;      // T Fi
 constexpr int kEU = 4;           // edges of a row whose gathers are issued together
+constexpr int kMaxED = 64;       // edge_dim of the route with edge features: the edge tile's K
 
 struct KArgs {
   const int32_t* rowptr; const int32_t* col;
@@ -58,6 +61,14 @@ struct KArgs {
   float* gxs; float* gxd;                                   // backward (V, T Fi): the gradient of x_src, x_dst
   float* gh;                                                // backward (V, in_dim)
   float* ggamma[kMaxT]; float* gbeta[kMaxT];
+  long ldw_pre;                                             // row pitch of w_pre[t]: 2 Fi, 2 Fi + ED with edge features
+  // edge features (pna_tower_edge_train_*): message = (x_src[u] + x_dst[v]) + x_edge[k], x_edge,t[k] = W_e,t e[eid[k]]
+  int E, ED;
+  const float* e; long ld_e; const int32_t* eid;            // (E, ld_e) in ORIGINAL edge order; original id of CSR edge k
+  float* xedge;                                             // saved (E, T Fi), CSR order
+  const int32_t* pos_t; const int32_t* items_t;             // backward: CSR position of transposed edge j; {u, beg, end, -1} per source row
+  float* dm; float* ecsr;                                   // backward (E, T Fi) message gradient, (E, ED) copy of e, both in CSR order
+  float* ge; long ld_ge;                                    // backward (E, ld_ge), original edge order, or NULL
 };
 
 __device__ __forceinline__ float leaky(float p, float slope) { return p > 0.f ? p : p * slope; }
@@ -82,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_project(const KArgs g) {
     const int j = nt * 16 + li;                             // output column of the tower's [x_src | x_dst]
     const bool jok = j < 2 * Fi;
     const int half = j >= Fi ? 1 : 0, f = min(j - half * Fi, Fi - 1);
-    const float* const wrow = g.w_pre[t] + (size_t)f * 2 * Fi + half * Fi;
+    const float* const wrow = g.w_pre[t] + (size_t)f * g.ldw_pre + half * Fi;
     const float* const hrow = H + li * PH + (g.div ? t * Fi : 0);
     f4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int qd = 0; qd < Q; ++qd) {
@@ -109,8 +120,55 @@ __global__ __launch_bounds__(kThreads) void k_tt_project(const KArgs g) {
   }
 }
 
-// ---- forward, launch 2: per tower gather + reduce + contraction of 16 destination rows; the tile's BatchNorm partial sums --------
-template <int S>
+// ---- forward with edge features, launch 2: x_edge,t[k] = W_e,t e[eid[k]] of 16 CSR edges, all towers.  The rows e[eid[k]] go to an LDS
+// tile (zeros in the K padding and in the rows past E); the B fragments are scalar loads from the tower's own weight (the block
+// starts at column 2 Fi of a row of 2 Fi + ED floats: not 16-byte aligned) ----
+__global__ __launch_bounds__(kThreads) void k_tt_edge_project(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int Fi = g.Fi, T = g.T, TFi = g.TFi, ED = g.ED, Q = quads(ED), P = pitch_of(Q);
+  float* const EF = lds;                                    // [16][P] the edges' feature rows
+  const int k0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.E - k0);
+  for (int i = tid; i < kRows * P; i += kThreads) {
+    const int r = i / P, k = i - r * P;
+    EF[i] = (k < ED && r < nrows) ? g.e[(size_t)g.eid[k0 + r] * g.ld_e + k] : 0.f;
+  }
+  __syncthreads();
+  const int NT = (Fi + 15) / 16;
+  for (int u = wave; u < T * NT; u += kWaves) {
+    const int t = u / NT, nt = u - t * NT;
+    const int f = nt * 16 + li;                             // output column inside the tower
+    const bool fok = f < Fi;
+    const float* const wrow = g.w_pre[t] + (size_t)min(f, Fi - 1) * g.ldw_pre + 2 * Fi;
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int qd = 0; qd < Q; ++qd) {
+      const int k = 16 * qd + 4 * lg;
+      const f4 a = *reinterpret_cast<const f4*>(EF + li * P + k);
+      f4 b;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool ok = fok && k + i < ED;
+        const float wv = wrow[ok ? k + i : 0];
+        b[i] = ok ? wv : 0.f;
+      }
+      quad_fma(acc, a, b);
+    }
+    if (fok) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * lg + i;
+        if (r < nrows) g.xedge[(size_t)(k0 + r) * TFi + t * Fi + f] = acc[i];
+      }
+    }
+  }
+}
+
+// ---- forward, launch 2 (3 with edge features): per tower gather + reduce + contraction of 16 destination rows; the tile's BatchNorm
+// partial sums.  EDGE: the message is (x_src[u] + x_dst[v]) + x_edge[k] (pna_segreduce.hip's order with dst_term and edge_term) and
+// the std is that of x_src[u] + x_edge[k] ----
+template <int S, bool EDGE>
 __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -153,21 +211,34 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) dt[j] = xs[(size_t)row * 2 * TFi + TFi + cc[j]];
       for (int e = beg; e < end; e += kEU) {
-        float v[kEU][2];
+        float v[kEU][2], xe[kEU][2];
 #pragma unroll
         for (int u = 0; u < kEU; ++u) {
-          const size_t o = (size_t)g.col[min(e + u, end - 1)] * 2 * TFi;
+          const int k = min(e + u, end - 1);
+          const size_t o = (size_t)g.col[k] * 2 * TFi;
           v[u][0] = xs[o + cc[0]];
           v[u][1] = xs[o + cc[1]];
+          if constexpr (EDGE) {
+            const float* const xr = g.xedge + (size_t)k * TFi + t * Fi;
+            xe[u][0] = xr[cc[0]];
+            xe[u][1] = xr[cc[1]];
+          }
         }
 #pragma unroll
         for (int u = 0; u < kEU; ++u)
           if (e + u < end) {                                // (wavefront-uniform)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-              fold_msg(v[u][j] + dt[j], e + u, s[j], q[j], mx[j], mn[j], ax[j], an[j]);
-              s0[j] = s0[j] + v[u][j];
-              q0[j] = q0[j] + v[u][j] * v[u][j];
+              if constexpr (EDGE) {
+                const float m0 = v[u][j] + xe[u][j];        // the std's message: no destination term
+                fold_msg((v[u][j] + dt[j]) + xe[u][j], e + u, s[j], q[j], mx[j], mn[j], ax[j], an[j]);
+                s0[j] = s0[j] + m0;
+                q0[j] = q0[j] + m0 * m0;
+              } else {
+                fold_msg(v[u][j] + dt[j], e + u, s[j], q[j], mx[j], mn[j], ax[j], an[j]);
+                s0[j] = s0[j] + v[u][j];
+                q0[j] = q0[j] + v[u][j] * v[u][j];
+              }
             }
           }
       }
@@ -528,8 +599,8 @@ __global__ __launch_bounds__(kThreads) void k_tt_grad_h(const KArgs g) {
           const int kk = min(k + i, KK - 1);
           float wv;
           if (kk < Fo) wv = wpost[(size_t)kk * ldpost];
-          else if (kk < Fo + Fi) wv = wpre[(size_t)(kk - Fo) * 2 * Fi + ii];
-          else wv = wpre[(size_t)(kk - Fo - Fi) * 2 * Fi + Fi + ii];
+          else if (kk < Fo + Fi) wv = wpre[(size_t)(kk - Fo) * g.ldw_pre + ii];
+          else wv = wpre[(size_t)(kk - Fo - Fi) * g.ldw_pre + Fi + ii];
           b[i] = (iok && k + i < KK) ? wv : 0.f;
         }
         quad_fma(acc, a, b);
@@ -548,6 +619,134 @@ __global__ __launch_bounds__(kThreads) void k_tt_grad_h(const KArgs g) {
         }
         acc = (f4){0.f, 0.f, 0.f, 0.f};
       }
+    }
+  }
+}
+
+// ---- backward with edge features, after the rows kernel: the message gradient per edge, destination row by destination row over the
+// FORWARD CSR (a wavefront owns rows wave, wave + 8; a lane owns columns lane and lane + 64 of a tower):
+//   dm[k] = G_mean[v] / D + [std^2 - 1e-5 > 0] G_std[v] / (std[v] D) ((x_src[u] + x_edge[k]) - (mean[v] - x_dst[v]))
+//           + [k = argmax[v]] G_max[v] + [k = argmin[v]] G_min[v]
+// gx_dst[v] = G_mean + G_max + G_min (the variance term sums to zero over a row; 0 for a row without in-edges), and the CSR-ordered
+// copy of e that the W_e weight gradient reads ----
+__global__ __launch_bounds__(kThreads) void k_tt_edge_dm(const KArgs g) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int Fi = g.Fi, T = g.T, TFi = g.TFi, K = 4 * Fi, ED = g.ED;
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  for (int r = wave; r < nrows; r += kWaves) {
+    const int row = r0 + r;
+    const int beg = g.rowptr[row], end = g.rowptr[row + 1], D = end - beg;
+    if (lane < ED)
+      for (int k = beg; k < end; ++k) g.ecsr[(size_t)k * ED + lane] = g.e[(size_t)g.eid[k] * g.ld_e + lane];
+    const float fD = (float)D, invD = D > 0 ? 1.0f / fD : 0.f;
+    for (int t = 0; t < T; ++t) {
+      const float* const xs = g.xcat + t * Fi;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j, cc = min(c, Fi - 1);   // (lanes past the last column redo it; not stored)
+        const bool ok = c < Fi;
+        if (j == 1 && Fi <= 64) continue;                   // (wavefront-uniform)
+        const size_t oa = (size_t)row * T * K + (size_t)t * K + cc;
+        const float Gm = g.gagg[oa], Gx = g.gagg[oa + Fi], Gn = g.gagg[oa + 2 * Fi], Gs = g.gagg[oa + 3 * Fi];
+        const float mean = g.a[oa], sd = g.a[oa + 3 * Fi];
+        const float xd = xs[(size_t)row * 2 * TFi + TFi + cc];
+        const int ax = g.amx[(size_t)row * TFi + t * Fi + cc], an = g.amn[(size_t)row * TFi + t * Fi + cc];
+        const float r1 = Gm * invD;
+        const float r2 = (D > 0 && sd * sd - 1e-5f > 0.f) ? Gs / (sd * fD) : 0.f;
+        const float sh = mean - xd;                         // the mean of x_src[u] + x_edge[k]
+        if (ok) g.gxd[(size_t)row * TFi + t * Fi + c] = D > 0 ? (Gm + Gx) + Gn : 0.f;
+        for (int e = beg; e < end; e += kEU) {
+          float m0[kEU];
+#pragma unroll
+          for (int u = 0; u < kEU; ++u) {
+            const int k = min(e + u, end - 1);
+            m0[u] = xs[(size_t)g.col[k] * 2 * TFi + cc] + g.xedge[(size_t)k * TFi + t * Fi + cc];
+          }
+#pragma unroll
+          for (int u = 0; u < kEU; ++u)
+            if (e + u < end) {                              // (wavefront-uniform)
+              const int k = e + u;
+              float d = r1 + r2 * (m0[u] - sh);
+              d = d + (k == ax ? Gx : 0.f);
+              d = d + (k == an ? Gn : 0.f);
+              if (ok) g.dm[(size_t)k * TFi + t * Fi + c] = d;
+            }
+        }
+      }
+    }
+  }
+}
+
+// ---- backward with edge features: gx_src[u] = sum of dm[pos_t[j]] over the source row's transposed edges in list order (one
+// whole-row record {u, beg, end, -1} per source row: no segments, no atomics); a wavefront owns records wave, wave + 8 of 16, a lane
+// one column of 64 at a time, four rows' loads in flight ----
+__global__ __launch_bounds__(kThreads) void k_tt_edge_pull(const KArgs g) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int TFi = g.TFi;
+  const int r0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.V - r0);
+  for (int r = wave; r < nrows; r += kWaves) {
+    const int32_t* const rec = g.items_t + 4 * (size_t)(r0 + r);
+    const int u = rec[0], beg = rec[1], end = rec[2];
+    for (int cb = 0; cb < TFi; cb += 64) {
+      const int c = cb + lane, cc = min(c, TFi - 1);
+      float acc = 0.f;
+      for (int j = beg; j < end; j += kEU) {
+        float v[kEU];
+#pragma unroll
+        for (int i = 0; i < kEU; ++i) v[i] = g.dm[(size_t)g.pos_t[min(j + i, end - 1)] * TFi + cc];
+#pragma unroll
+        for (int i = 0; i < kEU; ++i)
+          if (j + i < end) acc = acc + v[i];                // (wavefront-uniform)
+      }
+      if (c < TFi) g.gxs[(size_t)u * TFi + c] = acc;
+    }
+  }
+}
+
+// ---- backward with edge features, when grad_e is wanted: grad_e[eid[k]] = sum_t dm_t[k] W_e,t of 16 CSR edges; the accumulator is
+// kept across the towers; every row of grad_e is written exactly once, through the permutation ----
+__global__ __launch_bounds__(kThreads) void k_tt_edge_grad_e(const KArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int Fi = g.Fi, T = g.T, TFi = g.TFi, ED = g.ED, Q = quads(Fi), P = pitch_of(Q);
+  const int NTJ = (ED + 15) / 16;                           // <= 4: a wavefront owns at most one column tile
+  float* const A = lds;                                     // [16][P] one tower's dm rows
+  const int k0 = blockIdx.x * kRows;
+  const int nrows = min(kRows, g.E - k0);
+  const int j0 = wave * 16 + li;                            // this lane's column of e
+  const bool jok = wave < NTJ && j0 < ED;
+  const int jj = min(j0, ED - 1);
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < T; ++t) {
+    __syncthreads();
+    for (int i = tid; i < kRows * P; i += kThreads) {
+      const int r = i / P, k = i - r * P;
+      A[i] = (k < Fi && r < nrows) ? g.dm[(size_t)(k0 + r) * TFi + t * Fi + k] : 0.f;
+    }
+    __syncthreads();
+    if (wave < NTJ) {
+      const float* const w = g.w_pre[t] + 2 * Fi + jj;      // W_e,t[k][j]: row k of the pretrans weight, column 2 Fi + j
+      for (int qd = 0; qd < Q; ++qd) {
+        const int k = 16 * qd + 4 * lg;
+        const f4 a = *reinterpret_cast<const f4*>(A + li * P + k);
+        f4 b;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float wv = w[(size_t)min(k + i, Fi - 1) * g.ldw_pre];
+          b[i] = (jok && k + i < Fi) ? wv : 0.f;
+        }
+        quad_fma(acc, a, b);
+      }
+    }
+  }
+  if (jok) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * lg + i;
+      if (r < nrows) g.ge[(size_t)g.eid[k0 + r] * g.ld_ge + j0] = acc[i];
     }
   }
 }
@@ -572,7 +771,7 @@ __global__ __launch_bounds__(256) void k_tt_dw_plain(const float* gy, long ldg, 
 inline int64_t up64(int64_t floats) { return (floats + 63) / 64 * 64; }     // workspace pieces at 256-byte boundaries
 
 struct Layout {
-  int64_t part_fwd, part_bwd, cm, gp, hcat, ghc, gz, gagg, gxs, gxd, packed, dw, total;      // offsets in floats
+  int64_t part_fwd, part_bwd, cm, gp, hcat, ghc, gz, gagg, gxs, gxd, packed, dm, ecsr, dw, total;      // offsets in floats
   int64_t pitch, dw_bytes;
   int n_tile;
 };
@@ -588,7 +787,8 @@ bool in_scope(int64_t V, int64_t E, int T, int Fi, int Fo, int S, int div) {
 bool dw_takes(int N, int S, int K, int Kh) { return S * N <= 240 && K + Kh + 1 <= 384; }
 int64_t dw_bytes_of(int64_t V, int N, int S, int K, int Kh) { return dw_takes(N, S, K, Kh) ? (int64_t)240 * 384 * 4 * ((V + 255) / 256) : 0; }
 
-Layout layout_of(int64_t V, int T, int Fi, int Fo, int S) {
+// ED == 0: the route without edge features.  ED > 0: no packed rows (its pull reads dm), + dm (E, T Fi) and the CSR-ordered copy of e
+Layout layout_of(int64_t V, int T, int Fi, int Fo, int S, int64_t E = 0, int ED = 0) {
   Layout l;
   const int64_t C = (int64_t)T * Fo, TFi = (int64_t)T * Fi;
   l.n_tile = (int)((V + kRows - 1) / kRows);
@@ -604,16 +804,20 @@ Layout layout_of(int64_t V, int T, int Fi, int Fo, int S) {
   l.gxs = l.gagg + up64(V * 4 * TFi);
   l.gxd = l.gxs + up64(V * TFi);
   l.packed = l.gxd + up64(V * TFi);
-  l.dw = l.packed + up64(V * l.pitch);
+  l.dm = l.packed + (ED > 0 ? 0 : up64(V * l.pitch));
+  l.ecsr = l.dm + (ED > 0 ? up64(E * TFi) : 0);
+  l.dw = l.ecsr + (ED > 0 ? up64(E * ED) : 0);
   int64_t b = dw_bytes_of(V, Fo, S, 4 * Fi, Fi);
-  const int64_t b1 = dw_bytes_of(V, Fi, 1, Fi, 0), b2 = dw_bytes_of(V, (int)C, 1, (int)C, 0);
+  const int64_t b1 = dw_bytes_of(V, Fi, 1, Fi, 0), b2 = dw_bytes_of(V, (int)C, 1, (int)C, 0), b3 = ED > 0 ? dw_bytes_of(E, Fi, 1, ED, 0) : 0;
   b = b > b1 ? b : b1;
-  l.dw_bytes = b > b2 ? b : b2;
+  b = b > b2 ? b : b2;
+  l.dw_bytes = b > b3 ? b : b3;
   l.total = l.dw + up64((l.dw_bytes + 3) / 4);
   return l;
 }
 
-int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const char* who) {
+// q != NULL: the call with edge features (pna_tower_edge_train_*): its own checks, the wider pretrans weight, the larger workspace
+int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const char* who, const pna_tower_edge_train_args* q = nullptr) {
   if (!p) return pna_set_error(PNA_E_INVALID, who);
   if (int rc_ss = pna_check_struct_size(bwd ? "pna_tower_train_bwd_f32" : "pna_tower_train_fwd_f32", p->struct_size, sizeof(*p))) return rc_ss;
   const int T = p->n_tower, Fi = p->Fi, Fo = p->Fo, S = p->n_scaler;
@@ -629,13 +833,20 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
       return pna_set_error(PNA_E_INVALID, who);
   if (!bwd && (!p->out || p->ld_out < C)) return pna_set_error(PNA_E_INVALID, who);
   if (bwd) {
-    if (!p->grad_out || p->ld_go < C || !p->grad_h || !p->grad_w_mix || !p->grad_b_mix || !p->col_t || !p->rank_t || !p->items_t || p->n_items_t != p->V)
+    if (!p->grad_out || p->ld_go < C || !p->grad_h || !p->grad_w_mix || !p->grad_b_mix || !p->items_t || p->n_items_t != p->V)
       return pna_set_error(PNA_E_INVALID, who);
+    if (!q && (!p->col_t || !p->rank_t)) return pna_set_error(PNA_E_INVALID, who);      // (the edge route's pull reads pos_t instead)
     for (int t = 0; t < T; ++t)
       if (!p->grad_w_pre[t] || !p->grad_b_pre[t] || !p->grad_w_post[t] || !p->grad_b_post[t] || (p->gamma[t] && (!p->grad_gamma[t] || !p->grad_beta[t])))
         return pna_set_error(PNA_E_INVALID, who);
   }
-  l = layout_of(p->V, T, Fi, Fo, S);
+  const int ED = q ? q->edge_dim : 0;
+  if (q) {
+    if (ED < 1 || ED > kMaxED) return pna_set_error(PNA_E_INVALID, who);
+    if (p->E > 0 && (!q->e || q->ld_e < ED || !q->eid || !q->x_edge || (bwd && !q->pos_t))) return pna_set_error(PNA_E_INVALID, who);
+    if (bwd && q->grad_e && q->ld_ge < ED) return pna_set_error(PNA_E_INVALID, who);
+  }
+  l = layout_of(p->V, T, Fi, Fo, S, p->E, ED);
   if (p->workspace_bytes < l.total * 4) return pna_set_error(PNA_E_INVALID, who);
   memset(&g, 0, sizeof(g));
   float* const ws = (float*)p->workspace;
@@ -654,6 +865,11 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
   g.part = ws + (bwd ? l.part_bwd : l.part_fwd); g.n_part = l.n_tile;
   g.cm = ws + l.cm; g.gp = ws + l.gp; g.hcat = ws + l.hcat; g.ghc = ws + l.ghc; g.gz = ws + l.gz; g.gagg = ws + l.gagg;
   g.gxs = ws + l.gxs; g.gxd = ws + l.gxd; g.gh = p->grad_h;
+  g.ldw_pre = 2L * Fi + ED; g.E = p->E; g.ED = ED;
+  if (q) {
+    g.e = q->e; g.ld_e = (long)q->ld_e; g.eid = q->eid; g.xedge = q->x_edge; g.pos_t = q->pos_t; g.items_t = p->items_t;
+    g.dm = ws + l.dm; g.ecsr = ws + l.ecsr; g.ge = q->grad_e; g.ld_ge = (long)q->ld_ge;
+  }
   return PNA_OK;
 }
 
@@ -661,7 +877,7 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
 // identity when it forms an h panel or a bias), the plain fp32 kernel otherwise
 int weight_grad(const float* gy, int64_t ldg, int N, const float* a, int64_t lda, int K, const float* h, int64_t ldh, int Kh, int S,
                 const float* const* scale, int64_t V, float* gw, int64_t ldw, float* gb, void* ws, int64_t ws_bytes, hipStream_t st) {
-  if (dw_takes(N, S, K, Kh) && !(scale && scale[0])) {
+  if (V > 0 && dw_takes(N, S, K, Kh) && !(scale && scale[0])) {
     pna_posttrans_dw_args d;
     memset(&d, 0, sizeof(d));
     d.struct_size = (uint32_t)sizeof(d);
@@ -684,6 +900,105 @@ int weight_grad(const float* gy, int64_t ldg, int N, const float* a, int64_t lda
   return PNA_OK;
 }
 
+template <bool EDGE>
+int launch_fwd(const KArgs& g, const Layout& l, hipStream_t st, const char* failed) {
+  const int Fi = g.Fi, C = g.C, in_dim = g.div ? g.TFi : Fi;
+  const dim3 grid((unsigned)l.n_tile), block(kThreads);
+  hipLaunchKernelGGL(k_tt_project, grid, block, (size_t)kRows * (in_dim + 1) * sizeof(float), st, g);                   // <= 33 KB
+  if (EDGE && g.E > 0)
+    hipLaunchKernelGGL(k_tt_edge_project, dim3((unsigned)((g.E + kRows - 1) / kRows)), block, (size_t)kRows * pitch_of(quads(g.ED)) * sizeof(float), st, g);
+  const size_t lds = ((size_t)kRows * pitch_of(quads(4 * Fi)) + (size_t)kRows * pitch_of(quads(Fi)) + (size_t)kRows * (C + 1) + 4 * kRows) * sizeof(float);   // <= 50 KB
+  if (g.S == 1) hipLaunchKernelGGL((k_tt_rows_fwd<1, EDGE>), grid, block, lds, st, g);
+  else if (g.S == 2) hipLaunchKernelGGL((k_tt_rows_fwd<2, EDGE>), grid, block, lds, st, g);
+  else hipLaunchKernelGGL((k_tt_rows_fwd<3, EDGE>), grid, block, lds, st, g);
+  hipLaunchKernelGGL(k_tt_bn_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
+  hipLaunchKernelGGL(k_tt_mix_fwd, grid, block, (size_t)kRows * pitch_of(quads(C)) * sizeof(float), st, g);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, failed);
+  return PNA_OK;
+}
+
+// q != NULL: the backward with edge features -- the per-edge message gradient and its pull instead of rowprep + the ranked pull
+int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, pna_stream_t stream, const pna_tower_edge_train_args* q, const char* failed) {
+  hipStream_t st = (hipStream_t)stream;
+  const int T = g.T, Fi = g.Fi, Fo = g.Fo, S = g.S, C = g.C, TFi = g.TFi, K = 4 * Fi;
+  const dim3 grid((unsigned)l.n_tile), block(kThreads);
+  // 1. the mixing network, 2. the column sums, 3. gz and the aggregate's gradient
+  hipLaunchKernelGGL(k_tt_mix_bwd, grid, block, ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float), st, g);
+  hipLaunchKernelGGL(k_tt_bwd_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
+  const size_t lds = ((size_t)T * kRows * pitch_of(quads(Fo)) + 4 * kRows) * sizeof(float);
+  if (S == 1) hipLaunchKernelGGL(k_tt_rows_bwd<1>, grid, block, lds, st, g);
+  else if (S == 2) hipLaunchKernelGGL(k_tt_rows_bwd<2>, grid, block, lds, st, g);
+  else hipLaunchKernelGGL(k_tt_rows_bwd<3>, grid, block, lds, st, g);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, failed);
+  float* const ws = (float*)p->workspace;
+  int rc2;
+  if (q) {
+    // 4. the message gradient per edge (and gx_dst, the CSR-ordered e), then its pull per source row: gx_src; grad_e when wanted
+    hipLaunchKernelGGL(k_tt_edge_dm, grid, block, 0, st, g);
+    hipLaunchKernelGGL(k_tt_edge_pull, grid, block, 0, st, g);
+    if (g.ge && g.E > 0)
+      hipLaunchKernelGGL(k_tt_edge_grad_e, dim3((unsigned)((g.E + kRows - 1) / kRows)), block, (size_t)kRows * pitch_of(quads(Fi)) * sizeof(float), st, g);
+  } else {
+    // 4. rowprep + ranked pull over the transposed graph, all towers: gx_src; rowprep's grad_dst is gx_dst
+    pna_segreduce_bwd_args b;
+    memset(&b, 0, sizeof(b));
+    b.struct_size = (uint32_t)sizeof(b);
+    b.rowptr = p->rowptr; b.col = p->col; b.V = p->V; b.F = Fi;
+    b.x = p->x_cat; b.ldx = 2 * (int64_t)TFi;
+    b.dst_term = p->x_cat + TFi; b.ld_dst = 2 * (int64_t)TFi;
+    b.n_tower = T; b.n_aggr = 4; b.tower_stride_in = Fi;
+    b.aggr[0] = PNA_AGG_MEAN; b.aggr[1] = PNA_AGG_MAX; b.aggr[2] = PNA_AGG_MIN; b.aggr[3] = PNA_AGG_STD;
+    b.gagg = g.gagg; b.ld_g = (int64_t)T * K; b.tower_stride_g = K;
+    b.mean = p->a; b.stdv = p->a + 3 * (size_t)Fi; b.ld_stat = (int64_t)T * K; b.tower_stride_stat = K;
+    b.argmax = p->argmax; b.argmin = p->argmin; b.ld_arg = TFi;
+    b.grad_x = g.gxs; b.ld_gx = TFi;
+    b.grad_dst = g.gxd; b.ld_gd = TFi;
+    pna_segreduce_bwd_pull_args pl;
+    memset(&pl, 0, sizeof(pl));
+    pl.struct_size = (uint32_t)sizeof(pl);
+    float* const packed = ws + l.packed;
+    pl.base = &b; pl.table = packed; pl.ld_table = l.pitch;
+    pl.col_t = p->col_t; pl.rank_t = p->rank_t; pl.items_t = p->items_t; pl.n_items_t = p->n_items_t; pl.run_rowprep = 1;
+    pl.ranks = (uint16_t*)(packed + 4 * (size_t)TFi); pl.ld_rank = 2 * l.pitch;
+    rc2 = pna_segreduce_bwd_pull_launch(&pl, nullptr, 0, stream);
+    if (rc2 != PNA_OK) return rc2;
+  }
+  // 5. grad_h
+  hipLaunchKernelGGL(k_tt_grad_h, grid, block, (size_t)kRows * pitch_of(quads(Fo + 2 * Fi)) * sizeof(float), st, g);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, failed);
+  // 6. the weight and bias gradients, tower by tower, then the mixing network's
+  void* const dws = ws + l.dw;
+  const int64_t ldwp = (int64_t)g.ldw_pre;
+  for (int t = 0; t < T; ++t) {
+    const float* const ht = p->h + (g.div ? t * Fi : 0);
+    rc2 = weight_grad(g.gz + t * Fo, C, Fo, p->a + (size_t)t * K, (int64_t)T * K, K, ht, p->ldh, Fi, S, p->row_scale, p->V, p->grad_w_post[t], (int64_t)(1 + 4 * S) * Fi,
+                      p->grad_b_post[t], dws, l.dw_bytes, st);
+    if (rc2 != PNA_OK) return rc2;
+    rc2 = weight_grad(g.gxs + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t], ldwp, nullptr, dws, l.dw_bytes, st);
+    if (rc2 != PNA_OK) return rc2;
+    rc2 = weight_grad(g.gxd + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t] + Fi, ldwp, p->grad_b_pre[t], dws, l.dw_bytes, st);
+    if (rc2 != PNA_OK) return rc2;
+    if (q) {                                                // grad_W_e,t = dm_t^T e_csr over the E edges (zeros when there are none)
+      rc2 = weight_grad(g.dm + t * Fi, TFi, Fi, g.ecsr, g.ED, g.ED, nullptr, 0, 0, 1, nullptr, g.E, p->grad_w_pre[t] + 2 * Fi, ldwp, nullptr, dws, l.dw_bytes, st);
+      if (rc2 != PNA_OK) return rc2;
+    }
+  }
+  return weight_grad(g.gp, C, C, g.hcat, C, C, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_mix, C, p->grad_b_mix, dws, l.dw_bytes, st);
+}
+
+const char* const kEdgeNeeds =
+    ": needs a base inside pna_tower_train_*_f32's scope whose w_pre / grad_w_pre are (Fi, 2 Fi + edge_dim) and whose 256-byte aligned workspace "
+    "has pna_tower_edge_train_workspace_bytes(V, E, n_tower, Fi, Fo, n_scaler, divide_input, edge_dim) bytes (backward: items_t with "
+    "n_items_t == V), 1 <= edge_dim <= 64, and with E > 0: e (ld_e >= edge_dim), eid, x_edge, in the backward pos_t (grad_e: ld_ge >= edge_dim)";
+
+int fill_edge(const pna_tower_edge_train_args* q, KArgs& g, Layout& l, bool bwd) {
+  static const std::string fwd_msg = std::string("pna_tower_edge_train_fwd_f32") + kEdgeNeeds, bwd_msg = std::string("pna_tower_edge_train_bwd_f32") + kEdgeNeeds;
+  const char* const who = bwd ? bwd_msg.c_str() : fwd_msg.c_str();
+  if (!q) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(bwd ? "pna_tower_edge_train_bwd_f32" : "pna_tower_edge_train_fwd_f32", q->struct_size, sizeof(*q))) return rc_ss;
+  return fill(q->base, g, l, bwd, who, q);
+}
+
 }  // namespace
 
 extern "C" int64_t pna_tower_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input) {
@@ -700,18 +1015,7 @@ extern "C" int pna_tower_train_fwd_f32(const pna_tower_train_args* p, pna_stream
                                       "the saved tensors x_cat / a / argmax / argmin / z / p / save_mean / save_invstd, out (ld >= n_tower Fo), a 256-byte aligned "
                                       "workspace of pna_tower_train_workspace_bytes(V, E, n_tower, Fi, Fo, n_scaler, divide_input)");
   if (rc != PNA_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int Fi = g.Fi, C = g.C, in_dim = g.div ? g.TFi : Fi;
-  const dim3 grid((unsigned)l.n_tile), block(kThreads);
-  hipLaunchKernelGGL(k_tt_project, grid, block, (size_t)kRows * (in_dim + 1) * sizeof(float), st, g);                   // <= 33 KB
-  const size_t lds = ((size_t)kRows * pitch_of(quads(4 * Fi)) + (size_t)kRows * pitch_of(quads(Fi)) + (size_t)kRows * (C + 1) + 4 * kRows) * sizeof(float);   // <= 50 KB
-  if (g.S == 1) hipLaunchKernelGGL(k_tt_rows_fwd<1>, grid, block, lds, st, g);
-  else if (g.S == 2) hipLaunchKernelGGL(k_tt_rows_fwd<2>, grid, block, lds, st, g);
-  else hipLaunchKernelGGL(k_tt_rows_fwd<3>, grid, block, lds, st, g);
-  hipLaunchKernelGGL(k_tt_bn_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
-  hipLaunchKernelGGL(k_tt_mix_fwd, grid, block, (size_t)kRows * pitch_of(quads(C)) * sizeof(float), st, g);
-  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_fwd_f32: launch failed");
-  return PNA_OK;
+  return launch_fwd<false>(g, l, (hipStream_t)stream, "pna_tower_train_fwd_f32: launch failed");
 }
 
 extern "C" int pna_tower_train_bwd_f32(const pna_tower_train_args* p, pna_stream_t stream) {
@@ -721,55 +1025,27 @@ extern "C" int pna_tower_train_bwd_f32(const pna_tower_train_args* p, pna_stream
                                      "grad_w_pre / grad_b_pre / grad_w_post / grad_b_post (grad_gamma / grad_beta where it has gamma), grad_w_mix / grad_b_mix, the "
                                      "transposed graph (col_t, rank_t, one whole-row record per source row in items_t: n_items_t == V) and the forward's workspace size");
   if (rc != PNA_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int T = g.T, Fi = g.Fi, Fo = g.Fo, S = g.S, C = g.C, TFi = g.TFi, K = 4 * Fi;
-  const dim3 grid((unsigned)l.n_tile), block(kThreads);
-  // 1. the mixing network, 2. the column sums, 3. gz and the aggregate's gradient
-  hipLaunchKernelGGL(k_tt_mix_bwd, grid, block, ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float), st, g);
-  hipLaunchKernelGGL(k_tt_bwd_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
-  const size_t lds = ((size_t)T * kRows * pitch_of(quads(Fo)) + 4 * kRows) * sizeof(float);
-  if (S == 1) hipLaunchKernelGGL(k_tt_rows_bwd<1>, grid, block, lds, st, g);
-  else if (S == 2) hipLaunchKernelGGL(k_tt_rows_bwd<2>, grid, block, lds, st, g);
-  else hipLaunchKernelGGL(k_tt_rows_bwd<3>, grid, block, lds, st, g);
-  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_bwd_f32: launch failed");
-  // 4. rowprep + ranked pull over the transposed graph, all towers: gx_src; rowprep's grad_dst is gx_dst
-  float* const ws = (float*)p->workspace;
-  pna_segreduce_bwd_args b;
-  memset(&b, 0, sizeof(b));
-  b.struct_size = (uint32_t)sizeof(b);
-  b.rowptr = p->rowptr; b.col = p->col; b.V = p->V; b.F = Fi;
-  b.x = p->x_cat; b.ldx = 2 * (int64_t)TFi;
-  b.dst_term = p->x_cat + TFi; b.ld_dst = 2 * (int64_t)TFi;
-  b.n_tower = T; b.n_aggr = 4; b.tower_stride_in = Fi;
-  b.aggr[0] = PNA_AGG_MEAN; b.aggr[1] = PNA_AGG_MAX; b.aggr[2] = PNA_AGG_MIN; b.aggr[3] = PNA_AGG_STD;
-  b.gagg = g.gagg; b.ld_g = (int64_t)T * K; b.tower_stride_g = K;
-  b.mean = p->a; b.stdv = p->a + 3 * (size_t)Fi; b.ld_stat = (int64_t)T * K; b.tower_stride_stat = K;
-  b.argmax = p->argmax; b.argmin = p->argmin; b.ld_arg = TFi;
-  b.grad_x = g.gxs; b.ld_gx = TFi;
-  b.grad_dst = g.gxd; b.ld_gd = TFi;
-  pna_segreduce_bwd_pull_args q;
-  memset(&q, 0, sizeof(q));
-  q.struct_size = (uint32_t)sizeof(q);
-  float* const packed = ws + l.packed;
-  q.base = &b; q.table = packed; q.ld_table = l.pitch;
-  q.col_t = p->col_t; q.rank_t = p->rank_t; q.items_t = p->items_t; q.n_items_t = p->n_items_t; q.run_rowprep = 1;
-  q.ranks = (uint16_t*)(packed + 4 * (size_t)TFi); q.ld_rank = 2 * l.pitch;
-  int rc2 = pna_segreduce_bwd_pull_launch(&q, nullptr, 0, stream);
-  if (rc2 != PNA_OK) return rc2;
-  // 5. grad_h
-  hipLaunchKernelGGL(k_tt_grad_h, grid, block, (size_t)kRows * pitch_of(quads(Fo + 2 * Fi)) * sizeof(float), st, g);
-  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_tower_train_bwd_f32: launch failed");
-  // 6. the weight and bias gradients, tower by tower, then the mixing network's
-  void* const dws = ws + l.dw;
-  for (int t = 0; t < T; ++t) {
-    const float* const ht = p->h + (g.div ? t * Fi : 0);
-    rc2 = weight_grad(g.gz + t * Fo, C, Fo, p->a + (size_t)t * K, (int64_t)T * K, K, ht, p->ldh, Fi, S, p->row_scale, p->V, p->grad_w_post[t], (int64_t)(1 + 4 * S) * Fi,
-                      p->grad_b_post[t], dws, l.dw_bytes, st);
-    if (rc2 != PNA_OK) return rc2;
-    rc2 = weight_grad(g.gxs + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t], 2 * (int64_t)Fi, nullptr, dws, l.dw_bytes, st);
-    if (rc2 != PNA_OK) return rc2;
-    rc2 = weight_grad(g.gxd + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t] + Fi, 2 * (int64_t)Fi, p->grad_b_pre[t], dws, l.dw_bytes, st);
-    if (rc2 != PNA_OK) return rc2;
-  }
-  return weight_grad(g.gp, C, C, g.hcat, C, C, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_mix, C, p->grad_b_mix, dws, l.dw_bytes, st);
+  return launch_bwd(p, g, l, stream, nullptr, "pna_tower_train_bwd_f32: launch failed");
+}
+
+extern "C" int64_t pna_tower_edge_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input,
+                                                        int32_t edge_dim) {
+  if (!in_scope(V, E, n_tower, Fi, Fo, n_scaler, divide_input) || edge_dim < 1 || edge_dim > kMaxED) return -1;
+  return layout_of(V, n_tower, Fi, Fo, n_scaler, E, edge_dim).total * 4;
+}
+
+extern "C" int pna_tower_edge_train_fwd_f32(const pna_tower_edge_train_args* q, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill_edge(q, g, l, false);
+  if (rc != PNA_OK) return rc;
+  return launch_fwd<true>(g, l, (hipStream_t)stream, "pna_tower_edge_train_fwd_f32: launch failed");
+}
+
+extern "C" int pna_tower_edge_train_bwd_f32(const pna_tower_edge_train_args* q, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill_edge(q, g, l, true);
+  if (rc != PNA_OK) return rc;
+  return launch_bwd(q->base, g, l, stream, q, "pna_tower_edge_train_bwd_f32: launch failed");
 }

@@ -386,20 +386,41 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
         batch_norm with the default running statistics and one eps and momentum for all towers, graph_norm the same for every tower, no dropout inside the towers, a mixing
         network that is Linear + LeakyReLU without batch-norm or active dropout, widths pna_amd.functional.small_tower_train_fits
         accepts, at least 2 rows, in-degrees below 65535, snorm_n (V, 1) or (V,) fp32 when graph_norm is on."""
+        return self._small_tower_train_clauses(graph, h, snorm_n, PF.SMALL_TOWER_TRAIN_ROWS, False, None)
+
+    def _small_tower_train_edge_path(self, graph, h, e, snorm_n=None):
+        """Whether this call is served by pna_tower_edge_train_fwd_f32 / _bwd_f32 (autograd.TowerLayerEdgeSmallTrainFn): the clauses of
+        _small_tower_train_path with edge_features REQUIRED of the layer and of every tower and the knob
+        PNA_AMD_SMALL_TOWER_TRAIN_EDGE_ROWS in place of PNA_AMD_SMALL_TOWER_TRAIN_ROWS, plus: one edge_dim for all towers, within 1..64;
+        pretrans weights of shape (Fi, 2 Fi + edge_dim); e an fp32 tensor on the GPU of shape (E, edge_dim) with one row per edge of the
+        graph.  A gradient is wanted if h, e or any parameter requires one."""
+        return self._small_tower_train_clauses(graph, h, snorm_n, PF.SMALL_TOWER_TRAIN_EDGE_ROWS, True, e)
+
+    def _small_tower_train_clauses(self, graph, h, snorm_n, rows, edge, e):
+        """The clauses of the two one-call training routes: `rows` the route's knob, `edge` whether it is the route with edge features
+        (required of the layer and every tower) or the one without (excluded), `e` the edge route's features."""
         V = h.shape[0]
-        if not (PF.SMALL_TOWER_TRAIN_ROWS > 0 and 0 < V <= PF.SMALL_TOWER_TRAIN_ROWS):
+        if not (rows > 0 and 0 < V <= rows):
             return False
         towers = list(self._modules["towers"]._modules.values())
         t0, mix = towers[0], self.mixing_network
-        if not (self.training and not self.edge_features and h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and type(graph) is Graph
+        if not (self.training and bool(self.edge_features) == edge and h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and type(graph) is Graph
                 and graph.num_nodes == V and V >= 2 and h.shape[1] == self.in_dim):
             return False
         if not (tuple(t0.aggregators) == ("mean", "max", "min", "std") and 1 <= len(t0.scalers) <= 3
                 and PF.small_tower_train_fits(len(towers), self.input_tower, self.output_tower, len(t0.scalers))):
             return False
+        if edge:
+            Fi, ed = self.input_tower, t0.edge_dim
+            if not (PF.small_tower_train_edge_fits(len(towers), Fi, self.output_tower, len(t0.scalers), ed) and all(t.edge_dim == ed for t in towers)):
+                return False
+            if any(len(t.pretrans.fully_connected) != 1 or tuple(t.pretrans.fully_connected[0].linear.weight.shape) != (Fi, 2 * Fi + ed) for t in towers):
+                return False
+            if not (e is not None and e.is_cuda and e.dtype == torch.float32 and e.dim() == 2 and tuple(e.shape) == (graph.csr.col.numel(), ed)):
+                return False
         for t in towers:
             bn = t.batchnorm_h
-            if not (t.training and bn.training and t.batch_norm and not t.edge_features and t.dropout == 0 and t.graph_norm == t0.graph_norm
+            if not (t.training and bn.training and t.batch_norm and bool(t.edge_features) == edge and t.dropout == 0 and t.graph_norm == t0.graph_norm
                     and tuple(t.aggregators) == tuple(t0.aggregators) and tuple(t.scalers) == tuple(t0.scalers)
                     and len(t.pretrans.fully_connected) == 1 and len(t.posttrans.fully_connected) == 1):
                 return False
@@ -418,7 +439,7 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
         for t in list(self.parameters()) + list(self.buffers()):
             if t.is_floating_point() and (t.dtype != torch.float32 or not t.is_cuda):
                 return False
-        if not (torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters()))):
+        if not (torch.is_grad_enabled() and (h.requires_grad or (edge and e.requires_grad) or any(p.requires_grad for p in self.parameters()))):
             return False
         return graph.csr.max_degree < 65535
 
@@ -476,6 +497,11 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
             from .. import autograd as AG
             t0 = self.towers[0]
             return AG.tower_layer_small_train(self, graph, h, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
+        if PF.SMALL_TOWER_TRAIN_EDGE_ROWS > 0 and self._small_tower_train_edge_path(graph, h, e, snorm_n):
+            # the same with edge features (autograd.TowerLayerEdgeSmallTrainFn); e is an input of the call: its gradient comes back
+            from .. import autograd as AG
+            t0 = self.towers[0]
+            return AG.tower_layer_edge_small_train(self, graph, h, e, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
         h_cat = _towers_forward(list(self.towers), graph, h, e, snorm_n, self.divide_input)
         mix = self.mixing_network
         if (h_cat.shape[1] >= 4 and isinstance(mix.activation, nn.LeakyReLU) and mix.b_norm is None and (mix.dropout is None or not self.training)

@@ -1210,6 +1210,18 @@ def small_tower_train_fits(T, Fi, Fo, S=3):
     return 1 <= T <= 8 and 4 <= Fi <= 128 and T * Fi <= 512 and 1 <= Fo and T * Fo <= 128 and 1 <= S <= 3
 
 
+# PNALayer TRAINING batches WITH EDGE FEATURES up to this many nodes take the one-call route (autograd.TowerLayerEdgeSmallTrainFn:
+# pna_tower_edge_train_fwd_f32 / _bwd_f32).  A knob of its own: SMALL_TOWER_TRAIN_ROWS keeps its meaning.  0 = off, the default
+# 
+SMALL_TOWER_TRAIN_EDGE_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_EDGE_ROWS", "0"))
+
+
+def small_tower_train_edge_fits(T, Fi, Fo, S=3, edge_dim=0):
+    """Mirror of pna_tower_edge_train_fwd_f32's scope: small_tower_train_fits and 1 <= edge_dim <= 64 (the K of the edge tile: 16 rows
+    of at most 64 features, inside the LDS the rows kernels already use)."""
+    return small_tower_train_fits(T, Fi, Fo, S) and 1 <= edge_dim <= 64
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")

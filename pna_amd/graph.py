@@ -282,6 +282,13 @@ class Graph:
             self._heavy[key] = torch.cat([heavy_items, light], dim=0).to(torch.int32).contiguous()
         return self._heavy[key]
 
+    def edge_ids32(self):
+        """csr.eid as int32 (the C calls' index type), kept with the graph's other derived arrays."""
+        key = ("eid32",)
+        if key not in self._heavy:
+            self._heavy[key] = self.csr.eid.to(torch.int32).contiguous()
+        return self._heavy[key]
+
     def workspace(self, nbytes):
         """Reusable float32 scratch (heavy-row partials) on the graph's device."""
         n = (nbytes + 3) // 4

@@ -87,21 +87,22 @@ def timed(step):
     return (time.perf_counter() - t0) * 1e3
 
 
-def measure(workload, dev, steps, warmup):
-    step, V, E, graphs = setup(workload, dev)
+def measure(workload, dev, steps, warmup, setup=None, knob_name="SMALL_TOWER_TRAIN_ROWS"):
+    """setup / knob_name: another tool's workloads and the knob of its route (tools/bench_tower_edge_train.py)."""
+    step, V, E, graphs = (setup or globals()["setup"])(workload, dev)
     knobs = {"parent_route": 0, "one_call_route": V}
     times = {k: [] for k in knobs}
     gc.disable()
     try:
         for i in range(warmup + steps):
             for name, knob in knobs.items():                    # the routes alternate step by step
-                PF.SMALL_TOWER_TRAIN_ROWS = knob
+                setattr(PF, knob_name, knob)
                 t = timed(step)
                 if i >= warmup:
                     times[name].append(t)
     finally:
         gc.enable()
-        PF.SMALL_TOWER_TRAIN_ROWS = 0
+        setattr(PF, knob_name, 0)
     ent = {"graphs": graphs, "V": V, "E": E}
     for name, ts in times.items():
         ent[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "steps": len(ts)}
@@ -109,19 +110,19 @@ def measure(workload, dev, steps, warmup):
     return ent
 
 
-def child(workload, knob, steps):
+def child(workload, knob, steps, setup=None, knob_name="SMALL_TOWER_TRAIN_ROWS"):
     dev = torch.device("cuda:0")
-    step, V, _, _ = setup(workload, dev)
-    PF.SMALL_TOWER_TRAIN_ROWS = V if knob else 0
+    step, V, _, _ = (setup or globals()["setup"])(workload, dev)
+    setattr(PF, knob_name, V if knob else 0)
     for _ in range(steps):
         step()
     torch.cuda.synchronize()
 
 
-def _trace_rows(workload, knob, steps):
+def _trace_rows(workload, knob, steps, script):
     d = tempfile.mkdtemp(prefix="tower_train_trace_")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "st", "--",
-           sys.executable, os.path.abspath(__file__), "--child", workload, "--knob", str(knob), "--steps", str(steps)]
+           sys.executable, os.path.abspath(script), "--child", workload, "--knob", str(knob), "--steps", str(steps)]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         files = glob.glob(os.path.join(d, "**", "st_kernel_stats.csv"), recursive=True)
@@ -132,13 +133,13 @@ def _trace_rows(workload, knob, steps):
         shutil.rmtree(d, ignore_errors=True)
 
 
-def trace(workload, knob, short=3, long=13):
+def trace(workload, knob, short=3, long=13, script=__file__):
     """Launches per step and the per-kernel split of the device time: the difference between the rocprofv3 kernel statistics of a child
     that runs `long` steps and one that runs `short` (what the set-up launches -- graph build, initialisation -- cancels out of)."""
     if shutil.which("rocprofv3") is None:
         return {"error": "rocprofv3 not found"}
     try:
-        a, b = _trace_rows(workload, knob, short), _trace_rows(workload, knob, long)
+        a, b = _trace_rows(workload, knob, short, script), _trace_rows(workload, knob, long, script)
     except (RuntimeError, subprocess.TimeoutExpired) as ex:
         return {"error": str(ex)}
     n = long - short
