@@ -278,6 +278,10 @@ def _backward_pull(graph, x, dst_term, ident, amx, amn, gagg, aggs, all_aggs, T,
     V, TF = gagg.shape[0], T * F                            # (row_of: ident / amx / amn hold node v's row at row_of[v] -- plan order)
     A, A2 = len(aggs), len(all_aggs)
     has_var = any(a in _STAT_AGGS for a in aggs)
+    if csr.col.numel() == 0:
+        # a graph without edges: no message, so both gradients are zero -- and there is no index array (col, col_t, rank_t) to hand to a
+        # kernel (pna_segreduce_bwd_pull_f32 and _argscatter_f32 refuse null pointers)
+        return (torch.zeros_like(x) if need_x else None), (torch.zeros(V, TF, dtype=torch.float32, device=dev) if need_d else None)
     b = _lib.PnaSegreduceBwdArgs()
     if row_of is not None:
         b.stat_row_of = _lib.dev_ptr(row_of, torch.int32, "stat_row_of")

@@ -54,6 +54,10 @@ def test_route_is_off_by_default_and_read_from_the_environment(monkeypatch):
 def test_small_train_path_clause_by_clause(monkeypatch):
     g, shard, h = _graph(), _graph(cls=HaloGraph), _OnGpu(40, 20)
     assert g.csr.max_degree == 1                                                  # (built on the host, before tensors pretend below)
+    # the 16-bit ranks of the max / min gradient (0xFFFF: none): in-degree 65534 is the last the route admits, 65535 the first it declines
+    hubs = {d: _graph() for d in (65534, 65535)}
+    for d, hub in hubs.items():
+        hub._csr = hub.csr._replace(max_degree=d)
     # parameters and buffers report is_cuda -- the predicate's residency clause -- without a GPU
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
     monkeypatch.setattr(PF, "SMALL_TRAIN_ROWS", 0)
@@ -61,6 +65,7 @@ def test_small_train_path_clause_by_clause(monkeypatch):
     monkeypatch.setattr(PF, "SMALL_TRAIN_ROWS", 4096)
     assert _layer()._small_train_path(g, h)
     assert _layer(residual=True, N=20)._small_train_path(g, h)
+    assert _layer()._small_train_path(hubs[65534], h) and not _layer()._small_train_path(hubs[65535], h)
     assert not _layer().eval()._small_train_path(g, h)                            # eval mode
     half = _layer()
     half.batchnorm_h.eval()

@@ -62,6 +62,10 @@ def test_small_tower_train_edge_path_clause_by_clause(monkeypatch):
     g, shard, h, n = _graph(), _graph(cls=HaloGraph), _OnGpu(40, 24), _OnGpu(40, 1, requires_grad=False)
     e = _OnGpu(40, 3, requires_grad=False)
     assert g.csr.max_degree == 1 and g.csr.col.numel() == 40                      # (built on the host, before tensors pretend below)
+    # the 16-bit ranks of the max / min gradient (0xFFFF: none): in-degree 65534 is the last the route admits, 65535 the first it declines
+    hubs = {d: _graph() for d in (65534, 65535)}
+    for d, hub in hubs.items():
+        hub._csr = hub.csr._replace(max_degree=d)
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
     monkeypatch.setattr(PF, "SMALL_TOWER_TRAIN_EDGE_ROWS", 0)
     monkeypatch.setattr(PF, "SMALL_TOWER_TRAIN_ROWS", 4096)
@@ -71,6 +75,7 @@ def test_small_tower_train_edge_path_clause_by_clause(monkeypatch):
     monkeypatch.setattr(PF, "SMALL_TOWER_TRAIN_ROWS", 0)
     assert _layer()._small_tower_train_edge_path(g, h, e, n)
     assert _layer(residual=False)._small_tower_train_edge_path(g, h, e, n)
+    assert _layer()._small_tower_train_edge_path(hubs[65534], h, e, n) and not _layer()._small_tower_train_edge_path(hubs[65535], h, e, n)
     assert _layer(graph_norm=False)._small_tower_train_edge_path(g, h, e, None)
     assert _layer(divide_input=False)._small_tower_train_edge_path(g, h, e, n)
     assert _layer(in_dim=70, out_dim=70, towers=5, edge_dim=50)._small_tower_train_edge_path(g, _OnGpu(40, 70), _OnGpu(40, 50), n)      # ZINC's first layers

@@ -61,12 +61,17 @@ def test_route_is_off_by_default_and_read_from_the_environment(monkeypatch):
 def test_small_tower_train_path_clause_by_clause(monkeypatch):
     g, shard, h, n = _graph(), _graph(cls=HaloGraph), _OnGpu(40, 24), _OnGpu(40, 1, requires_grad=False)
     assert g.csr.max_degree == 1                                                  # (built on the host, before tensors pretend below)
+    # the 16-bit ranks of the max / min gradient (0xFFFF: none): in-degree 65534 is the last the route admits, 65535 the first it declines
+    hubs = {d: _graph() for d in (65534, 65535)}
+    for d, hub in hubs.items():
+        hub._csr = hub.csr._replace(max_degree=d)
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
     monkeypatch.setattr(PF, "SMALL_TOWER_TRAIN_ROWS", 0)
     assert not _layer()._small_tower_train_path(g, h, n)                          # the knob at 0
     monkeypatch.setattr(PF, "SMALL_TOWER_TRAIN_ROWS", 4096)
     assert _layer()._small_tower_train_path(g, h, n)
     assert _layer(residual=False)._small_tower_train_path(g, h, n)
+    assert _layer()._small_tower_train_path(hubs[65534], h, n) and not _layer()._small_tower_train_path(hubs[65535], h, n)
     assert _layer(graph_norm=False)._small_tower_train_path(g, h, None)
     assert _layer(divide_input=False, in_dim=24, out_dim=24)._small_tower_train_path(g, h, n)
     assert _layer(in_dim=75, out_dim=75, towers=5, divide_input=False)._small_tower_train_path(g, _OnGpu(40, 75), n)      # ZINC's first layers
