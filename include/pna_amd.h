@@ -26,7 +26,11 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_train_fwd_f32 / pna_tower_train_bwd_f32 / pna_tower_train_workspace_bytes /
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_embed_sum_fwd_f32 / pna_embed_sum_bwd_f32 / pna_embed_sum_workspace_bytes / pna_embed_sum_args,
+                                  pna_readout_fwd_f32 / pna_readout_bwd_f32 / pna_readout_args, PNA_MAX_EMBED_TABLE (the two ends of the molecule
+                                  nets: the sum of embedding tables and the per-graph readout, one call each way); no existing struct or entry
+                                  point changed.
+                                  23, additive: + pna_tower_train_fwd_f32 / pna_tower_train_bwd_f32 / pna_tower_train_workspace_bytes /
                                   pna_tower_train_args, PNA_MAX_TOWER (PNALayer's TRAINING forward and backward on molecule batches, one call
                                   each); no existing struct or entry point changed.
                                   23, additive: + pna_tower_edge_train_fwd_f32 / pna_tower_edge_train_bwd_f32 / pna_tower_edge_train_workspace_bytes /
@@ -112,6 +116,7 @@ enum {
 #define PNA_MAX_AGGR 8
 #define PNA_MAX_SCALER 8
 #define PNA_MAX_TOWER 8   /* towers of one pna_tower_train_args */
+#define PNA_MAX_EMBED_TABLE 16   /* tables of one pna_embed_sum_args */
 
 /* Optional launch tuning; all-zero = library defaults. */
 typedef struct pna_tuning {
@@ -1576,6 +1581,82 @@ int64_t pna_tower_edge_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tow
                                              int32_t edge_dim);   /* -1 outside the scope */
 int pna_tower_edge_train_fwd_f32(const pna_tower_edge_train_args* args, pna_stream_t stream);
 int pna_tower_edge_train_bwd_f32(const pna_tower_edge_train_args* args, pna_stream_t stream);
+
+/* ---- The two ENDS of the molecule nets: the sum of embedding tables and the per-graph readout, one call each way ----------------
+ * replaces: ogb's AtomEncoder as nets/HIV_graph_classification/pna_net.py:42 calls it (a sum of nine nn.Embedding lookups), the single
+ * nn.Embedding of nets/molecules_graph_regression/pna_net.py:68-73, what autograd derives from them, and dgl.sum_nodes / mean_nodes /
+ * max_nodes of pna_net.py:83-90 with their backward.
+ *
+ * pna_embed_sum_fwd_f32 (one launch): out[v, :] = ((0 + table_0[idx[v, 0], :]) + table_1[idx[v, 1], :]) + ... in table order, fp32.
+ * pna_embed_sum_bwd_f32 (two launches, no atomics of any kind, bitwise repeatable): grad_table_j[r, :] = sum of grad_out[v, :] over the
+ *   rows v with idx[v, j] == r.  The rows are cut into n_slab = ceil(V / L) slabs of L = max(PNA_EMBED_SLAB_ROWS, ceil(V /
+ *   PNA_EMBED_MAX_SLABS)) consecutive rows (so n_slab <= PNA_EMBED_MAX_SLABS whatever V is).  A workgroup owns one slab and keeps ONE fp32
+ *   image of all tables, (sum_j rows_j, round4(F)), in LDS; a thread owns one column and a fixed subset of the tables (tables occupy
+ *   disjoint rows of the image: no two threads touch the same word) and adds the slab's rows in row order; the image goes to the slab's
+ *   slot of the workspace.  The second launch, one thread per table element, adds the slots in slab order in float64 and stores fp32:
+ *   EVERY element of every grad_table_j is written (zeros included); nothing is accumulated into or assumed cleared.
+ * Scope (PNA_E_INVALID outside it, pna_embed_sum_workspace_bytes returns -1): V >= 1, 1 <= n_table <= PNA_MAX_EMBED_TABLE,
+ * 1 <= F <= 256, rows_j >= 1 and sum_j rows_j * round4(F) * 4 <= 128 KiB (the image beside the kernel's staging area in the CU's
+ * 160 KiB of LDS).  An index outside [0, rows_j) is CLAMPED into range by both calls: no index reads or writes out of bounds.
+ * idx is int64, (V, ld_idx >= n_table) in elements (a 1-D index of any stride when n_table == 1).  grad_table_j is (rows_j, F)
+ * contiguous.  workspace: pna_embed_sum_workspace_bytes(...) bytes (backward only), 16-byte aligned, no initialisation: no launch reads
+ * what the call has not written. */
+#define PNA_EMBED_SLAB_ROWS 64
+#define PNA_EMBED_MAX_SLABS 256
+typedef struct pna_embed_sum_args {
+  uint32_t struct_size;    /* sizeof(pna_embed_sum_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  int32_t V;
+  int32_t n_table;
+  int32_t F;
+  int32_t _pad0;
+  const int64_t* idx;      /* (V, ld_idx) */
+  int64_t ld_idx;          /* in elements */
+  const float* table[PNA_MAX_EMBED_TABLE];    /* first n_table: (rows_j, ld_table_j >= F) */
+  int32_t rows[PNA_MAX_EMBED_TABLE];
+  int64_t ld_table[PNA_MAX_EMBED_TABLE];
+  float* out;              /* forward (V, ld_out >= F) */
+  int64_t ld_out;
+  const float* grad_out;   /* backward (V, ld_go >= F) */
+  int64_t ld_go;
+  float* grad_table[PNA_MAX_EMBED_TABLE];     /* backward, first n_table: (rows_j, F) contiguous */
+  void* workspace;         /* backward */
+  int64_t workspace_bytes;
+} pna_embed_sum_args;
+
+int64_t pna_embed_sum_workspace_bytes(int64_t V, int32_t n_table, const int32_t* rows /* host */, int32_t F);   /* -1 outside the scope */
+int pna_embed_sum_fwd_f32(const pna_embed_sum_args* args, pna_stream_t stream);
+int pna_embed_sum_bwd_f32(const pna_embed_sum_args* args, pna_stream_t stream);
+
+/* pna_readout_fwd_f32 (one launch, one workgroup per graph, a thread per column walking the graph's rows in order):
+ *   out[g, :] = sum / mean / max of h[offsets[g] .. offsets[g+1], :]; op = PNA_AGG_SUM, PNA_AGG_MEAN (sum / n) or PNA_AGG_MAX.  For max
+ *   the launch also writes argmax (G, F): the row of the FIRST maximum, pna_segreduce_fwd_f32's strict comparison and sticky NaN (-1 where
+ *   no row exceeds -inf), so values and indices are that call's bits over the identity edge list.
+ * pna_readout_bwd_f32 (one launch, no atomics, EVERY element of grad_h's rows [offsets[0], offsets[G]) written):
+ *   sum: grad_out[g]; mean: grad_out[g] / n; max: grad_out[g] in the arg row, 0 elsewhere.
+ * Scope: G >= 1 segments given by G + 1 ascending int32 offsets, every segment non-empty, inside [0, V] (offsets are clamped to it: no
+ * offset reads or writes out of bounds); 1 <= F <= 512. */
+typedef struct pna_readout_args {
+  uint32_t struct_size;    /* sizeof(pna_readout_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* offsets;  /* [G+1] */
+  int32_t G;
+  int32_t V;               /* rows of h / grad_h */
+  int32_t F;
+  int32_t op;              /* PNA_AGG_SUM, PNA_AGG_MEAN or PNA_AGG_MAX */
+  const float* h;          /* forward (V, ldh >= F) */
+  int64_t ldh;
+  float* out;              /* forward (G, ld_out >= F) */
+  int64_t ld_out;
+  int32_t* argmax;         /* max only: (G, F) contiguous; forward writes, backward reads */
+  const float* grad_out;   /* backward (G, ld_go >= F) */
+  int64_t ld_go;
+  float* grad_h;           /* backward (V, ld_gh >= F) */
+  int64_t ld_gh;
+} pna_readout_args;
+
+int pna_readout_fwd_f32(const pna_readout_args* args, pna_stream_t stream);
+int pna_readout_bwd_f32(const pna_readout_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

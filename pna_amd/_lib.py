@@ -17,6 +17,9 @@ PNA_ABI_VERSION = 23
 PNA_MAX_AGGR = 8
 PNA_MAX_SCALER = 8
 PNA_MAX_TOWER = 8
+PNA_MAX_EMBED_TABLE = 16
+PNA_EMBED_SLAB_ROWS = 64        # pna_embed_sum_bwd_f32: a slab is max(this, ceil(V / PNA_EMBED_MAX_SLABS)) rows
+PNA_EMBED_MAX_SLABS = 256
 
 # (std_pyg: the bf16 entry points only -- the PyG std, whose row without in-edges is sqrt(1e-5) in the device code)
 AGG_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5, "var_raw": 6, "std_pyg": 7}
@@ -363,6 +366,29 @@ class PnaTowerEdgeTrainArgs(_Args):
     ]
 
 
+class PnaEmbedSumArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("V", ctypes.c_int32), ("n_table", ctypes.c_int32), ("F", ctypes.c_int32), ("_pad0", ctypes.c_int32),
+        ("idx", ctypes.c_void_p), ("ld_idx", ctypes.c_int64),
+        ("table", ctypes.c_void_p * PNA_MAX_EMBED_TABLE), ("rows", ctypes.c_int32 * PNA_MAX_EMBED_TABLE),
+        ("ld_table", ctypes.c_int64 * PNA_MAX_EMBED_TABLE),
+        ("out", ctypes.c_void_p), ("ld_out", ctypes.c_int64), ("grad_out", ctypes.c_void_p), ("ld_go", ctypes.c_int64),
+        ("grad_table", ctypes.c_void_p * PNA_MAX_EMBED_TABLE),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
+class PnaReadoutArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("offsets", ctypes.c_void_p), ("G", ctypes.c_int32), ("V", ctypes.c_int32), ("F", ctypes.c_int32), ("op", ctypes.c_int32),
+        ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("out", ctypes.c_void_p), ("ld_out", ctypes.c_int64),
+        ("argmax", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("ld_go", ctypes.c_int64),
+        ("grad_h", ctypes.c_void_p), ("ld_gh", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -516,6 +542,14 @@ def lib():
         L.pna_tower_edge_train_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_tower_edge_train_fwd_f32, L.pna_tower_edge_train_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaTowerEdgeTrainArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_embed_sum_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
+        L.pna_embed_sum_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_embed_sum_fwd_f32, L.pna_embed_sum_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaEmbedSumArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        for fn in (L.pna_readout_fwd_f32, L.pna_readout_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaReadoutArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")

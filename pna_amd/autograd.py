@@ -1096,3 +1096,124 @@ def tower_layer_edge_small_train(layer, graph, h, e, snorm_n, scales):
         snorm = snorm_n.reshape(-1)
         snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
     return TowerLayerEdgeSmallTrainFn.apply(h, e, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)
+
+
+# ---- the two ends of the molecule nets: the sum of embedding tables and the per-graph readout (pna_net_ends.hip) -----------------
+_embed_ws = {}      # device -> the embedding backward's reusable workspace (no graph is at hand where the encoder runs)
+
+
+def _embed_workspace(dev, nbytes):
+    """A cached fp32 buffer of at least `nbytes` on `dev`, grown when a larger call arrives.  Every launch writes what it reads and
+    nothing is carried in it between calls; one caller at a time per device and stream, like a graph's scratch."""
+    n = (nbytes + 3) // 4
+    buf = _embed_ws.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = _embed_ws[dev] = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    return buf
+
+
+def _embed_args(idx, tables):
+    a = _lib.PnaEmbedSumArgs()
+    T, F = len(tables), tables[0].shape[1]
+    a.V, a.n_table, a.F = idx.shape[0], T, F
+    if idx.dtype != torch.int64 or not idx.is_cuda:
+        raise TypeError("pna_amd: the embedding index must be an int64 tensor on the GPU")
+    a.idx, a.ld_idx = ctypes.c_void_p(idx.data_ptr()), idx.stride(0)
+    for j, w in enumerate(tables):
+        a.table[j], a.rows[j], a.ld_table[j] = _lib.dev_ptr(w, torch.float32, "table").value, w.shape[0], w.stride(0)
+    return a
+
+
+class EmbedSumFn(torch.autograd.Function):
+    """out[v] = sum_j table_j[idx[v, j]] (ogb's AtomEncoder; one table: nn.Embedding) as ONE C call (pna_embed_sum_fwd_f32) and the
+    gradient of every table as one (pna_embed_sum_bwd_f32: no atomics, bitwise repeatable).  idx: int64 (V, n_table) with unit column
+    stride, or 1-D of any stride for one table.  The backward's workspace is a cached buffer; nothing is carried in it."""
+
+    @staticmethod
+    def forward(ctx, idx, *tables):
+        if idx.dim() == 2 and idx.stride(1) != 1:
+            idx = idx.contiguous()
+        tables = tuple(w if w.stride(1) == 1 else w.contiguous() for w in tables)
+        dev = tables[0].device
+        out = torch.empty(idx.shape[0], tables[0].shape[1], dtype=torch.float32, device=dev)
+        a = _embed_args(idx, tables)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        _lib.check(_lib.lib().pna_embed_sum_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_embed_sum_fwd_f32")
+        ctx.save_for_backward(idx, *tables)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        idx, *tables = ctx.saved_tensors
+        dev = go.device
+        go = go if go.stride(1) == 1 else go.contiguous()
+        a = _embed_args(idx, tables)
+        F = tables[0].shape[1]
+        rows = [w.shape[0] for w in tables]
+        flat = torch.empty(sum(rows) * F, dtype=torch.float32, device=dev)     # every table's gradient, one allocation
+        grads, at = [], 0
+        for j, r in enumerate(rows):
+            grads.append(flat[at:at + r * F].view(r, F))
+            a.grad_table[j] = flat.data_ptr() + 4 * at
+            at += r * F
+        # pna_embed_sum_workspace_bytes' formula (tests/test_net_ends_host.py holds the two together): one image of all tables per slab
+        V = idx.shape[0]
+        slab = max(_lib.PNA_EMBED_SLAB_ROWS, -(-V // _lib.PNA_EMBED_MAX_SLABS))
+        nbytes = -(-V // slab) * sum(rows) * ((F + 3) // 4 * 4) * 4
+        ws = _embed_workspace(dev, nbytes + 16)
+        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
+        _lib.check(_lib.lib().pna_embed_sum_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_embed_sum_bwd_f32")
+        return (None, *[g if ctx.needs_input_grad[1 + j] else None for j, g in enumerate(grads)])
+
+
+def embed_sum(idx, tables):
+    """sum_j tables[j][idx[:, j]] through EmbedSumFn."""
+    return EmbedSumFn.apply(idx, *tables)
+
+
+def _readout_args(offsets, G, V, F, op):
+    a = _lib.PnaReadoutArgs()
+    a.offsets = _lib.dev_ptr(offsets, torch.int32, "offsets")
+    a.G, a.V, a.F, a.op = G, V, F, _lib.AGG_CODES[op]
+    return a
+
+
+class ReadoutFn(torch.autograd.Function):
+    """(G, F) sum / mean / max of the node rows of every graph of a batch (dgl.sum_nodes / mean_nodes / max_nodes) as ONE C call
+    (pna_readout_fwd_f32) and its backward as one (pna_readout_bwd_f32).  offsets: int32 [G + 1], the contiguous node range of every
+    graph, none empty.  No workspace; max keeps its (G, F) arg rows for the backward."""
+
+    @staticmethod
+    def forward(ctx, h, offsets, op):
+        h = h if h.stride(1) == 1 else h.contiguous()
+        V, F = h.shape
+        G = offsets.numel() - 1
+        dev = h.device
+        out = torch.empty(G, F, dtype=torch.float32, device=dev)
+        arg = torch.empty(G, F, dtype=torch.int32, device=dev) if op == "max" else None
+        a = _readout_args(offsets, G, V, F, op)
+        a.h, a.ldh = _lib.dev_ptr(h, torch.float32, "h"), h.stride(0)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        a.argmax = _lib.dev_ptr(arg, torch.int32, "argmax")
+        _lib.check(_lib.lib().pna_readout_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_readout_fwd_f32")
+        ctx.offsets, ctx.op, ctx.shape, ctx.arg = offsets, op, (G, V, F), arg
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        G, V, F = ctx.shape
+        dev = go.device
+        go = go if go.stride(1) == 1 else go.contiguous()
+        gh = torch.empty(V, F, dtype=torch.float32, device=dev)
+        a = _readout_args(ctx.offsets, G, V, F, ctx.op)
+        a.argmax = _lib.dev_ptr(ctx.arg, torch.int32, "argmax")
+        a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
+        a.grad_h, a.ld_gh = _lib.dev_ptr(gh, torch.float32, "grad_h"), gh.stride(0)
+        _lib.check(_lib.lib().pna_readout_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_readout_bwd_f32")
+        return gh, None, None
+
+
+def readout(h, offsets, op):
+    """Per-graph sum / mean / max of h's rows through ReadoutFn."""
+    return ReadoutFn.apply(h, offsets, op)

@@ -1222,6 +1222,34 @@ def small_tower_train_edge_fits(T, Fi, Fo, S=3, edge_dim=0):
     return small_tower_train_fits(T, Fi, Fo, S) and 1 <= edge_dim <= 64
 
 
+# The two ENDS of the molecule nets -- the sum of embedding tables (AtomEncoderStandIn, nets.embed) and the per-graph readout
+# (nets.readout_nodes) -- take the one-call route (autograd.EmbedSumFn / ReadoutFn: pna_embed_sum_*_f32, pna_readout_*_f32) on calls of up
+# to this many rows.  0 = off, the default
+NET_ENDS_ROWS = int(os.environ.get("PNA_AMD_NET_ENDS_ROWS", "0"))
+
+
+def embed_sum_fits(rows, F):
+    """Mirror of pna_embed_sum_*_f32's scope: 1..16 tables of >= 1 rows, 1 <= F <= 256, and ONE fp32 image of all tables --
+    sum_j rows_j x round4(F) floats -- within 128 KiB of LDS (the atom encoder at F = 128: 88 576 bytes)."""
+    if not (1 <= len(rows) <= _lib.PNA_MAX_EMBED_TABLE and 1 <= F <= 256 and all(r >= 1 for r in rows)):
+        return False
+    return sum(rows) * ((F + 3) // 4 * 4) * 4 <= 128 * 1024
+
+
+def embed_sum_slab_rows(V):
+    """Rows per slab of pna_embed_sum_bwd_f32 (a slab = one workgroup = one workspace slot): at least PNA_EMBED_SLAB_ROWS, and long
+    enough that there are never more than PNA_EMBED_MAX_SLABS of them."""
+    return max(_lib.PNA_EMBED_SLAB_ROWS, -(-V // _lib.PNA_EMBED_MAX_SLABS))
+
+
+def embed_sum_workspace_bytes(V, rows, F):
+    """pna_embed_sum_workspace_bytes' formula: one image per slab; -1 outside the scope."""
+    if V < 1 or not embed_sum_fits(rows, F):
+        return -1
+    L = embed_sum_slab_rows(V)
+    return -(-V // L) * sum(rows) * ((F + 3) // 4 * 4) * 4
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")

@@ -48,9 +48,39 @@ class GRU(nn.Module):
         return self.gru(x.unsqueeze(0), y.unsqueeze(0))[1].squeeze()
 
 
+def _readout_path(graph, h):
+    """Whether this readout is served by pna_readout_fwd_f32 / _bwd_f32 (autograd.ReadoutFn: one C call each way): the knob
+    PNA_AMD_NET_ENDS_ROWS is on and covers the batch, fp32 rows on the GPU inside the call's width, one row per node, and no graph of the
+    batch is empty (the call's segments are non-empty node ranges).  No float is read and the device is not waited for."""
+    V = h.shape[0]
+    if not (PF.NET_ENDS_ROWS > 0 and 0 < V <= PF.NET_ENDS_ROWS):
+        return False
+    if not (h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and 1 <= h.shape[1] <= 512):
+        return False
+    if not (type(graph) is Graph and graph.num_nodes == V):
+        return False
+    return _readout_offsets(graph, h.device) is not None
+
+
+def _readout_offsets(graph, dev):
+    """int32 [n_graphs + 1] on `dev`: the node range of every graph of the batch (the readout graph's rowptr, without building that
+    graph), or None when a graph of the batch is empty or the sizes do not add up to the node count.  From the host-side size list,
+    kept with the graph's other derived arrays."""
+    key = ("readout_offsets", dev)
+    if key not in graph._heavy:
+        sizes = torch.tensor([0] + list(graph.batch_num_nodes), dtype=torch.int64)
+        ok = sizes.numel() >= 2 and int(sizes[1:].min()) >= 1 and int(sizes.sum()) == graph.num_nodes
+        graph._heavy[key] = sizes.cumsum(0).to(torch.int32).to(dev) if ok else None
+    return graph._heavy[key]
+
+
 def readout_nodes(g, h, op):
     """(n_graphs, F): sum / mean / max of the node rows of every graph of the batch -- one segment-reduce launch."""
     graph = as_graph(g)
+    if PF.NET_ENDS_ROWS > 0 and _readout_path(graph, h):
+        # a molecule batch: the graphs are contiguous node ranges, one C call each way (autograd.ReadoutFn)
+        from . import autograd as AG
+        return AG.readout(h, _readout_offsets(graph, h.device), op)
     key = ("readout", h.device)
     rg = graph._heavy.get(key)
     if rg is None:
@@ -177,10 +207,33 @@ class _SmallTableEmbedding(torch.autograd.Function):
         return gw, None
 
 
+def _embed_sum_path(embs, idx):
+    """Whether sum_j embs[j](idx[:, j]) is served by pna_embed_sum_fwd_f32 / _bwd_f32 (autograd.EmbedSumFn: one C call each way, train
+    or eval, with or without grad): the knob PNA_AMD_NET_ENDS_ROWS is on and covers the rows, the index is int64 on the GPU with one
+    column per table (1-D for a single table), every table is a plain fp32 nn.Embedding on the same GPU (no padding_idx, no max_norm)
+    of one width, and the tables fit the call's scope (functional.embed_sum_fits).  Indices are not looked at: the calls clamp them."""
+    V = idx.shape[0] if idx.dim() >= 1 else 0
+    if not (PF.NET_ENDS_ROWS > 0 and 0 < V <= PF.NET_ENDS_ROWS):
+        return False
+    if not (idx.dtype == torch.int64 and idx.is_cuda):
+        return False
+    if not ((idx.dim() == 1 and len(embs) == 1) or (idx.dim() == 2 and idx.shape[1] == len(embs))):
+        return False
+    if any(type(e) is not nn.Embedding or e.padding_idx is not None or e.max_norm is not None for e in embs):
+        return False
+    ws = [e.weight for e in embs]
+    if any(w.dtype != torch.float32 or w.device != idx.device or w.shape[1] != ws[0].shape[1] for w in ws):
+        return False
+    return PF.embed_sum_fits([w.shape[0] for w in ws], ws[0].shape[1])
+
+
 def embed(emb: nn.Embedding, idx):
     """emb(idx) for the small categorical vocabularies of the molecule nets (same values, faster backward)."""
     if emb.padding_idx is not None or emb.max_norm is not None or idx.dim() != 1:
         return emb(idx)
+    if PF.NET_ENDS_ROWS > 0 and _embed_sum_path([emb], idx):
+        from . import autograd as AG
+        return AG.embed_sum(idx, [emb.weight])
     return _SmallTableEmbedding.apply(emb.weight, idx)
 
 
@@ -196,6 +249,10 @@ class AtomEncoderStandIn(nn.Module):
             nn.init.xavier_uniform_(emb.weight.data)
 
     def forward(self, x):
+        if PF.NET_ENDS_ROWS > 0 and _embed_sum_path(list(self.atom_embedding_list), x):
+            # a molecule batch: the nine lookups and their sum as one C call, the nine table gradients as another (autograd.EmbedSumFn)
+            from . import autograd as AG
+            return AG.embed_sum(x, [emb.weight for emb in self.atom_embedding_list])
         out = 0
         for i, emb in enumerate(self.atom_embedding_list):
             out = out + embed(emb, x[:, i])
