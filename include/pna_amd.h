@@ -566,7 +566,7 @@ int pna_fused_simple_f32(const pna_fused_simple_args* args, pna_stream_t stream)
  *     |acc| >= 2^34 fs(v) + 2^35 fw(n)          (floor error <= 2^-20 |acc|: everything else of the split's error is relative term by term);
  * a 64-row (wide shapes: 64-row) workgroup tile with an uncertified output is appended to a device-side list and a second launch computes
  * exactly those tiles again in bf16 x 3 (no host round trip; on Gaussian features and weights nothing is handed over, the launch finds an
- * empty list and costs ~6 us).  In tower mode the row's scale also covers its own x_dst / h_self strips: it is lowered when they arrive,
+ * empty list and costs ~6 us; rows without in-edges outside tower mode have exact zeros for operands and certify themselves).  In tower mode the row's scale also covers its own x_dst / h_self strips: it is lowered when they arrive,
  * mid-row, and the accumulator with it (exact).  Measured against float64 on BASELINE configs[2] / [4] shapes: 1.25 x the error of bf16x3, a
  * fifth of an fp32 GEMM's.
  * Non-finite operands: NaN propagates; a row that holds an infinite statistic (column: an infinite weight) is non-finite in every output
@@ -580,13 +580,16 @@ int pna_fused_simple_f32(const pna_fused_simple_args* args, pna_stream_t stream)
  *   tile_ids      n_records records of 16 int32: record (first + e)[i] = source row (row of x) of the e-th in-edge of the block's
  *                 i-th row, e in [0, D), in the row's edge order; a padding row repeats the block's first row; a block owns
  *                 max(4, round_up(D, 4)) records, the ones past D being copies of record D - 1 (D = 0: any valid row);
+ *                 D is ANY in-degree >= 0 -- the degrees of a tile's four (eight) blocks may all differ, and nothing ties D to the
+ *                 caller's hub threshold: the only limit is n_records < 2^26 (tests/test_gpu_fused_degree_plans.py pins D = 0 .. 9,
+ *                 12, 13, 16, 17, 31 .. 33, 127 .. 129 and 300, one degree per tile and four per tile);
  *   w_img         n_img images, image_stride == pna_fused_image_bytes(F, N, tower, 0) bytes apart (the pack function's layout), from pna_fused_pack_f32
  *                 (w_img_x3 / image_stride_x3: the bf16 x 3 images, x3 = 1):
  *                 w_ref is the Linear weight (N, n_scaler * 4F) in the reference's column order [scaler][aggregator][feature]
  *                 (pna_layer.py:192-193), scale (n_img, n_scaler) the scalers' values for image i (NULL with n_scaler = 1:
  *                 the weight itself); W_D is formed in fp32 in scaler order, like the reference's blocks.
- * x: (x_rows, ldx) rows, 16-byte aligned, ldx % 4 == 0, ldx >= round_up(F, 8) (round_up(F, 4) when F % 32 is in 1..16),
- * x_rows < 2^24, table < 4 GiB; y and residual: n_nodes rows, each table < 4 GiB.
+ * x: (x_rows, ldx) rows, 4-byte aligned, any ldx >= F (a contiguous (x_rows, F) table included: no read leaves a row's F floats),
+ * x_rows < 2^32, ldx < 2^29; y and residual: n_nodes rows, each table < 4 GiB.
  * F in 17..80, or (ABI 15; 97..112 since ABI 21) 97..128 -- the features in two gather passes (BASELINE configs[4]: 128 -> 128);
  * N in 4..80, or (ABI 15) 81..128 -- the output columns in two panels of 64 (needs F in 49..64 or 97..128).  pna_fused_degree_image_bytes(F, N) > 0
  * is the authoritative test.

@@ -914,7 +914,9 @@ __device__ __forceinline__ void fd_body(const FDArgs& g, const int t_first, cons
       }
     }
     if constexpr (H2) {
-      if (guard_on && __builtin_amdgcn_ballot_w64(bad && row >= 0) != 0 && lane == 0)
+      // (a block without in-edges outside tower mode: every operand is an exact zero and so is the accumulator -- nothing to certify; without
+      //  this a column with a floor error of its own sent every tile that holds such rows to the second launch: tests/test_gpu_fused_degree_plans.py)
+      if (guard_on && (TOWER || deg > 0) && __builtin_amdgcn_ballot_w64(bad && row >= 0) != 0 && lane == 0)
         asm volatile("ds_or_b32 %0, %1" : : "v"(gflag_b + (unsigned)gpar * 4u), "v"(1u) : "memory");
     }
   };
