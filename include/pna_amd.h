@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_embed_sum_fwd_f32 / pna_embed_sum_bwd_f32 / pna_embed_sum_workspace_bytes / pna_embed_sum_args,
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_gru_cell_fwd_f32 / pna_gru_cell_bwd_f32 / pna_gru_cell_workspace_bytes / pna_gru_cell_args,
+                                  PNA_GRU_F32, PNA_GRU_SLAB_ROWS, PNA_GRU_MAX_SLABS (the GRU update between two message-passing steps: nn.GRU over
+                                  a length-1 sequence as a cell over rows, one call each way); no existing struct or entry point changed.
+                                  23, additive: + pna_embed_sum_fwd_f32 / pna_embed_sum_bwd_f32 / pna_embed_sum_workspace_bytes / pna_embed_sum_args,
                                   pna_readout_fwd_f32 / pna_readout_bwd_f32 / pna_readout_args, PNA_MAX_EMBED_TABLE (the two ends of the molecule
                                   nets: the sum of embedding tables and the per-graph readout, one call each way); no existing struct or entry
                                   point changed.
@@ -1660,6 +1663,86 @@ typedef struct pna_readout_args {
 
 int pna_readout_fwd_f32(const pna_readout_args* args, pna_stream_t stream);
 int pna_readout_bwd_f32(const pna_readout_args* args, pna_stream_t stream);
+
+/* ---- The GRU update between two message-passing steps: a GRU CELL over rows, one call each way ------------------------------------
+ * replaces: realworld_benchmark/nets/gru.py:5-30 (PNANet / PNANetSuperpixels with gru=True: nn.GRU over a length-1 sequence with the
+ * previous features as hidden state), models/layers.py:237-268 (the multitask GNN's GRU with its zero padding, shared by the N/2
+ * convolutions of models/pytorch/gnn_framework.py:60,93-95), and what autograd derives from them.
+ *
+ * Semantics: torch.nn.GRU, one layer, one direction, bias, sequence length 1; gate order in the 3H weight rows r, z, n:
+ *   gi = x W_ih^T + b_ih    gh = h W_hh^T + b_hh
+ *   r = sigmoid(gi_r + gh_r)    z = sigmoid(gi_z + gh_z)    n = tanh(gi_n + r gh_n)    out = (1 - z) n + z h
+ * x is (V, I) with 1 <= I <= input_size and h is (V, Hc) with 1 <= Hc <= hidden_size: the columns that are missing are the reference's
+ * zero padding (layers.py:260-264) and are never materialised (the K loops end there; z h is 0 there).  out is (V, hidden_size).
+ * sigmoid and tanh branch on the sign of their argument (1 / (1 + exp(-a)) or exp(a) / (1 + exp(a)); -m / (m + 2) with m = expm1(-2 |a|)):
+ * no overflow, no cancellation, exactly saturated and finite at +-100; exp / expm1 are the full-precision library functions.
+ *
+ * pna_gru_cell_fwd_f32 (one launch): a workgroup owns 16 rows; the x and h tiles sit in LDS; the two projections run on
+ *   v_mfma_f32_16x16x4_f32 (exact fp32 products) with B fragments read straight from the nn.GRU parameters (any row pitch); gi_n and gh_n
+ *   keep separate accumulators.  saved != NULL: r, z, n, gh_n are stored as (4, V, hidden_size) contiguous for the backward; NULL (no
+ *   gradient wanted): nothing is saved.
+ * pna_gru_cell_bwd_f32 (at most three launches, no atomics of any kind, bitwise repeatable):
+ *   (a) rows kernel: da_n = grad_out (1 - z) (1 - n)(1 + n), da_z = grad_out (h - n) z (1 - z), da_r = da_n gh_n r (1 - r);
+ *       dgi = [da_r | da_z | da_n], dgh = [da_r | da_z | da_n r]; grad_x = dgi W_ih (first I columns), grad_h = dgh W_hh + grad_out z
+ *       (first Hc columns): gradients of padded columns are not produced.
+ *   (b) per slab of L = max(PNA_GRU_SLAB_ROWS, ceil(V / PNA_GRU_MAX_SLABS)) consecutive rows: grad_W_ih = dgi^T x, grad_W_hh = dgh^T h and
+ *       the column sums grad_b_ih, grad_b_hh, into the slab's slot of the workspace.
+ *   (c) one thread per parameter element adds the slots in slab order in float64 and stores fp32.  EVERY element of a wanted parameter
+ *       gradient is written (grad_W_ih (3H, input_size) and grad_W_hh (3H, hidden_size) contiguous, zeros in the padded columns).
+ *   A gradient whose need_* flag is 0 is not written; (b) and (c) are not launched when no parameter gradient is wanted.
+ * Scope (PNA_E_INVALID outside it, pna_last_error names the clause; pna_gru_cell_workspace_bytes returns -1): fp32 only (dtype ==
+ * PNA_GRU_F32), 1 <= input_size <= 128, 2 <= hidden_size <= 128, V >= 2, 1 <= I <= input_size, 1 <= Hc <= hidden_size.
+ * workspace (backward only): pna_gru_cell_workspace_bytes(...) = 4 (V 4 hidden_size + n_slab 3 hidden_size (I + Hc + 2)) bytes, 16-byte
+ * aligned, no initialisation: no launch reads what the call has not written. */
+#define PNA_GRU_F32 0
+#define PNA_GRU_SLAB_ROWS 64
+#define PNA_GRU_MAX_SLABS 64
+typedef struct pna_gru_cell_args {
+  uint32_t struct_size;    /* sizeof(pna_gru_cell_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  int64_t V;               /* rows */
+  int32_t I;               /* columns of x */
+  int32_t Hc;              /* columns of h */
+  int32_t input_size;      /* columns of w_ih */
+  int32_t hidden_size;     /* H: columns of w_hh and of out; both weights have 3H rows */
+  int32_t dtype;           /* PNA_GRU_F32 */
+  int32_t _pad0;
+  const float* x;          /* (V, ldx >= I) */
+  int64_t ldx;
+  const float* h;          /* (V, ldh >= Hc) */
+  int64_t ldh;
+  const float* w_ih;       /* (3H, ld_wih >= input_size): nn.GRU.weight_ih_l0 as it is */
+  int64_t ld_wih;
+  const float* w_hh;       /* (3H, ld_whh >= H): nn.GRU.weight_hh_l0 as it is */
+  int64_t ld_whh;
+  const float* b_ih;       /* [3H] (forward) */
+  const float* b_hh;       /* [3H] (forward) */
+  float* out;              /* forward (V, ld_out >= H) */
+  int64_t ld_out;
+  float* saved;            /* (4, V, H) contiguous: r | z | n | gh_n; forward writes (NULL = not kept), backward reads */
+  const float* grad_out;   /* backward (V, ld_go >= H) */
+  int64_t ld_go;
+  float* grad_x;           /* backward (V, ld_gx >= I) */
+  int64_t ld_gx;
+  float* grad_h;           /* backward (V, ld_gh >= Hc) */
+  int64_t ld_gh;
+  float* grad_w_ih;        /* backward (3H, input_size) contiguous */
+  float* grad_w_hh;        /* backward (3H, H) contiguous */
+  float* grad_b_ih;        /* backward [3H] */
+  float* grad_b_hh;        /* backward [3H] */
+  int32_t need_x;          /* backward: 0 = that gradient is not computed and its buffer (may be NULL) is not written */
+  int32_t need_h;
+  int32_t need_w_ih;
+  int32_t need_w_hh;
+  int32_t need_b_ih;
+  int32_t need_b_hh;
+  void* workspace;         /* backward */
+  int64_t workspace_bytes;
+} pna_gru_cell_args;
+
+int64_t pna_gru_cell_workspace_bytes(int64_t V, int32_t I, int32_t Hc, int32_t hidden_size);   /* -1 outside the scope */
+int pna_gru_cell_fwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
+int pna_gru_cell_bwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -20,6 +20,9 @@ PNA_MAX_TOWER = 8
 PNA_MAX_EMBED_TABLE = 16
 PNA_EMBED_SLAB_ROWS = 64        # pna_embed_sum_bwd_f32: a slab is max(this, ceil(V / PNA_EMBED_MAX_SLABS)) rows
 PNA_EMBED_MAX_SLABS = 256
+PNA_GRU_F32 = 0
+PNA_GRU_SLAB_ROWS = 64          # pna_gru_cell_bwd_f32: a slab is max(this, ceil(V / PNA_GRU_MAX_SLABS)) rows
+PNA_GRU_MAX_SLABS = 64
 
 # (std_pyg: the bf16 entry points only -- the PyG std, whose row without in-edges is sqrt(1e-5) in the device code)
 AGG_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5, "var_raw": 6, "std_pyg": 7}
@@ -389,6 +392,24 @@ class PnaReadoutArgs(_Args):
     ]
 
 
+class PnaGruCellArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("V", ctypes.c_int64), ("I", ctypes.c_int32), ("Hc", ctypes.c_int32), ("input_size", ctypes.c_int32), ("hidden_size", ctypes.c_int32),
+        ("dtype", ctypes.c_int32), ("_pad0", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64),
+        ("w_ih", ctypes.c_void_p), ("ld_wih", ctypes.c_int64), ("w_hh", ctypes.c_void_p), ("ld_whh", ctypes.c_int64),
+        ("b_ih", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+        ("out", ctypes.c_void_p), ("ld_out", ctypes.c_int64), ("saved", ctypes.c_void_p),
+        ("grad_out", ctypes.c_void_p), ("ld_go", ctypes.c_int64), ("grad_x", ctypes.c_void_p), ("ld_gx", ctypes.c_int64),
+        ("grad_h", ctypes.c_void_p), ("ld_gh", ctypes.c_int64),
+        ("grad_w_ih", ctypes.c_void_p), ("grad_w_hh", ctypes.c_void_p), ("grad_b_ih", ctypes.c_void_p), ("grad_b_hh", ctypes.c_void_p),
+        ("need_x", ctypes.c_int32), ("need_h", ctypes.c_int32), ("need_w_ih", ctypes.c_int32), ("need_w_hh", ctypes.c_int32),
+        ("need_b_ih", ctypes.c_int32), ("need_b_hh", ctypes.c_int32),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -550,6 +571,11 @@ def lib():
             fn.restype = ctypes.c_int
         for fn in (L.pna_readout_fwd_f32, L.pna_readout_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaReadoutArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_gru_cell_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        L.pna_gru_cell_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_gru_cell_fwd_f32, L.pna_gru_cell_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaGruCellArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")

@@ -1217,3 +1217,101 @@ class ReadoutFn(torch.autograd.Function):
 def readout(h, offsets, op):
     """Per-graph sum / mean / max of h's rows through ReadoutFn."""
     return ReadoutFn.apply(h, offsets, op)
+
+
+# ---- the GRU update between two message-passing steps: nn.GRU over a length-1 sequence as a cell over rows (pna_gru.hip) -------------
+_gru_ws = {}        # device -> the backward's reusable workspace; nothing is keyed per module: a shared GRU has several calls alive
+
+
+def _gru_workspace(dev, nbytes):
+    """A cached fp32 buffer of at least `nbytes` (+ 16 for alignment) on `dev`, ONE per device, grown when a larger call arrives
+    (_embed_workspace's scheme: molecule batches have another row count every step, so a buffer per size would never stop growing).
+    Every launch writes what it reads and nothing is carried in it between calls; one caller at a time per device and stream."""
+    n = (nbytes + 16 + 3) // 4
+    buf = _gru_ws.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = _gru_ws[dev] = torch.empty(n, dtype=torch.float32, device=dev)
+    return buf
+
+
+def _gru_rows(t):
+    """t as rows the calls take: unit column stride and a row pitch of at least the width (an expanded tensor has pitch 0)."""
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def _gru_saved(V, H, dev):
+    """The saved state of ONE call, (4, V, H): r | z | n | gh_n.  Allocated per call -- a shared GRU keeps one per application alive."""
+    return torch.empty(4, V, H, dtype=torch.float32, device=dev)
+
+
+def _gru_args(x, h, w_ih, w_hh):
+    a = _lib.PnaGruCellArgs()
+    a.V, a.I, a.Hc, a.input_size, a.hidden_size, a.dtype = x.shape[0], x.shape[1], h.shape[1], w_ih.shape[1], w_hh.shape[1], _lib.PNA_GRU_F32
+    a.x, a.ldx = _lib.dev_ptr(x, torch.float32, "x"), x.stride(0)
+    a.h, a.ldh = _lib.dev_ptr(h, torch.float32, "h"), h.stride(0)
+    a.w_ih, a.ld_wih = _lib.dev_ptr(w_ih, torch.float32, "weight_ih"), w_ih.stride(0)
+    a.w_hh, a.ld_whh = _lib.dev_ptr(w_hh, torch.float32, "weight_hh"), w_hh.stride(0)
+    return a
+
+
+class GruCellFn(torch.autograd.Function):
+    """torch.nn.GRU (one layer, one direction, bias) over a length-1 sequence as ONE C call (pna_gru_cell_fwd_f32) and its backward as
+    one (pna_gru_cell_bwd_f32: at most three launches, no atomics, bitwise repeatable).  x: (V, I <= input_size), h: (V, Hc <=
+    hidden_size), fp32 with unit column stride and any row pitch; missing columns are zero padding, never materialised.  Once
+    differentiable.  The saved state is allocated per call (`keep`; not at all under no_grad or when nothing requires a gradient); the
+    workspace is one cached buffer per device, grown on demand."""
+
+    @staticmethod
+    def forward(ctx, x, h, w_ih, w_hh, b_ih, b_hh, keep):
+        x, h, w_ih, w_hh = _gru_rows(x), _gru_rows(h), _gru_rows(w_ih), _gru_rows(w_hh)
+        b_ih, b_hh = b_ih.contiguous(), b_hh.contiguous()
+        dev, V, H = x.device, x.shape[0], w_hh.shape[1]
+        out = torch.empty(V, H, dtype=torch.float32, device=dev)
+        saved = _gru_saved(V, H, dev) if keep else None
+        a = _gru_args(x, h, w_ih, w_hh)
+        a.b_ih, a.b_hh = _lib.dev_ptr(b_ih, torch.float32, "bias_ih"), _lib.dev_ptr(b_hh, torch.float32, "bias_hh")
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        a.saved = _lib.dev_ptr(saved, torch.float32, "saved")
+        _lib.check(_lib.lib().pna_gru_cell_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_gru_cell_fwd_f32")
+        if saved is not None:
+            ctx.save_for_backward(x, h, w_ih, w_hh, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        x, h, w_ih, w_hh, saved = ctx.saved_tensors
+        dev, V, H = go.device, x.shape[0], w_hh.shape[1]
+        I, Hc, IN = x.shape[1], h.shape[1], w_ih.shape[1]
+        go = _gru_rows(go)                                     # (the cotangent of out.sum(0) is an expand: strides (0, 1))
+        need = ctx.needs_input_grad
+        a = _gru_args(x, h, w_ih, w_hh)
+        a.saved = _lib.dev_ptr(saved, torch.float32, "saved")
+        a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
+        gx = torch.empty(V, I, dtype=torch.float32, device=dev) if need[0] else None
+        gh = torch.empty(V, Hc, dtype=torch.float32, device=dev) if need[1] else None
+        gwi = torch.empty(3 * H, IN, dtype=torch.float32, device=dev) if need[2] else None
+        gwh = torch.empty(3 * H, H, dtype=torch.float32, device=dev) if need[3] else None
+        gbi = torch.empty(3 * H, dtype=torch.float32, device=dev) if need[4] else None
+        gbh = torch.empty(3 * H, dtype=torch.float32, device=dev) if need[5] else None
+        if gx is not None:
+            a.grad_x, a.ld_gx = _lib.dev_ptr(gx, torch.float32, "grad_x"), gx.stride(0)
+        if gh is not None:
+            a.grad_h, a.ld_gh = _lib.dev_ptr(gh, torch.float32, "grad_h"), gh.stride(0)
+        a.grad_w_ih, a.grad_w_hh = _lib.dev_ptr(gwi, torch.float32, "grad_w_ih"), _lib.dev_ptr(gwh, torch.float32, "grad_w_hh")
+        a.grad_b_ih, a.grad_b_hh = _lib.dev_ptr(gbi, torch.float32, "grad_b_ih"), _lib.dev_ptr(gbh, torch.float32, "grad_b_hh")
+        a.need_x, a.need_h, a.need_w_ih, a.need_w_hh, a.need_b_ih, a.need_b_hh = [int(bool(n)) for n in need[:6]]
+        # pna_gru_cell_workspace_bytes' formula (tests/test_gru_host.py holds the two together)
+        slab = max(_lib.PNA_GRU_SLAB_ROWS, -(-V // _lib.PNA_GRU_MAX_SLABS))
+        nbytes = 4 * (V * 4 * H + -(-V // slab) * 3 * H * (I + Hc + 2))
+        ws = _gru_workspace(dev, nbytes)
+        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        _lib.check(_lib.lib().pna_gru_cell_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_gru_cell_bwd_f32")
+        return gx, gh, gwi, gwh, gbi, gbh, None
+
+
+def gru_cell(x, h, gru):
+    """One step of `gru` (an nn.GRU: one layer, one direction, bias) from hidden rows h on input rows x through GruCellFn.  The state the
+    backward needs is kept only when one will come: grad mode on and an input or parameter that requires a gradient."""
+    ts = (x, h, gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)
+    return GruCellFn.apply(*ts, torch.is_grad_enabled() and any(t.requires_grad for t in ts))

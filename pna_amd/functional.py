@@ -1250,6 +1250,32 @@ def embed_sum_workspace_bytes(V, rows, F):
     return -(-V // L) * sum(rows) * ((F + 3) // 4 * 4) * 4
 
 
+# The GRU update between two message-passing steps (nets.GRU, layers.GRU: nn.GRU over a length-1 sequence) takes the one-call route
+# (autograd.GruCellFn: pna_gru_cell_fwd_f32 / _bwd_f32) on calls of 2 .. this many rows.  0 = off, the default
+GRU_ROWS = int(os.environ.get("PNA_AMD_GRU_ROWS", "0"))
+
+
+def gru_cell_fits(I, Hc, input_size, hidden_size):
+    """Mirror of pna_gru_cell_*_f32's scope in the widths: 1 <= input_size <= 128, 2 <= hidden_size <= 128, 1 <= I <= input_size columns
+    of x and 1 <= Hc <= hidden_size columns of h (the missing ones are the reference's zero padding)."""
+    return 1 <= input_size <= 128 and 2 <= hidden_size <= 128 and 1 <= I <= input_size and 1 <= Hc <= hidden_size
+
+
+def gru_cell_slab_rows(V):
+    """Rows per slab of pna_gru_cell_bwd_f32's weight gradient (a slab = one workspace slot): at least PNA_GRU_SLAB_ROWS, and long enough
+    that there are never more than PNA_GRU_MAX_SLABS of them."""
+    return max(_lib.PNA_GRU_SLAB_ROWS, -(-V // _lib.PNA_GRU_MAX_SLABS))
+
+
+def gru_cell_workspace_bytes(V, I, Hc, hidden_size):
+    """pna_gru_cell_workspace_bytes' formula: dgi / dgh as (V, 4H) and one image of the four parameter gradients per slab; -1 outside
+    the scope."""
+    if V < 2 or V >= 2 ** 31 or not gru_cell_fits(I, Hc, 128, hidden_size):
+        return -1
+    L = gru_cell_slab_rows(V)
+    return 4 * (V * 4 * hidden_size + -(-V // L) * 3 * hidden_size * (I + Hc + 2))
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")

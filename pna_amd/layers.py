@@ -1,4 +1,4 @@
-"""Dense blocks the PNA layers are assembled from: `FCLayer` and `MLP`.
+"""Dense blocks the PNA layers are assembled from: `FCLayer`, `MLP` and `GRU`.
 
 Same constructor arguments, forward order (linear -> activation -> dropout -> batch-norm), weight
 initialisation and state_dict keys (`fully_connected.{k}.linear.{weight,bias}`) as the reference's
@@ -104,3 +104,40 @@ class MLP(nn.Module):
         for fc in self.fully_connected[1:]:
             x = fc(x)
         return x
+
+
+class GRU(nn.Module):
+    """models/layers.py:237-268: the multitask GNN's GRU -- nn.GRU over a length-1 sequence on (B, N, Din <= input_size) inputs with
+    (B, N, Dh <= hidden_size) hidden rows, the difference zero-padded; (B, N, hidden_size) out.  Same parameter names
+    (`gru.weight_ih_l0` .. `gru.bias_hh_l0`).  With PNA_AMD_GRU_ROWS on and the call in scope (nets.gru_one_call_path) the update is one C
+    call each way on the (B N, D) views, the padding expressed through the column counts; otherwise exactly the reference's lines."""
+
+    def __init__(self, input_size, hidden_size, device):
+        super().__init__()
+        self.input_size, self.hidden_size = input_size, hidden_size
+        self.gru = nn.GRU(input_size=input_size, hidden_size=hidden_size).to(device)
+
+    def _one_call_path(self, x, y):
+        """nets.GRU._one_call_path on the (B N, D) views of 3-D x and y (a reshape that would copy declines)."""
+        from . import functional as PF
+        if not PF.GRU_ROWS > 0:
+            return False
+        if not (x.dim() == 3 and y.dim() == 3 and x.shape[:2] == y.shape[:2] and x.is_contiguous() and y.is_contiguous()):
+            return False
+        from .nets import gru_one_call_path
+        return gru_one_call_path(self.gru, x.reshape(x.shape[0] * x.shape[1], -1), y.reshape(y.shape[0] * y.shape[1], -1))
+
+    def forward(self, x, y):
+        assert (x.shape[-1] <= self.input_size and y.shape[-1] <= self.hidden_size)
+        (B, N, _) = x.shape
+        if self._one_call_path(x, y):
+            from .autograd import gru_cell
+            return gru_cell(x.reshape(B * N, -1), y.reshape(B * N, -1), self.gru).reshape(B, N, -1)
+        x = x.reshape(1, B * N, -1).contiguous()
+        y = y.reshape(1, B * N, -1).contiguous()
+        if x.shape[-1] < self.input_size:
+            x = F.pad(input=x, pad=[0, self.input_size - x.shape[-1]], mode='constant', value=0)
+        if y.shape[-1] < self.hidden_size:
+            y = F.pad(input=y, pad=[0, self.hidden_size - y.shape[-1]], mode='constant', value=0)
+        x = self.gru(x, y)[1]
+        return x.reshape(B, N, -1)

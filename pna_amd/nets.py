@@ -43,9 +43,39 @@ class GRU(nn.Module):
         self.input_size, self.hidden_size = input_size, hidden_size
         self.gru = nn.GRU(input_size=input_size, hidden_size=hidden_size).to(device)
 
+    def _one_call_path(self, x, y):
+        """Whether this update is served by pna_gru_cell_fwd_f32 / _bwd_f32 (autograd.GruCellFn: one C call each way, train and eval,
+        with and without grad): the knob PNA_AMD_GRU_ROWS is on and covers the rows (2 <= V: one row's `.squeeze()` has another shape),
+        x and y are 2-D fp32 on the GPU with unit column stride and a row pitch of at least the width, the nn.GRU is one layer, one
+        direction, bias=True, batch_first=False with its four parameters fp32 on that GPU, and the widths fit the call
+        (functional.gru_cell_fits).  No float is read."""
+        return gru_one_call_path(self.gru, x, y)
+
     def forward(self, x, y):
         assert x.shape[-1] <= self.input_size and y.shape[-1] <= self.hidden_size
+        if PF.GRU_ROWS > 0 and self._one_call_path(x, y):
+            from . import autograd as AG
+            return AG.gru_cell(x, y, self.gru)
         return self.gru(x.unsqueeze(0), y.unsqueeze(0))[1].squeeze()
+
+
+def gru_one_call_path(gru, x, y):
+    """nets.GRU._one_call_path for an nn.GRU and (V, I) / (V, Hc) rows (layers.GRU asks for its (B N, D) views)."""
+    if not PF.GRU_ROWS > 0:
+        return False
+    if not (x.dim() == 2 and y.dim() == 2 and x.shape[0] == y.shape[0] and 2 <= x.shape[0] <= PF.GRU_ROWS):
+        return False
+    for t in (x, y):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+            return False
+    if not (type(gru) is nn.GRU and gru.num_layers == 1 and not gru.bidirectional and gru.bias and not gru.batch_first and
+            getattr(gru, "proj_size", 0) == 0 and gru.dropout == 0):
+        return False
+    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+        p = getattr(gru, name, None)
+        if p is None or not (p.is_cuda and p.dtype == torch.float32 and p.device == x.device and p.device == y.device):
+            return False
+    return PF.gru_cell_fits(x.shape[1], y.shape[1], gru.input_size, gru.hidden_size)
 
 
 def _readout_path(graph, h):
