@@ -814,7 +814,7 @@ int pna_tower_layer_f32(const pna_tower_layer_args* args, pna_stream_t stream);
  *   grad_b[n]               = sum_m gy[m, n]                                (grad_b nullable)
  *
  * bf16x3 arithmetic (each fp32 operand cut exactly into three bf16 terms, six partial products, fp32 accumulation per slab of
- * rows, float64 across the slabs in a fixed order: deterministic).  Shapes: 1 <= n_scaler <= 3, n_scaler * N <= 240,
+ * rows, float64 across the slabs in a fixed order: deterministic).  Shapes: 1 <= n_scaler <= 3, N <= 128, n_scaler * N <= 240,
  * K + Kh + 1 <= 384 (pna_posttrans_dw_workspace_bytes returns -1 otherwise: the caller keeps its library route); rows 4-byte
  * aligned; with an h panel or grad_b, row_scale[0] must be NULL (they are formed from the first copy of gy -- the identity scaler
  * comes first in every reference configuration).  Non-finite inputs give NaN in the columns / rows they touch.  workspace: no
@@ -1369,7 +1369,7 @@ int pna_gather_rows_bf16(const pna_gather_rows_bf16_args* args, pna_stream_t str
  * order: for in-degrees <= 128 the saved aggregate and arg indices carry pna_segreduce_fwd_f32's bits and tie rule); in-degrees
  * < 65535 in the backward (16-bit ranks of the pull).  fp32 throughout; the contractions are exact-product fp32 MFMAs
  * (v_mfma_f32_16x16x4_f32) except the weight gradient, which is pna_posttrans_dw_f32's kernel (bf16x3) where that kernel's shape
- * limits hold (n_scaler * N <= 240, 4 F + 1 <= 384) and a plain fp32 kernel otherwise.  NO float atomics: every sum has a fixed order, repeated
+ * limits hold (N <= 128 -- this scope's own cap --, n_scaler * N <= 240, 4 F + 1 <= 384) and a plain fp32 kernel otherwise.  NO float atomics: every sum has a fixed order, repeated
  * calls give identical bits.
  *
  * pna_simple_train_fwd_f32 (three launches):

@@ -424,8 +424,12 @@ __global__ __launch_bounds__(512) void k_posttrans_dw_grouped_reduce(const GRArg
   }
 }
 
+constexpr int kMaxN = 128;             // columns of gy the conversion units stage: two blocks of 64 lanes (u & 1 in k_posttrans_dw)
+
 int plan(int64_t M, int N, int S, int K, int Kh, long* slab, long* n_slab, int* nth) {
-  if (M < 1 || N < 1 || S < 1 || S > 3 || K < 1 || Kh < 0 || S * N > kMA || K + Kh + 1 > kMaxR) return 0;
+  // N > 128 (only possible with one scaler under S N <= 240) is refused: columns 128 .. of gy would never reach LDS, and rows 128 .. of
+  // grad_w / grad_b would come back as the zeros of the LDS clear
+  if (M < 1 || N < 1 || N > kMaxN || S < 1 || S > 3 || K < 1 || Kh < 0 || S * N > kMA || K + Kh + 1 > kMaxR) return 0;
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   *nth = (K + Kh + 1 + kNB - 1) / kNB;
@@ -453,7 +457,7 @@ extern "C" int pna_posttrans_dw_f32(const pna_posttrans_dw_args* p, pna_stream_t
     return pna_set_error(PNA_E_INVALID, "pna_posttrans_dw_f32: null argument");
   long slab, n_slab; int nth;
   if (!plan(p->M, p->N, p->n_scaler, p->K, p->Kh, &slab, &n_slab, &nth))
-    return pna_set_error(PNA_E_INVALID, "pna_posttrans_dw_f32: unsupported shape (n_scaler in 1..3, n_scaler * N <= 240, K + Kh + 1 <= 384; "
+    return pna_set_error(PNA_E_INVALID, "pna_posttrans_dw_f32: unsupported shape (n_scaler in 1..3, N <= 128, n_scaler * N <= 240, K + Kh + 1 <= 384; "
                                         "pna_posttrans_dw_workspace_bytes returns -1 for it)");
   if (p->ldg < p->N || p->lda < p->K || (p->Kh > 0 && p->ldh < p->Kh) || p->ldw < p->Kh + (int64_t)p->n_scaler * p->K)
     return pna_set_error(PNA_E_INVALID, "pna_posttrans_dw_f32: leading dimension too small");

@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kThreads) void k_st_rows_bwd(const KArgs g) {
   }
 }
 
-// ---- the weight gradient of the shapes pna_posttrans_dw_f32's kernel does not take (n_scaler N > 240 or 4F + 1 > 384): one thread per
+// ---- the weight gradient of the shapes pna_posttrans_dw_f32's kernel does not take (n_scaler N > 240 or 4F + 1 > 384; N <= 128 holds here): one thread per
 // (n, k), the rows in sequence (fp32, a fixed order).  grad_b from the threads of k = 0. ----
 template <int S>
 __global__ __launch_bounds__(256) void k_st_dw_plain(const KArgs g, float* gw, float* gb) {

@@ -781,10 +781,10 @@ bool in_scope(int64_t V, int64_t E, int T, int Fi, int Fo, int S, int div) {
          Fo >= 1 && (int64_t)T * Fo <= kMaxC && S >= 1 && S <= 3 && (div == 0 || div == 1);
 }
 
-// pna_posttrans_dw_f32's shape limits and workspace (include/pna_amd.h: n_scaler N <= 240, K + Kh + 1 <= 384; one 240 x 384 fp32 partial
+// pna_posttrans_dw_f32's shape limits and workspace (include/pna_amd.h: N <= 128, n_scaler N <= 240, K + Kh + 1 <= 384; one 240 x 384 fp32 partial
 // per slab of >= 256 rows -- how many slabs depends on the device: room for the most it can ask for), restated here so that a call
 // of this route asks the runtime nothing
-bool dw_takes(int N, int S, int K, int Kh) { return S * N <= 240 && K + Kh + 1 <= 384; }
+bool dw_takes(int N, int S, int K, int Kh) { return N <= 128 && S * N <= 240 && K + Kh + 1 <= 384; }      // (every N of this file is <= 128)
 int64_t dw_bytes_of(int64_t V, int N, int S, int K, int Kh) { return dw_takes(N, S, K, Kh) ? (int64_t)240 * 384 * 4 * ((V + 255) / 256) : 0; }
 
 // ED == 0: the route without edge features.  ED > 0: no packed rows (its pull reads dm), + dm (E, T Fi) and the CSR-ordered copy of e

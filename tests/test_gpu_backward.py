@@ -869,7 +869,12 @@ def test_posttrans_weight_gradient_in_degree_plan_order(cuda_device, V, E, F, N)
 
 
 def test_posttrans_weight_gradient_kernel_declines_other_shapes(cuda_device):
-    from pna_amd import ops
+    from pna_amd import _lib, ops
     gy, a = torch.randn(5000, 80, device=cuda_device), torch.randn(5000, 320, device=cuda_device)
     assert ops.posttrans_dw(gy, a, 320, torch.randn(5000, 80, device=cuda_device), [None, None, None]) is None      # K + Kh + 1 = 401 > 384
     assert ops.posttrans_dw(torch.randn(5000, 128, device=cuda_device), a, 320, None, [None, None]) is None         # S N = 256 > 240
+    # one scaler, N > 128: S N <= 240 holds, but the kernel stages two 64-column blocks of gy (rows 128 .. of grad_w came back as zeros)
+    for N in (129, 136, 240):
+        assert ops.posttrans_dw(torch.randn(5000, N, device=cuda_device), a, 320, None, [None]) is None
+        assert _lib.lib().pna_posttrans_dw_workspace_bytes(5000, N, 1, 320, 0) == -1
+    assert _lib.lib().pna_posttrans_dw_workspace_bytes(5000, 128, 1, 320, 0) > 0 and _lib.lib().pna_posttrans_dw_workspace_bytes(5000, 120, 2, 320, 0) > 0
