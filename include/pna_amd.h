@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_gru_cell_fwd_f32 / pna_gru_cell_bwd_f32 / pna_gru_cell_workspace_bytes / pna_gru_cell_args,
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_dense_layer_fwd_f32 / pna_dense_layer_bwd_f32 / pna_dense_layer_workspace_bytes /
+                                  pna_dense_layer_lds_bytes / pna_dense_layer_args, PNA_DENSE_MAX_NODES, PNA_DENSE_MAX_SLABS, PNA_DENSE_SCALER_* (the
+                                  dense-adjacency PNALayer of the multitask GNN, one call each way); no existing struct or entry point changed.
+                                  23, additive: + pna_gru_cell_fwd_f32 / pna_gru_cell_bwd_f32 / pna_gru_cell_workspace_bytes / pna_gru_cell_args,
                                   PNA_GRU_F32, PNA_GRU_SLAB_ROWS, PNA_GRU_MAX_SLABS (the GRU update between two message-passing steps: nn.GRU over
                                   a length-1 sequence as a cell over rows, one call each way); no existing struct or entry point changed.
                                   23, additive: + pna_embed_sum_fwd_f32 / pna_embed_sum_bwd_f32 / pna_embed_sum_workspace_bytes / pna_embed_sum_args,
@@ -1743,6 +1746,86 @@ typedef struct pna_gru_cell_args {
 int64_t pna_gru_cell_workspace_bytes(int64_t V, int32_t I, int32_t Hc, int32_t hidden_size);   /* -1 outside the scope */
 int pna_gru_cell_fwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
 int pna_gru_cell_bwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
+
+/* ---- The dense-adjacency PNALayer (the multitask GNN's convolution), one call each way ------------------------------------------------
+ * replaces: models/pytorch/pna/layer.py:33-49,99-109 (PNATower / PNALayer with 1-layer pretrans and posttrans and the Linear + LeakyReLU
+ * mixing network), aggregators.py:17-73 (mean, max, min, std), scalers.py:7-38 (the five scalers), and what autograd derives from them.
+ *
+ * x (B, N, in_dim) and adj (B, N, N) contiguous; in_dim = n_tower Fi (divide_input: tower t reads columns [t Fi, (t + 1) Fi)) or Fi.
+ * Per tower t: w_pre (Fi, 2 Fi) = [W_p | W_q], b_pre [Fi], w_post (Fo, (1 + A S) Fi) = [W_h | W_(s, a) scaler-major], b_post [Fo];
+ * w_mix (C, C), b_mix [C], C = n_tower Fo -- all read as the optimiser leaves them, no packed image.  out (B, N, C).
+ * avg_log / avg_lin point to ONE float each ON THE DEVICE (avg_d["log"], avg_d["lin"]); one that no listed scaler reads may be NULL.
+ *
+ * Per graph: P = W_p x_t, Q = W_q x_t + b_pre, message m[i,j] = P[i] + Q[j]; a' = adj + I when self_loop (the aggregators only: the scalers'
+ * D_i = sum_j adj_ij is taken from adj as passed).  mean_i = P_i + (sum_j a'_ij Q_j) / D'_i; std_i = sqrt(relu(var_i) + 1e-5) with var_i the
+ * a'-weighted variance of Q_j about its weighted mean (the shift by P_i does not change it; never E[m^2] - E[m]^2); max_j = Q_j + max of
+ * P_i over {i : a'_ij > 0}, min alike -- the FIRST extremal i wins (strict comparison in ascending i: pna_segreduce_fwd_f32's tie rule on
+ * the by-column order).  A row (mean, std) or column (max, min) without an entry gives 0.  z_t = b_post + W_h x_t + sum_s f_s(D_i) W_s a_t
+ * with f of PNA_DENSE_SCALER_*; out = leaky(W_mix cat_t z_t + b_mix, slope).
+ *
+ * pna_dense_layer_fwd_f32: ONE launch; a workgroup owns a slab of ceil(B / PNA_DENSE_MAX_SLABS) consecutive graphs and holds one graph's
+ *   block, messages, aggregates and rows in LDS at a time.
+ * pna_dense_layer_bwd_f32: at most TWO launches, nothing saved but x and adj: (a) the same workgroups rebuild the forward with the forward's
+ *   device functions (so the LeakyReLU mask and the arg indices are the forward's), write grad_x (NULL: skipped) and add each graph's
+ *   parameter gradients into the slab's image of the workspace in graph order; (b) the images are added in slab order in float64.  A NULL
+ *   gradient pointer is skipped; adj gets no gradient.  Every sum has a fixed order and there are no atomics: bitwise repeatable.
+ * Scope (PNA_E_INVALID outside it, pna_last_error names the clause; pna_dense_layer_workspace_bytes returns -1): 1 <= N <=
+ * PNA_DENSE_MAX_NODES, 1 <= n_tower <= PNA_MAX_TOWER, Fi, Fo >= 1 with n_tower Fi <= 64 and n_tower Fo <= 64, 1-4 distinct aggregators
+ * (PNA_AGG_MEAN, _MAX, _MIN, _STD), 1-3 distinct scalers, B >= 1, B N < 2^31, and pna_dense_layer_lds_bytes(...) <= 160 KiB:
+ *   4 N ((N | 1) + 5 T Fi + A T Fi + 2 T Fo + 3 + S) + 2 N T Fi rounded up to 16.
+ * workspace (backward only): min(B, PNA_DENSE_MAX_SLABS) images of T (2 Fi^2 + Fi + Fo (1 + A S) Fi + Fo) + C^2 + C floats, 16-byte aligned,
+ * no initialisation. */
+#define PNA_DENSE_MAX_NODES 128
+#define PNA_DENSE_MAX_SLABS 256
+#define PNA_DENSE_SCALER_IDENTITY 0
+#define PNA_DENSE_SCALER_AMPLIFICATION 1  /* log(D + 1) / avg_log */
+#define PNA_DENSE_SCALER_ATTENUATION 2    /* avg_log / log(D + 1) */
+#define PNA_DENSE_SCALER_LINEAR 3         /* D / avg_lin */
+#define PNA_DENSE_SCALER_INVERSE_LINEAR 4 /* avg_lin / D */
+typedef struct pna_dense_layer_args {
+  uint32_t struct_size;    /* sizeof(pna_dense_layer_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  int64_t B;               /* graphs */
+  int32_t N;               /* nodes per graph */
+  int32_t in_dim;          /* columns of x */
+  int32_t n_tower;
+  int32_t Fi;              /* a tower's input width */
+  int32_t Fo;              /* a tower's output width */
+  int32_t divide_input;
+  int32_t self_loop;
+  int32_t n_aggr;
+  int32_t aggr[PNA_MAX_AGGR];      /* PNA_AGG_MEAN / _MAX / _MIN / _STD in the caller's order */
+  int32_t n_scaler;
+  int32_t scaler[PNA_MAX_SCALER];  /* PNA_DENSE_SCALER_* in the caller's order */
+  float slope;                     /* of the LeakyReLU */
+  const float* x;
+  const float* adj;
+  const float* avg_log;            /* one device float */
+  const float* avg_lin;            /* one device float */
+  const float* w_pre[PNA_MAX_TOWER];
+  const float* b_pre[PNA_MAX_TOWER];
+  const float* w_post[PNA_MAX_TOWER];
+  const float* b_post[PNA_MAX_TOWER];
+  const float* w_mix;
+  const float* b_mix;
+  float* out;                      /* forward */
+  const float* grad_out;           /* backward (B, N, C) contiguous */
+  float* grad_x;                   /* backward (B, N, in_dim) contiguous, NULL = not wanted */
+  float* grad_w_pre[PNA_MAX_TOWER];   /* backward, the parameters' shapes, contiguous; NULL = not wanted */
+  float* grad_b_pre[PNA_MAX_TOWER];
+  float* grad_w_post[PNA_MAX_TOWER];
+  float* grad_b_post[PNA_MAX_TOWER];
+  float* grad_w_mix;
+  float* grad_b_mix;
+  void* workspace;                 /* backward */
+  int64_t workspace_bytes;
+} pna_dense_layer_args;
+
+int64_t pna_dense_layer_lds_bytes(int32_t N, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_aggr, int32_t n_scaler);  /* -1: bad widths */
+int64_t pna_dense_layer_workspace_bytes(int64_t B, int32_t N, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_aggr,
+                                        int32_t n_scaler);                                      /* -1 outside the scope */
+int pna_dense_layer_fwd_f32(const pna_dense_layer_args* args, pna_stream_t stream);
+int pna_dense_layer_bwd_f32(const pna_dense_layer_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -23,6 +23,9 @@ PNA_EMBED_MAX_SLABS = 256
 PNA_GRU_F32 = 0
 PNA_GRU_SLAB_ROWS = 64          # pna_gru_cell_bwd_f32: a slab is max(this, ceil(V / PNA_GRU_MAX_SLABS)) rows
 PNA_GRU_MAX_SLABS = 64
+PNA_DENSE_MAX_NODES = 128
+PNA_DENSE_MAX_SLABS = 256       # pna_dense_layer_*: a slab is ceil(B / this) consecutive graphs, one workgroup and one gradient image each
+DENSE_SCALER_CODES = {"identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}
 
 # (std_pyg: the bf16 entry points only -- the PyG std, whose row without in-edges is sqrt(1e-5) in the device code)
 AGG_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5, "var_raw": 6, "std_pyg": 7}
@@ -410,6 +413,25 @@ class PnaGruCellArgs(_Args):
     ]
 
 
+class PnaDenseLayerArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("B", ctypes.c_int64), ("N", ctypes.c_int32), ("in_dim", ctypes.c_int32), ("n_tower", ctypes.c_int32), ("Fi", ctypes.c_int32),
+        ("Fo", ctypes.c_int32), ("divide_input", ctypes.c_int32), ("self_loop", ctypes.c_int32),
+        ("n_aggr", ctypes.c_int32), ("aggr", ctypes.c_int32 * PNA_MAX_AGGR),
+        ("n_scaler", ctypes.c_int32), ("scaler", ctypes.c_int32 * PNA_MAX_SCALER), ("slope", ctypes.c_float),
+        ("x", ctypes.c_void_p), ("adj", ctypes.c_void_p), ("avg_log", ctypes.c_void_p), ("avg_lin", ctypes.c_void_p),
+        ("w_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("b_pre", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("w_post", ctypes.c_void_p * PNA_MAX_TOWER), ("b_post", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("w_mix", ctypes.c_void_p), ("b_mix", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("grad_out", ctypes.c_void_p), ("grad_x", ctypes.c_void_p),
+        ("grad_w_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_b_pre", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("grad_w_post", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_b_post", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("grad_w_mix", ctypes.c_void_p), ("grad_b_mix", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -576,6 +598,13 @@ def lib():
         L.pna_gru_cell_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_gru_cell_fwd_f32, L.pna_gru_cell_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaGruCellArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_dense_layer_lds_bytes.argtypes = [ctypes.c_int32] * 6
+        L.pna_dense_layer_lds_bytes.restype = ctypes.c_int64
+        L.pna_dense_layer_workspace_bytes.argtypes = [ctypes.c_int64] + [ctypes.c_int32] * 6
+        L.pna_dense_layer_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_dense_layer_fwd_f32, L.pna_dense_layer_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaDenseLayerArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")

@@ -1315,3 +1315,119 @@ def gru_cell(x, h, gru):
     backward needs is kept only when one will come: grad mode on and an input or parameter that requires a gradient."""
     ts = (x, h, gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)
     return GruCellFn.apply(*ts, torch.is_grad_enabled() and any(t.requires_grad for t in ts))
+
+
+# ---- the dense-adjacency PNALayer (the multitask GNN's convolution) as one C call each way (pna_dense_layer.hip) -------------------------
+_dense_ws = {}      # device -> the backward's reusable workspace (the slabs' gradient images); _gru_workspace's scheme
+
+
+def _dense_workspace(dev, nbytes):
+    n = (nbytes + 16 + 3) // 4
+    buf = _dense_ws.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = _dense_ws[dev] = torch.empty(n, dtype=torch.float32, device=dev)
+    return buf
+
+
+def _dense_args(cfg, x, adj, avg_log, avg_lin, params):
+    T, Fi, Fo, divide, self_loop, aggr, scalers, slope = cfg
+    a = _lib.PnaDenseLayerArgs()
+    a.B, a.N, a.in_dim, a.n_tower, a.Fi, a.Fo = x.shape[0], x.shape[1], x.shape[2], T, Fi, Fo
+    a.divide_input, a.self_loop, a.slope = int(divide), int(self_loop), slope
+    a.n_aggr, a.n_scaler = len(aggr), len(scalers)
+    for k, name in enumerate(aggr):
+        a.aggr[k] = _lib.AGG_CODES[name]
+    for k, name in enumerate(scalers):
+        a.scaler[k] = _lib.DENSE_SCALER_CODES[name]
+    a.x, a.adj = _lib.dev_ptr(x, torch.float32, "input"), _lib.dev_ptr(adj, torch.float32, "adj")
+    a.avg_log, a.avg_lin = _lib.dev_ptr(avg_log, torch.float32, "avg_d['log']"), _lib.dev_ptr(avg_lin, torch.float32, "avg_d['lin']")
+    for t in range(T):
+        for k, f in enumerate(("w_pre", "b_pre", "w_post", "b_post")):
+            getattr(a, f)[t] = _lib.dev_ptr(params[4 * t + k], torch.float32, f).value
+    a.w_mix, a.b_mix = _lib.dev_ptr(params[4 * T], torch.float32, "w_mix"), _lib.dev_ptr(params[4 * T + 1], torch.float32, "b_mix")
+    return a
+
+
+class DenseLayerFn(torch.autograd.Function):
+    """pna_amd.pytorch.pna.layer.PNALayer (1-layer pretrans and posttrans, aggregators out of mean / max / min / std, Linear + LeakyReLU
+    mixing) as ONE C call (pna_dense_layer_fwd_f32: one launch) and its backward as one (pna_dense_layer_bwd_f32: at most two launches, no
+    atomics, bitwise repeatable).  Nothing is saved but the inputs: the backward rebuilds the forward in LDS.  `cfg` = (towers, Fi, Fo,
+    divide_input, self_loop, aggregator names, scaler names, slope); `params` = per tower the pretrans weight and bias and the posttrans
+    weight and bias, then the mixing weight and bias, contiguous fp32.  avg_log / avg_lin: one device float each, or None where no scaler
+    reads it.  adj gets no gradient.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, adj, avg_log, avg_lin, cfg, *params):
+        T, Fo = cfg[0], cfg[2]
+        dev, (B, N, _) = x.device, x.shape
+        out = torch.empty(B, N, T * Fo, dtype=torch.float32, device=dev)
+        a = _dense_args(cfg, x, adj, avg_log, avg_lin, params)
+        a.out = _lib.dev_ptr(out, torch.float32, "out")
+        _lib.check(_lib.lib().pna_dense_layer_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_dense_layer_fwd_f32")
+        ctx.cfg, ctx.has_log, ctx.has_lin = cfg, avg_log is not None, avg_lin is not None
+        ctx.save_for_backward(x, adj, *[t for t in (avg_log, avg_lin) if t is not None], *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        cfg = ctx.cfg
+        T, Fi, Fo, aggr, scalers = cfg[0], cfg[1], cfg[2], cfg[5], cfg[6]
+        saved = list(ctx.saved_tensors)
+        x, adj = saved[:2]
+        k = 2
+        avg_log = avg_lin = None
+        if ctx.has_log:
+            avg_log, k = saved[k], k + 1
+        if ctx.has_lin:
+            avg_lin, k = saved[k], k + 1
+        params = saved[k:]
+        dev, (B, N, _) = x.device, x.shape
+        go = go.contiguous()
+        need = ctx.needs_input_grad
+        a = _dense_args(cfg, x, adj, avg_log, avg_lin, params)
+        a.grad_out = _lib.dev_ptr(go, torch.float32, "grad_out")
+        gx = torch.empty_like(x) if need[0] else None
+        a.grad_x = _lib.dev_ptr(gx, torch.float32, "grad_x")
+        grads = [torch.empty_like(p) if need[5 + i] else None for i, p in enumerate(params)]
+        for t in range(T):
+            for j, f in enumerate(("grad_w_pre", "grad_b_pre", "grad_w_post", "grad_b_post")):
+                gt = grads[4 * t + j]
+                getattr(a, f)[t] = None if gt is None else gt.data_ptr()
+        a.grad_w_mix, a.grad_b_mix = _lib.dev_ptr(grads[4 * T], torch.float32, "grad_w_mix"), _lib.dev_ptr(grads[4 * T + 1], torch.float32, "grad_b_mix")
+        from .functional import dense_layer_workspace_bytes
+        nbytes = dense_layer_workspace_bytes(B, N, T, Fi, Fo, len(aggr), len(scalers))
+        ws = _dense_workspace(dev, nbytes)
+        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        _lib.check(_lib.lib().pna_dense_layer_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_dense_layer_bwd_f32")
+        return (gx, None, None, None, None, *grads)
+
+
+def _dense_avg(v, dev):
+    """avg_d[key] as one fp32 float on `dev`: a 0-dim or 1-element fp32 tensor already there is passed as it is; a Python number or a
+    tensor on the host becomes a fresh device scalar per call -- one small fill launch, stream-ordered, nothing read from the device and
+    nothing kept, so there is no cached operand to go stale (DESIGN.md 4.13's census has no row for this route)."""
+    if torch.is_tensor(v):
+        if v.device == dev and v.dtype == torch.float32 and v.numel() == 1:
+            return v.detach()
+        if v.is_cuda:
+            return v.detach().to(device=dev, dtype=torch.float32).reshape(1)      # (device to device: stream-ordered)
+    return torch.full((1,), float(v), dtype=torch.float32, device=dev)
+
+
+def dense_layer(layer, x, adj):
+    """`layer` (a pna_amd.pytorch.pna.layer.PNALayer inside the scope of its `_one_call_path`) on x (B, N, in) and adj (B, N, N) through
+    DenseLayerFn.  Reads no float on the host and waits for nothing: capturable."""
+    t0 = layer.towers[0]
+    scalers = tuple(t0.scalers)
+    avg_log = _dense_avg(t0.avg_d["log"], x.device) if ("amplification" in scalers or "attenuation" in scalers) else None
+    avg_lin = _dense_avg(t0.avg_d["lin"], x.device) if ("linear" in scalers or "inverse_linear" in scalers) else None
+    params = []
+    for t in layer.towers:
+        pre, post = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear
+        params += [pre.weight, pre.bias, post.weight, post.bias]
+    mix = layer.mixing_network
+    params += [mix.linear.weight, mix.linear.bias]
+    cfg = (len(layer.towers), t0.in_features, t0.out_features, bool(layer.divide_input), bool(t0.self_loop), tuple(t0.aggregators), scalers,
+           float(mix.activation.negative_slope))
+    return DenseLayerFn.apply(x, adj, avg_log, avg_lin, cfg, *params)

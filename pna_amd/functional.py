@@ -1276,6 +1276,42 @@ def gru_cell_workspace_bytes(V, I, Hc, hidden_size):
     return 4 * (V * 4 * hidden_size + -(-V // L) * 3 * hidden_size * (I + Hc + 2))
 
 
+# The dense-adjacency PNALayer (pna_amd.pytorch.pna.layer.PNALayer: the multitask GNN's convolution) takes the one-call route
+# (autograd.DenseLayerFn: pna_dense_layer_fwd_f32 / _bwd_f32) on calls of up to this many rows B N.  0 = off, the default
+DENSE_LAYER_ROWS = int(os.environ.get("PNA_AMD_DENSE_LAYER_ROWS", "0"))
+DENSE_LAYER_LDS_BUDGET = 160 * 1024
+DENSE_LAYER_AGGREGATORS = ("mean", "max", "min", "std")
+
+
+def dense_layer_lds_bytes(N, T, Fi, Fo, A, S):
+    """pna_dense_layer_lds_bytes' formula: one graph's block (odd row pitch), x, P, Q, the row means and 1 / (2 std), the aggregates, two
+    (N, T Fo) row sets, 3 + S per-node factors and two byte planes of arg indices; -1 where the widths are outside the scope."""
+    if not (1 <= N <= _lib.PNA_DENSE_MAX_NODES and 1 <= T <= _lib.PNA_MAX_TOWER and Fi >= 1 and T * Fi <= 64 and Fo >= 1 and T * Fo <= 64
+            and 1 <= A <= 4 and 1 <= S <= 3):
+        return -1
+    TF, C = T * Fi, T * Fo
+    return 4 * N * ((N | 1) + 5 * TF + A * TF + 2 * C + 3 + S) + (2 * N * TF + 15) // 16 * 16
+
+
+def dense_layer_fits(N, T, Fi, Fo, A, S):
+    """Mirror of pna_dense_layer_*_f32's scope in the shapes: the widths, and one graph inside a workgroup's 160 KiB of LDS."""
+    return 0 < dense_layer_lds_bytes(N, T, Fi, Fo, A, S) <= DENSE_LAYER_LDS_BUDGET
+
+
+def dense_layer_slab_graphs(B):
+    """Graphs per slab (a slab = one workgroup = one image of the parameter gradients): never more than PNA_DENSE_MAX_SLABS slabs."""
+    return -(-B // _lib.PNA_DENSE_MAX_SLABS)
+
+
+def dense_layer_workspace_bytes(B, N, T, Fi, Fo, A, S):
+    """pna_dense_layer_workspace_bytes' formula: min(B, PNA_DENSE_MAX_SLABS) images of every parameter gradient (at least one per slab
+    in use, monotone in B); -1 outside the scope."""
+    if B < 1 or B * N >= 2 ** 31 or not dense_layer_fits(N, T, Fi, Fo, A, S):
+        return -1
+    C = T * Fo
+    return min(B, _lib.PNA_DENSE_MAX_SLABS) * (T * (2 * Fi * Fi + Fi + Fo * (1 + A * S) * Fi + Fo) + C * C + C) * 4
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")

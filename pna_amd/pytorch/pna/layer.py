@@ -149,7 +149,43 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
                      posttrans_layers=posttrans_layers, device=device) for _ in range(towers))
         self.mixing_network = FCLayer(out_features, out_features, activation="LeakyReLU")
 
+    def _one_call_path(self, input, adj):
+        """Whether this call is served by pna_dense_layer_fwd_f32 / _bwd_f32 (autograd.DenseLayerFn: one C call each way, train and eval,
+        with and without grad): the knob PNA_AMD_DENSE_LAYER_ROWS is on and covers B N; input (B, N, in) and adj (B, N, N) are contiguous
+        fp32 on one GPU and adj wants no gradient; every tower's pretrans and posttrans is one affine layer; the aggregators are distinct
+        names out of mean / max / min / std and the scalers 1-3 distinct names; every parameter is contiguous fp32 on that GPU; the mixing network is
+        Linear + LeakyReLU with bias, without dropout or batch-norm; and one graph fits the kernel's LDS (functional.dense_layer_fits).
+        No float is read."""
+        if not PF.DENSE_LAYER_ROWS > 0:
+            return False
+        if not (input.dim() == 3 and adj.dim() == 3 and adj.shape[0] == input.shape[0] and adj.shape[1] == adj.shape[2] == input.shape[1]
+                and input.shape[2] == self.in_features and 1 <= input.shape[0] * input.shape[1] <= PF.DENSE_LAYER_ROWS):
+            return False
+        for t in (input, adj):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == input.device):
+                return False
+        if adj.requires_grad:
+            return False
+        t0 = self.towers[0]
+        if not all(t.pretrans.is_affine and t.posttrans.is_affine for t in self.towers):
+            return False
+        aggs, scalers = t0.aggregators, t0.scalers
+        if not (1 <= len(aggs) == len(set(aggs)) and all(a in PF.DENSE_LAYER_AGGREGATORS for a in aggs)):
+            return False
+        if not (1 <= len(scalers) <= 3 and len(scalers) == len(set(scalers)) and all(s in SCALERS for s in scalers)):
+            return False
+        mix = self.mixing_network
+        if not (type(mix.activation) is nn.LeakyReLU and mix.linear.bias is not None and mix.dropout is None and mix.b_norm is None):
+            return False
+        for p in self.parameters():
+            if not (p.is_cuda and p.dtype == torch.float32 and p.device == input.device and p.is_contiguous()):
+                return False
+        return PF.dense_layer_fits(input.shape[1], len(self.towers), t0.in_features, t0.out_features, len(aggs), len(scalers))
+
     def forward(self, input, adj):
+        if PF.DENSE_LAYER_ROWS > 0 and self._one_call_path(input, adj):
+            from ... import autograd as AG
+            return AG.dense_layer(self, input, adj)
         y = _dense_towers_forward(list(self.towers), input, adj, self.divide_input)
         return self.mixing_network(y)
 
