@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_dense_layer_fwd_f32 / pna_dense_layer_bwd_f32 / pna_dense_layer_workspace_bytes /
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_set2set_fwd_f32 / pna_set2set_bwd_f32 / pna_set2set_workspace_bytes / pna_set2set_lds_bytes /
+                                  pna_set2set_args, PNA_S2S_F32, PNA_S2S_MAX_WIDTH, PNA_S2S_MAX_NODES, PNA_S2S_MAX_STEPS, PNA_S2S_MAX_SLABS (the Set2Set
+                                  graph readout of the multitask GNN, one call each way); no existing struct or entry point changed.
+                                  23, additive: + pna_dense_layer_fwd_f32 / pna_dense_layer_bwd_f32 / pna_dense_layer_workspace_bytes /
                                   pna_dense_layer_lds_bytes / pna_dense_layer_args, PNA_DENSE_MAX_NODES, PNA_DENSE_MAX_SLABS, PNA_DENSE_SCALER_* (the
                                   dense-adjacency PNALayer of the multitask GNN, one call each way); no existing struct or entry point changed.
                                   23, additive: + pna_gru_cell_fwd_f32 / pna_gru_cell_bwd_f32 / pna_gru_cell_workspace_bytes / pna_gru_cell_args,
@@ -1826,6 +1829,69 @@ int64_t pna_dense_layer_workspace_bytes(int64_t B, int32_t N, int32_t n_tower, i
                                         int32_t n_scaler);                                      /* -1 outside the scope */
 int pna_dense_layer_fwd_f32(const pna_dense_layer_args* args, pna_stream_t stream);
 int pna_dense_layer_bwd_f32(const pna_dense_layer_args* args, pna_stream_t stream);
+
+/* ---- The Set2Set graph readout (the multitask GNN's graph head), one call each way ---------------------------------------------------
+ * replaces: models/layers.py:22-98 (Set2Set: a one-step nn.LSTM, the scores x q, a softmax over the nodes and the weighted sum, repeated
+ * `steps` times; the loop is :81-98), as S2SReadout (:271-289) and the GNN (models/pytorch/gnn_framework.py:83,108) use it, and what
+ * autograd derives from it.
+ *
+ * x (B, N, D) contiguous; w_ih (4D, 2D), w_hh (4D, D), b_ih, b_hh [4D]: nn.LSTM(2D, D).{weight,bias}_{ih,hh}_l0 as the optimiser leaves them,
+ * contiguous, gate order i, f, g, o; out (B, 2D).  Per graph b with rows x_n:
+ *   h = c = 0 (D), q* = 0 (2D); `steps` times:
+ *     z = W_ih q* + W_hh h + (b_ih + b_hh);   c = sigmoid(z_f) c + sigmoid(z_i) tanh(z_g);   h = sigmoid(z_o) tanh(c);   q = h
+ *     e_n = x_n . q;   a = softmax_n(e) (the maximum subtracted);   r = sum_n a_n x_n;   q* = [q | r]
+ *   out_b = q*.
+ * Exact fp32 on the vector ALU; every sum has a fixed order (the k of a product row ascending, the nodes ascending, the two wavefronts of
+ * a softmax reduction in wavefront order after a butterfly inside each).  sigmoid and tanh are pna_gru_cell's forms: no overflow, no
+ * cancellation, finite and exactly saturated at +-100.
+ *
+ * pna_set2set_fwd_f32: ONE launch; a workgroup owns a slab of ceil(B / PNA_S2S_MAX_SLABS) consecutive graphs; both weight matrices, the bias
+ *   sum and one graph's rows sit in LDS; the step loop runs inside the kernel with workgroup barriers only.  Nothing is saved but out.
+ * pna_set2set_bwd_f32: at most TWO launches, no atomics of any kind, bitwise repeatable.  (a) the same workgroups rebuild each graph's
+ *   forward with the forward's device function, writing per step the activated gates, c_t, q*_t and a_t (7D + N floats) to the slab's own
+ *   region of the workspace, then walk the steps in reverse: the weighted sum, the softmax, the scores, the LSTM cell, W_ih^T dz and W_hh^T dz
+ *   into the previous step.  grad_x is accumulated in LDS and written once per graph (NULL: skipped); grad W_ih, grad W_hh and ONE bias
+ *   gradient are accumulated in LDS over the slab's graphs in graph order and written as the slab's image.  (b) one thread per parameter
+ *   element adds the images in slab order in float64 and rounds once; grad_b_ih and grad_b_hh receive the same bits.  A NULL gradient
+ *   pointer is skipped; (b) is not launched when no parameter gradient is wanted.
+ * Scope (PNA_E_INVALID outside it, pna_last_error names the clause; pna_set2set_workspace_bytes returns -1): fp32 only (dtype ==
+ * PNA_S2S_F32), 1 <= D <= PNA_S2S_MAX_WIDTH, 1 <= N <= PNA_S2S_MAX_NODES, 1 <= steps <= PNA_S2S_MAX_STEPS, B >= 1, B N < 2^31.
+ * pna_set2set_lds_bytes(N, D) is the backward's footprint, the larger one (-1: N or D outside the scope), with PI = 2D | 1, PH = D | 1:
+ *   4 (4D (PI + PH) + N PH + 12 D^2 + N D + 26 D + 2 N + 4) rounded up to 16: 136976 bytes at D = 32, N = 128, inside a CU's 160 KiB.
+ * workspace (backward only): min(B, PNA_S2S_MAX_SLABS) (12 D^2 + 4D + steps (7D + N)) floats, 16-byte aligned, no initialisation. */
+#define PNA_S2S_F32 0
+#define PNA_S2S_MAX_WIDTH 32
+#define PNA_S2S_MAX_NODES 128
+#define PNA_S2S_MAX_STEPS 128
+#define PNA_S2S_MAX_SLABS 256
+typedef struct pna_set2set_args {
+  uint32_t struct_size;    /* sizeof(pna_set2set_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  int64_t B;               /* graphs */
+  int32_t N;               /* nodes per graph */
+  int32_t D;               /* columns of x = the LSTM's hidden size; its input size is 2D */
+  int32_t steps;
+  int32_t dtype;           /* PNA_S2S_F32 */
+  const float* x;          /* (B, N, D) contiguous */
+  const float* w_ih;       /* (4D, 2D) contiguous */
+  const float* w_hh;       /* (4D, D) contiguous */
+  const float* b_ih;       /* [4D] */
+  const float* b_hh;       /* [4D] */
+  float* out;              /* forward (B, 2D) contiguous */
+  const float* grad_out;   /* backward (B, 2D) contiguous */
+  float* grad_x;           /* backward (B, N, D) contiguous, NULL = not wanted */
+  float* grad_w_ih;        /* backward, the parameters' shapes, contiguous; NULL = not wanted */
+  float* grad_w_hh;
+  float* grad_b_ih;
+  float* grad_b_hh;
+  void* workspace;         /* backward */
+  int64_t workspace_bytes;
+} pna_set2set_args;
+
+int64_t pna_set2set_lds_bytes(int32_t N, int32_t D);                                            /* -1: N or D outside the scope */
+int64_t pna_set2set_workspace_bytes(int64_t B, int32_t N, int32_t D, int32_t steps);            /* -1 outside the scope */
+int pna_set2set_fwd_f32(const pna_set2set_args* args, pna_stream_t stream);
+int pna_set2set_bwd_f32(const pna_set2set_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -25,6 +25,11 @@ PNA_GRU_SLAB_ROWS = 64          # pna_gru_cell_bwd_f32: a slab is max(this, ceil
 PNA_GRU_MAX_SLABS = 64
 PNA_DENSE_MAX_NODES = 128
 PNA_DENSE_MAX_SLABS = 256       # pna_dense_layer_*: a slab is ceil(B / this) consecutive graphs, one workgroup and one gradient image each
+PNA_S2S_F32 = 0
+PNA_S2S_MAX_WIDTH = 32          # pna_set2set_*: columns of x (the LSTM's hidden size)
+PNA_S2S_MAX_NODES = 128
+PNA_S2S_MAX_STEPS = 128
+PNA_S2S_MAX_SLABS = 256         # a slab is ceil(B / this) consecutive graphs, one workgroup and one gradient image each
 DENSE_SCALER_CODES = {"identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}
 
 # (std_pyg: the bf16 entry points only -- the PyG std, whose row without in-edges is sqrt(1e-5) in the device code)
@@ -432,6 +437,17 @@ class PnaDenseLayerArgs(_Args):
     ]
 
 
+class PnaSet2setArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("B", ctypes.c_int64), ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("steps", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("w_ih", ctypes.c_void_p), ("w_hh", ctypes.c_void_p), ("b_ih", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+        ("out", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("grad_x", ctypes.c_void_p),
+        ("grad_w_ih", ctypes.c_void_p), ("grad_w_hh", ctypes.c_void_p), ("grad_b_ih", ctypes.c_void_p), ("grad_b_hh", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -605,6 +621,13 @@ def lib():
         L.pna_dense_layer_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_dense_layer_fwd_f32, L.pna_dense_layer_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaDenseLayerArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_set2set_lds_bytes.argtypes = [ctypes.c_int32] * 2
+        L.pna_set2set_lds_bytes.restype = ctypes.c_int64
+        L.pna_set2set_workspace_bytes.argtypes = [ctypes.c_int64] + [ctypes.c_int32] * 3
+        L.pna_set2set_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_set2set_fwd_f32, L.pna_set2set_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaSet2setArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")

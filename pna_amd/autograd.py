@@ -1431,3 +1431,68 @@ def dense_layer(layer, x, adj):
     cfg = (len(layer.towers), t0.in_features, t0.out_features, bool(layer.divide_input), bool(t0.self_loop), tuple(t0.aggregators), scalers,
            float(mix.activation.negative_slope))
     return DenseLayerFn.apply(x, adj, avg_log, avg_lin, cfg, *params)
+
+
+# ---- the Set2Set graph readout (layers.Set2Set: the multitask GNN's graph head) as one C call each way (pna_set2set.hip) ----------------
+_s2s_ws = {}        # device -> the backward's reusable workspace (the slabs' records and gradient images); _gru_workspace's scheme
+
+
+def _s2s_workspace(dev, nbytes):
+    n = (nbytes + 16 + 3) // 4
+    buf = _s2s_ws.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = _s2s_ws[dev] = torch.empty(n, dtype=torch.float32, device=dev)
+    return buf
+
+
+def _s2s_args(x, w_ih, w_hh, b_ih, b_hh, steps):
+    a = _lib.PnaSet2setArgs()
+    a.B, a.N, a.D, a.steps, a.dtype = x.shape[0], x.shape[1], x.shape[2], steps, _lib.PNA_S2S_F32
+    a.x = _lib.dev_ptr(x, torch.float32, "x")
+    a.w_ih, a.w_hh = _lib.dev_ptr(w_ih, torch.float32, "weight_ih"), _lib.dev_ptr(w_hh, torch.float32, "weight_hh")
+    a.b_ih, a.b_hh = _lib.dev_ptr(b_ih, torch.float32, "bias_ih"), _lib.dev_ptr(b_hh, torch.float32, "bias_hh")
+    return a
+
+
+class Set2SetFn(torch.autograd.Function):
+    """models/layers.py:81-98 (`steps` rounds of a one-step nn.LSTM(2D, D), the scores, a softmax over the nodes and the weighted sum) as
+    ONE C call (pna_set2set_fwd_f32: one launch) and its backward as one (pna_set2set_bwd_f32: at most two launches, no atomics, bitwise
+    repeatable).  x: (B, N, D) contiguous fp32; the four nn.LSTM parameters as they are.  Nothing is saved but the inputs: the backward
+    rebuilds the forward.  The workspace is one cached buffer per device, grown on demand.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, steps):
+        w_ih, w_hh, b_ih, b_hh = w_ih.contiguous(), w_hh.contiguous(), b_ih.contiguous(), b_hh.contiguous()
+        dev, (B, _, D) = x.device, x.shape
+        out = torch.empty(B, 2 * D, dtype=torch.float32, device=dev)
+        a = _s2s_args(x, w_ih, w_hh, b_ih, b_hh, steps)
+        a.out = _lib.dev_ptr(out, torch.float32, "out")
+        _lib.check(_lib.lib().pna_set2set_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_set2set_fwd_f32")
+        ctx.steps = steps
+        ctx.save_for_backward(x, w_ih, w_hh, b_ih, b_hh)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        x, w_ih, w_hh, b_ih, b_hh = ctx.saved_tensors
+        dev, (B, N, D) = x.device, x.shape
+        go = go.contiguous()
+        need = ctx.needs_input_grad
+        a = _s2s_args(x, w_ih, w_hh, b_ih, b_hh, ctx.steps)
+        a.grad_out = _lib.dev_ptr(go, torch.float32, "grad_out")
+        grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate((x, w_ih, w_hh, b_ih, b_hh))]
+        for f, t in zip(("grad_x", "grad_w_ih", "grad_w_hh", "grad_b_ih", "grad_b_hh"), grads):
+            setattr(a, f, _lib.dev_ptr(t, torch.float32, f))
+        from .functional import set2set_workspace_bytes
+        nbytes = set2set_workspace_bytes(B, N, D, ctx.steps)
+        ws = _s2s_workspace(dev, nbytes)
+        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        _lib.check(_lib.lib().pna_set2set_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_set2set_bwd_f32")
+        return (*grads, None)
+
+
+def set2set(x, lstm, steps):
+    """`steps` rounds of Set2Set on x (B, N, D) with `lstm` (an nn.LSTM(2D, D): one layer, one direction, bias) through Set2SetFn.  Reads
+    nothing on the host and waits for nothing: capturable."""
+    return Set2SetFn.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, int(steps))

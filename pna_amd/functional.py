@@ -1312,6 +1312,39 @@ def dense_layer_workspace_bytes(B, N, T, Fi, Fo, A, S):
     return min(B, _lib.PNA_DENSE_MAX_SLABS) * (T * (2 * Fi * Fi + Fi + Fo * (1 + A * S) * Fi + Fo) + C * C + C) * 4
 
 
+# The Set2Set graph readout (layers.Set2Set: the multitask GNN's graph head) takes the one-call route (autograd.Set2SetFn:
+# pna_set2set_fwd_f32 / _bwd_f32) on calls of up to this many rows B N.  0 = off, the default
+S2S_ROWS = int(os.environ.get("PNA_AMD_S2S_ROWS", "0"))
+S2S_LDS_BUDGET = 160 * 1024
+
+
+def set2set_lds_bytes(N, D):
+    """pna_set2set_lds_bytes' formula, the backward's footprint: both weight matrices on odd row pitches, the bias sum, the graph's rows,
+    the three gradient accumulators, grad_x and the step state; -1 where N or D is outside the scope."""
+    if not (1 <= N <= _lib.PNA_S2S_MAX_NODES and 1 <= D <= _lib.PNA_S2S_MAX_WIDTH):
+        return -1
+    PI, PH = (2 * D) | 1, D | 1
+    return (4 * (4 * D * (PI + PH) + N * PH + 12 * D * D + N * D + 26 * D + 2 * N + 4) + 15) // 16 * 16
+
+
+def set2set_fits(N, D, steps):
+    """Mirror of pna_set2set_*_f32's scope in the shapes: the bounds on N, D and steps, and the backward inside a workgroup's 160 KiB."""
+    return 1 <= steps <= _lib.PNA_S2S_MAX_STEPS and 0 < set2set_lds_bytes(N, D) <= S2S_LDS_BUDGET
+
+
+def set2set_slab_graphs(B):
+    """Graphs per slab (a slab = one workgroup = one image of the parameter gradients): never more than PNA_S2S_MAX_SLABS slabs."""
+    return -(-B // _lib.PNA_S2S_MAX_SLABS)
+
+
+def set2set_workspace_bytes(B, N, D, steps):
+    """pna_set2set_workspace_bytes' formula: min(B, PNA_S2S_MAX_SLABS) times one image of the parameter gradients and the steps' records
+    [gates 4D | c D | q* 2D | a N] of the graph a slab is working on; -1 outside the scope."""
+    if B < 1 or B * N >= 2 ** 31 or not set2set_fits(N, D, steps):
+        return -1
+    return min(B, _lib.PNA_S2S_MAX_SLABS) * (12 * D * D + 4 * D + steps * (7 * D + N)) * 4
+
+
 def simple_layer_small(layer, graph, h, row_scales):
     """PNASimpleLayer.forward (eval) through pna_tower_layer_f32; the plan is cached on the layer."""
     plan = layer.__dict__.get("_pna_amd_small")

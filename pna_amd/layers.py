@@ -1,4 +1,4 @@
-"""Dense blocks the PNA layers are assembled from: `FCLayer`, `MLP` and `GRU`.
+"""Dense blocks the PNA layers and the multitask GNN are assembled from: `FCLayer`, `MLP`, `GRU`, `Set2Set` and `S2SReadout`.
 
 Same constructor arguments, forward order (linear -> activation -> dropout -> batch-norm), weight
 initialisation and state_dict keys (`fully_connected.{k}.linear.{weight,bias}`) as the reference's
@@ -141,3 +141,70 @@ class GRU(nn.Module):
             y = F.pad(input=y, pad=[0, self.hidden_size - y.shape[-1]], mode='constant', value=0)
         x = self.gru(x, y)[1]
         return x.reshape(B, N, -1)
+
+
+class Set2Set(nn.Module):
+    """models/layers.py:22-98: the Set2Set pooling of (B, N, nin) rows into (B, nhid) -- `steps` (default: N) rounds of a one-step LSTM on
+    q*, the scores x . q, a softmax over the nodes and the weighted sum r, with q* = [q | r].  Same constructor, same parameter names
+    (`lstm.weight_ih_l0` .. `lstm.bias_hh_l0`).  With PNA_AMD_S2S_ROWS on and the call in scope (`_one_call_path`) the whole loop is one C
+    call each way (autograd.set2set); otherwise exactly the reference's loop over `self.lstm`."""
+
+    def __init__(self, nin, nhid=None, steps=None, num_layers=1, activation=None, device='cpu'):
+        super().__init__()
+        self.steps = steps
+        self.nin = nin
+        self.nhid = 2 * nin if nhid is None else nhid
+        if self.nhid <= self.nin:
+            raise ValueError('Set2Set hidden_dim should be larger than input_dim')
+        self.lstm_output_dim = self.nhid - self.nin
+        self.num_layers = num_layers
+        self.lstm = nn.LSTM(self.nhid, self.nin, num_layers=num_layers, batch_first=True).to(device)
+        self.softmax = nn.Softmax(dim=1)
+
+    def _one_call_path(self, x):
+        """True where the one-call route covers the call: the knob covers B N rows; x a contiguous fp32 (B, N, nin) tensor on a GPU; one
+        LSTM layer of input size 2 nin with biases, fp32 on x's device; N, nin and the step count inside the kernel's scope."""
+        from . import functional as PF
+        if not PF.S2S_ROWS > 0:
+            return False
+        if not (x.dim() == 3 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+            return False
+        B, N, D = x.shape
+        if not (self.num_layers == 1 and D == self.nin and self.nhid == 2 * self.nin and self.lstm.bias and not self.lstm.bidirectional
+                and getattr(self.lstm, "proj_size", 0) == 0):
+            return False
+        ps = (self.lstm.weight_ih_l0, self.lstm.weight_hh_l0, self.lstm.bias_ih_l0, self.lstm.bias_hh_l0)
+        if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in ps):
+            return False
+        return B >= 1 and PF.set2set_fits(N, D, self.steps or N) and B * N <= PF.S2S_ROWS
+
+    def forward(self, x):
+        if self._one_call_path(x):
+            from .autograd import set2set
+            return set2set(x, self.lstm, self.steps or x.shape[1])
+        batch_size = x.shape[0]
+        n = self.steps or x.shape[1]
+        h = (x.new_zeros((self.num_layers, batch_size, self.nin)),
+             x.new_zeros((self.num_layers, batch_size, self.nin)))
+        q_star = x.new_zeros(batch_size, 1, self.nhid)
+        for _ in range(n):
+            q, h = self.lstm(q_star, h)                              # q: (B, 1, nin)
+            e = torch.matmul(x, torch.transpose(q, 1, 2))            # (B, N, 1)
+            a = self.softmax(e)
+            r = torch.sum(a * x, dim=1, keepdim=True)
+            q_star = torch.cat([q, r], dim=-1)
+        return torch.squeeze(q_star, dim=1)
+
+
+class S2SReadout(nn.Module):
+    """models/layers.py:271-289: the graph head -- `Set2Set` over all nodes' features, then an MLP with batch-norm between its layers
+    (torch's own ops: it works on B rows).  Parameter names `set2set.lstm.*` and `mlp.fully_connected.{k}.*`."""
+
+    def __init__(self, in_size, hidden_size, out_size, fc_layers=3, device='cpu', final_activation='relu'):
+        super().__init__()
+        self.set2set = Set2Set(in_size, device=device)
+        self.mlp = MLP(in_size=2 * in_size, hidden_size=hidden_size, out_size=out_size, layers=fc_layers, mid_activation="relu",
+                       last_activation=final_activation, mid_b_norm=True, last_b_norm=False, device=device)
+
+    def forward(self, x):
+        return self.mlp(self.set2set(x))
