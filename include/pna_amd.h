@@ -26,7 +26,11 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_set2set_fwd_f32 / pna_set2set_bwd_f32 / pna_set2set_workspace_bytes / pna_set2set_lds_bytes /
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_drop_train_fwd_f32 / pna_tower_drop_train_bwd_f32 / pna_tower_drop_args, pna_dropout_mask_f32
+                                  (the one-call tower training routes, with and without edge features, with the towers' dropout between
+                                  their BatchNorm and the mixing Linear: a Philox4x32-10 mask regenerated in the backward from a 128-bit
+                                  key); no existing struct or entry point changed.
+                                  23, additive: + pna_set2set_fwd_f32 / pna_set2set_bwd_f32 / pna_set2set_workspace_bytes / pna_set2set_lds_bytes /
                                   pna_set2set_args, PNA_S2S_F32, PNA_S2S_MAX_WIDTH, PNA_S2S_MAX_NODES, PNA_S2S_MAX_STEPS, PNA_S2S_MAX_SLABS (the Set2Set
                                   graph readout of the multitask GNN, one call each way); no existing struct or entry point changed.
                                   23, additive: + pna_dense_layer_fwd_f32 / pna_dense_layer_bwd_f32 / pna_dense_layer_workspace_bytes /
@@ -1593,6 +1597,40 @@ int64_t pna_tower_edge_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tow
                                              int32_t edge_dim);   /* -1 outside the scope */
 int pna_tower_edge_train_fwd_f32(const pna_tower_edge_train_args* args, pna_stream_t stream);
 int pna_tower_edge_train_bwd_f32(const pna_tower_edge_train_args* args, pna_stream_t stream);
+
+/* ---- The two calls above WITH THE TOWERS' DROPOUT: forward and backward as ONE call each ---------------------------------------
+ * replaces: models/dgl/pna_layer.py:71-75 (graph norm, BatchNorm, then F.dropout(h, self.dropout, training=self.training) inside every
+ * tower) in front of :134-141 (cat, the mixing network) in train mode, and what autograd derives from them; every superpixel
+ * configuration of realworld_benchmark/README.md:65-100 trains with --dropout 0.1, 0.2 or 0.3.
+ *
+ * The mask rule.  Element (v, c) of hcat (V, C = n_tower Fo) has index e = v C + c (64 bits).  Its word is word e & 3 of
+ * Philox4x32-10(counter = (lo32(e >> 2), hi32(e >> 2), lo32(offset), hi32(offset)), key = (lo32(seed), hi32(seed))); multipliers
+ * 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85.  The element is KEPT iff word >= thr, thr = (uint32) min(floor((double) p
+ * 2^32), 2^32 - 1); a kept element is multiplied by 1.0f / (1.0f - p) (formed once in fp32), a dropped one is exactly 0.0f.
+ *
+ * pna_tower_drop_train_fwd_f32: the base forward (edge == NULL: pna_tower_train_fwd_f32 on `base`; else pna_tower_edge_train_fwd_f32 on
+ *   `edge`, edge->base == base) whose last launch multiplies mask * hcat into the mixing Linear.  z, the batch statistics and the
+ *   running statistics are those of the undropped rows.
+ * pna_tower_drop_train_bwd_f32: the base backward whose first launch regenerates the mask: the hcat of the mixing weight's gradient is
+ *   the masked one and g_hcat = mask * (g_p W_mix) before it is stored and summed.  Nothing but (p, seed, offset) goes from the forward
+ *   to the backward.  Workspace and saved tensors: the base route's.  No float atomics; one key gives identical bits; p == 0 gives
+ *   the bits of the base calls.  PNA_E_INVALID: p outside [0, 1) or NaN, a short struct, base == NULL, edge->base != base, and
+ *   whatever the base call refuses.
+ * pna_dropout_mask_f32 (one launch): out[v, c] (V, ld >= C) = 0.0f or 1.0f / (1.0f - p) by the rule above; V C <= 2^40. */
+typedef struct pna_tower_drop_args {
+  uint32_t struct_size;    /* sizeof(pna_tower_drop_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const pna_tower_train_args* base;        /* everything the route without dropout takes */
+  const pna_tower_edge_train_args* edge;   /* NULL: no edge features; else edge->base == base */
+  float p;                 /* 0 <= p < 1 */
+  int32_t _pad0;
+  uint64_t seed;           /* the mask's key ... */
+  uint64_t offset;         /* ... and the high half of its counters */
+} pna_tower_drop_args;
+
+int pna_tower_drop_train_fwd_f32(const pna_tower_drop_args* args, pna_stream_t stream);
+int pna_tower_drop_train_bwd_f32(const pna_tower_drop_args* args, pna_stream_t stream);
+int pna_dropout_mask_f32(float* out, int64_t ld, int64_t V, int32_t C, float p, uint64_t seed, uint64_t offset, pna_stream_t stream);
 
 /* ---- The two ENDS of the molecule nets: the sum of embedding tables and the per-graph readout, one call each way ----------------
  * replaces: ogb's AtomEncoder as nets/HIV_graph_classification/pna_net.py:42 calls it (a sum of nine nn.Embedding lookups), the single

@@ -377,6 +377,13 @@ class PnaTowerEdgeTrainArgs(_Args):
     ]
 
 
+class PnaTowerDropArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32), ("base", ctypes.c_void_p), ("edge", ctypes.c_void_p),
+        ("p", ctypes.c_float), ("_pad0", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+    ]
+
+
 class PnaEmbedSumArgs(_Args):
     _fields_ = [
         ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
@@ -602,6 +609,12 @@ def lib():
         for fn in (L.pna_tower_edge_train_fwd_f32, L.pna_tower_edge_train_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaTowerEdgeTrainArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
+        for fn in (L.pna_tower_drop_train_fwd_f32, L.pna_tower_drop_train_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaTowerDropArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_dropout_mask_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_void_p]
+        L.pna_dropout_mask_f32.restype = ctypes.c_int
         L.pna_embed_sum_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
         L.pna_embed_sum_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_embed_sum_fwd_f32, L.pna_embed_sum_bwd_f32):

@@ -1098,6 +1098,104 @@ def tower_layer_edge_small_train(layer, graph, h, e, snorm_n, scales):
     return TowerLayerEdgeSmallTrainFn.apply(h, e, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)
 
 
+def _tower_drop_args(base, edge, key):
+    """The pna_tower_drop_args around `base` (and `edge`, or None) under the mask key (p, seed, offset)."""
+    d = _lib.PnaTowerDropArgs()
+    d.base = ctypes.cast(ctypes.pointer(base), ctypes.c_void_p)
+    if edge is not None:
+        d.edge = ctypes.cast(ctypes.pointer(edge), ctypes.c_void_p)
+    d.p, d.seed, d.offset = key
+    d._keep = (base, edge)
+    return d
+
+
+class TowerLayerDropSmallTrainFn(torch.autograd.Function):
+    """TowerLayerSmallTrainFn / TowerLayerEdgeSmallTrainFn for a PNALayer whose towers have dropout (models/dgl/pna_layer.py:75, in front
+    of the mixing network of :134-141): the training forward as ONE C call (pna_tower_drop_train_fwd_f32) and the backward as one
+    (pna_tower_drop_train_bwd_f32).  `e` is None for a layer without edge features.  `key` = (p, seed, offset), Python numbers: the
+    backward regenerates the forward's mask from them, no mask is saved.  `params` as in TowerLayerSmallTrainFn."""
+
+    @staticmethod
+    def forward(ctx, h, e, layer, graph, scales, snorm, key, *params):
+        T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
+        dev = h.device
+        x = h if h.stride(1) == 1 else h.contiguous()
+        ed = layer.towers[0].edge_dim if e is not None else 0
+        ef = None if e is None else (e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous())
+        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed)
+        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
+        saved = plan.new_saved()
+        mix = layer.mixing_network
+        slope = mix.activation.negative_slope
+        a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer), mix.linear.weight, mix.linear.bias, slope, layer.residual, saved)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        q = plan.edge_args(a, ef, saved) if ed else None
+        d = _tower_drop_args(a, q, key)
+        _lib.check(_lib.lib().pna_tower_drop_train_fwd_f32(ctypes.byref(d), _lib.stream_ptr(dev)), "pna_tower_drop_train_fwd_f32")
+        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope, ctx.key = plan, graph, layer, scales, snorm, saved, slope, key
+        ctx.has_e = ed > 0
+        ctx.save_for_backward(x, *(([ef] if ed else []) + list(params)))
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, *rest = ctx.saved_tensors
+        ef, params = (rest[0], rest[1:]) if ctx.has_e else (None, rest)
+        plan, layer = ctx.plan, ctx.layer
+        T, Fi, Fo, S, ed = plan.T, plan.Fi, plan.Fo, plan.S, plan.edge_dim
+        C = T * Fo
+        dev = x.device
+        go = go if go.stride(1) == 1 else go.contiguous()
+        need = ctx.needs_input_grad
+        g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
+        g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if (ed and need[1]) else None
+        g_wpre = torch.empty(T, Fi, 2 * Fi + ed, dtype=torch.float32, device=dev)
+        g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
+        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
+        g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
+        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
+        towers = []
+        for t in range(T):
+            w_pre, b_pre, w_post, b_post, gamma, beta = params[6 * t:6 * t + 6]
+            bn = layer.towers[t].batchnorm_h
+            towers.append((w_pre, b_pre, w_post, b_post, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
+        mix_w, mix_b = params[6 * T], params[6 * T + 1]
+        a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, towers, mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
+        has_affine = towers[0][4] is not None
+        grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
+                 for t in range(T)]
+        plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
+        q = plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True) if ed else None
+        d = _tower_drop_args(a, q, ctx.key)
+        _lib.check(_lib.lib().pna_tower_drop_train_bwd_f32(ctypes.byref(d), _lib.stream_ptr(dev)), "pna_tower_drop_train_bwd_f32")
+        res = [g_h if need[0] else None, g_e, None, None, None, None, None]
+        for t in range(T):
+            res += [grads[t][0], grads[t][1], grads[t][2], grads[t][3], grads[t][4], grads[t][5]]
+        res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
+        return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
+
+
+def tower_layer_drop_small_train(layer, graph, h, e, snorm_n, scales):
+    """tower_layer_small_train / tower_layer_edge_small_train for a layer whose towers have dropout, through TowerLayerDropSmallTrainFn;
+    the mask's key comes from the device's default generator (functional.tower_dropout_key), one per call; every tower's
+    num_batches_tracked advances like the module's own forward."""
+    from . import functional as PF
+    params = []
+    for t in layer.towers:
+        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        params += [pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias]
+    mix = layer.mixing_network.linear
+    snorm = None
+    if layer.towers[0].graph_norm:
+        snorm = snorm_n.reshape(-1)
+        snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
+    seed, offset = PF.tower_dropout_key(h.device, h.shape[0] * layer.out_dim)
+    key = (float(layer.towers[0].dropout), seed, offset)
+    return TowerLayerDropSmallTrainFn.apply(h, e if layer.edge_features else None, layer, graph, tuple(scales), snorm, key, *params, mix.weight, mix.bias)
+
+
 # ---- the two ends of the molecule nets: the sum of embedding tables and the per-graph readout (pna_net_ends.hip) -----------------
 _embed_ws = {}      # device -> the embedding backward's reusable workspace (no graph is at hand where the encoder runs)
 

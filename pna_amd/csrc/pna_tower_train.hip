@@ -15,6 +15,10 @@
 // for in-degrees <= 128: same bits, same arg indices; the std block is that kernel's on x_src without the destination term); column
 // sums are fp32 inside a 16-row tile and float64 across the tiles in a fixed order, in launches of their own (one workgroup per
 // column: no row workgroup re-adds the partial sums).
+//
+// Dropout inside the towers (pna_tower_drop_train_*_f32, pna_dropout_mask_f32): the two mixing kernels have a DROP instantiation that
+// applies a Philox4x32-10 mask (pna_philox.h) between the BatchNorms' output and the mixing Linear; the backward regenerates it from
+// the call's (seed, offset).  Every other launch is shared with the calls without dropout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -23,6 +27,7 @@
 
 #include "pna_amd.h"
 #include "pna_internal.h"
+#include "pna_philox.h"
 #include "pna_rowstats.h"
 #include "pna_train_dev.h"
 
@@ -69,6 +74,7 @@ struct KArgs {
   const int32_t* pos_t; const int32_t* items_t;             // backward: CSR position of transposed edge j; {u, beg, end, -1} per source row
   float* dm; float* ecsr;                                   // backward (E, T Fi) message gradient, (E, ED) copy of e, both in CSR order
   float* ge; long ld_ge;                                    // backward (E, ld_ge), original edge order, or NULL
+  pna_philox::Mask drop;                                    // pna_tower_drop_train_*: the dropout between the BatchNorms and the mixing Linear
 };
 
 __device__ __forceinline__ float leaky(float p, float slope) { return p > 0.f ? p : p * slope; }
@@ -340,7 +346,28 @@ __device__ __forceinline__ void bn_consts(const KArgs& g, int c, float& cm, floa
   cb = g.beta[t] ? g.beta[t][n] : 0.f;
 }
 
-// ---- forward, launch 4: hcat = (z - mean) (gamma invstd) + beta, p = W_mix hcat + b_mix (saved), out = [h +] leaky(p) of 16 rows ----
+// The dropout mask of a tile's rows [r0, r0 + nrows) x C: one Philox call per quad of four consecutive elements e = v C + c (a quad
+// straddles a row end whenever C % 4 != 0), f(r, c, keep) for each of its elements inside the tile -- every element exactly once.
+template <class F>
+__device__ __forceinline__ void tile_mask_each(const KArgs& g, int r0, int nrows, int tid, F f) {
+  const uint64_t e0 = (uint64_t)r0 * (uint64_t)g.C, e1 = e0 + (uint64_t)nrows * (uint64_t)g.C;
+  for (uint64_t q = (e0 >> 2) + (uint64_t)tid; q <= ((e1 - 1) >> 2); q += kThreads) {
+    uint32_t w[4];
+    pna_philox::quad_words(g.drop, q, w);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint64_t e = 4 * q + i;
+      if (e >= e0 && e < e1) {
+        const int d = (int)(e - e0), r = d / g.C;
+        f(r, d - r * g.C, w[i] >= g.drop.thr);
+      }
+    }
+  }
+}
+
+// ---- forward, launch 4: hcat = (z - mean) (gamma invstd) + beta, p = W_mix hcat + b_mix (saved), out = [h +] leaky(p) of 16 rows.
+// DROP (pna_tower_drop_train_fwd_f32): the tile holds mask * hcat -- a kept element times 1 / (1 - p), a dropped one exactly 0 ----
+template <bool DROP>
 __global__ __launch_bounds__(kThreads) void k_tt_mix_fwd(const KArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -349,15 +376,28 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_fwd(const KArgs g) {
   float* const HC = lds;                                    // [16][P]
   const int r0 = blockIdx.x * kRows;
   const int nrows = min(kRows, g.V - r0);
-  for (int i = tid; i < kRows * P; i += kThreads) {
-    const int r = i / P, c = i - r * P;
-    float v = 0.f;
-    if (c < C && r < nrows) {
+  if constexpr (DROP) {
+    for (int i = tid; i < kRows * P; i += kThreads) {       // the padding; the quads below write every element inside the tile
+      const int r = i / P, c = i - r * P;
+      if (c >= C || r >= nrows) HC[i] = 0.f;
+    }
+    tile_mask_each(g, r0, nrows, tid, [&](int r, int c, bool keep) {
       float cm, ci, ca, cb;
       bn_consts(g, c, cm, ci, ca, cb);
-      v = bn_affine(g.z[(size_t)(r0 + r) * C + c], cm, ca, cb);
+      const float v = bn_affine(g.z[(size_t)(r0 + r) * C + c], cm, ca, cb);
+      HC[r * P + c] = keep ? v * g.drop.scale : 0.f;
+    });
+  } else {
+    for (int i = tid; i < kRows * P; i += kThreads) {
+      const int r = i / P, c = i - r * P;
+      float v = 0.f;
+      if (c < C && r < nrows) {
+        float cm, ci, ca, cb;
+        bn_consts(g, c, cm, ci, ca, cb);
+        v = bn_affine(g.z[(size_t)(r0 + r) * C + c], cm, ca, cb);
+      }
+      HC[i] = v;
     }
-    HC[i] = v;
   }
   __syncthreads();
   for (int nt = wave; nt < NT; nt += kWaves) {
@@ -396,7 +436,9 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_fwd(const KArgs g) {
 }
 
 // ---- backward, launch 1: g_p = grad_out leaky'(p), hcat (both stored for the mixing weight's gradient), g_hcat = g_p W_mix (stored),
-// the tile's column sums of g_hcat and g_hcat xhat ----
+// the tile's column sums of g_hcat and g_hcat xhat.  DROP (pna_tower_drop_train_bwd_f32): the forward's mask, regenerated from the key --
+// the stored hcat is the masked one, g_hcat = mask * (g_p W_mix) before it is stored and before the column sums ----
+template <bool DROP>
 __global__ __launch_bounds__(kThreads) void k_tt_mix_bwd(const KArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -414,11 +456,24 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_bwd(const KArgs g) {
       const float p = g.p[row * C + c], go = g.go[row * g.ld_go + c];
       v = p > 0.f ? go : go * g.slope;
       g.gp[row * C + c] = v;
-      float cm, ci, ca, cb;
-      bn_consts(g, c, cm, ci, ca, cb);
-      g.hcat[row * C + c] = bn_affine(g.z[row * C + c], cm, ca, cb);
+      if constexpr (!DROP) {
+        float cm, ci, ca, cb;
+        bn_consts(g, c, cm, ci, ca, cb);
+        g.hcat[row * C + c] = bn_affine(g.z[row * C + c], cm, ca, cb);
+      }
     }
     GP[i] = v;
+  }
+  if constexpr (DROP) {
+    // the masked hcat, and the mask's factor parked in GH where the g_hcat of the same element lands below
+    tile_mask_each(g, r0, nrows, tid, [&](int r, int c, bool keep) {
+      const size_t row = (size_t)(r0 + r);
+      float cm, ci, ca, cb;
+      bn_consts(g, c, cm, ci, ca, cb);
+      const float v = bn_affine(g.z[row * C + c], cm, ca, cb);
+      g.hcat[row * C + c] = keep ? v * g.drop.scale : 0.f;
+      GH[r * PG + c] = keep ? g.drop.scale : 0.f;
+    });
   }
   __syncthreads();
   // g_hcat tile (16 rows x 16 columns j): A = g_p (K = the mixing output n), B[k = n][j] = W_mix[n][j]
@@ -442,8 +497,14 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_bwd(const KArgs g) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = 4 * lg + i;
-        GH[r * PG + j] = acc[i];
-        if (r < nrows) g.ghc[(size_t)(r0 + r) * C + j] = acc[i];
+        if constexpr (DROP) {
+          const float gv = (r < nrows && GH[r * PG + j] > 0.f) ? acc[i] * g.drop.scale : 0.f;     // (rows past the end hold no factor)
+          GH[r * PG + j] = gv;
+          if (r < nrows) g.ghc[(size_t)(r0 + r) * C + j] = gv;
+        } else {
+          GH[r * PG + j] = acc[i];
+          if (r < nrows) g.ghc[(size_t)(r0 + r) * C + j] = acc[i];
+        }
       }
     }
   }
@@ -900,7 +961,7 @@ int weight_grad(const float* gy, int64_t ldg, int N, const float* a, int64_t lda
   return PNA_OK;
 }
 
-template <bool EDGE>
+template <bool EDGE, bool DROP = false>
 int launch_fwd(const KArgs& g, const Layout& l, hipStream_t st, const char* failed) {
   const int Fi = g.Fi, C = g.C, in_dim = g.div ? g.TFi : Fi;
   const dim3 grid((unsigned)l.n_tile), block(kThreads);
@@ -912,18 +973,21 @@ int launch_fwd(const KArgs& g, const Layout& l, hipStream_t st, const char* fail
   else if (g.S == 2) hipLaunchKernelGGL((k_tt_rows_fwd<2, EDGE>), grid, block, lds, st, g);
   else hipLaunchKernelGGL((k_tt_rows_fwd<3, EDGE>), grid, block, lds, st, g);
   hipLaunchKernelGGL(k_tt_bn_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
-  hipLaunchKernelGGL(k_tt_mix_fwd, grid, block, (size_t)kRows * pitch_of(quads(C)) * sizeof(float), st, g);
+  hipLaunchKernelGGL(k_tt_mix_fwd<DROP>, grid, block, (size_t)kRows * pitch_of(quads(C)) * sizeof(float), st, g);
   if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, failed);
   return PNA_OK;
 }
 
 // q != NULL: the backward with edge features -- the per-edge message gradient and its pull instead of rowprep + the ranked pull
-int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, pna_stream_t stream, const pna_tower_edge_train_args* q, const char* failed) {
+int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, pna_stream_t stream, const pna_tower_edge_train_args* q, const char* failed,
+               bool drop = false) {
   hipStream_t st = (hipStream_t)stream;
   const int T = g.T, Fi = g.Fi, Fo = g.Fo, S = g.S, C = g.C, TFi = g.TFi, K = 4 * Fi;
   const dim3 grid((unsigned)l.n_tile), block(kThreads);
   // 1. the mixing network, 2. the column sums, 3. gz and the aggregate's gradient
-  hipLaunchKernelGGL(k_tt_mix_bwd, grid, block, ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float), st, g);
+  const size_t lds_mix = ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float);
+  if (drop) hipLaunchKernelGGL(k_tt_mix_bwd<true>, grid, block, lds_mix, st, g);
+  else hipLaunchKernelGGL(k_tt_mix_bwd<false>, grid, block, lds_mix, st, g);
   hipLaunchKernelGGL(k_tt_bwd_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
   const size_t lds = ((size_t)T * kRows * pitch_of(quads(Fo)) + 4 * kRows) * sizeof(float);
   if (S == 1) hipLaunchKernelGGL(k_tt_rows_bwd<1>, grid, block, lds, st, g);
@@ -999,6 +1063,42 @@ int fill_edge(const pna_tower_edge_train_args* q, KArgs& g, Layout& l, bool bwd)
   return fill(q->base, g, l, bwd, who, q);
 }
 
+// pna_tower_drop_train_*: its own checks, then the base route's (with or without edge features); the mask's constants into g.drop
+int fill_drop(const pna_tower_drop_args* d, KArgs& g, Layout& l, bool bwd) {
+  const char* const who = bwd ? "pna_tower_drop_train_bwd_f32: needs 0 <= p < 1, a base pna_tower_train_bwd_f32 accepts and edge == NULL, or an edge "
+                                "pna_tower_edge_train_bwd_f32 accepts with edge->base == base"
+                              : "pna_tower_drop_train_fwd_f32: needs 0 <= p < 1, a base pna_tower_train_fwd_f32 accepts and edge == NULL, or an edge "
+                                "pna_tower_edge_train_fwd_f32 accepts with edge->base == base";
+  if (!d) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(bwd ? "pna_tower_drop_train_bwd_f32" : "pna_tower_drop_train_fwd_f32", d->struct_size, sizeof(*d))) return rc_ss;
+  if (!(d->p >= 0.f && d->p < 1.f) || !d->base) return pna_set_error(PNA_E_INVALID, who);      // (a NaN fails both comparisons)
+  if (d->edge) {
+    if (int rc_ss = pna_check_struct_size(bwd ? "pna_tower_drop_train_bwd_f32" : "pna_tower_drop_train_fwd_f32", d->edge->struct_size, sizeof(*d->edge)))
+      return rc_ss;
+    if (d->edge->base != d->base) return pna_set_error(PNA_E_INVALID, who);
+  }
+  const int rc = fill(d->base, g, l, bwd, who, d->edge);
+  if (rc != PNA_OK) return rc;
+  g.drop = pna_philox::make_mask(d->p, d->seed, d->offset);
+  return PNA_OK;
+}
+
+// out[v, c] = the factor of element (v, c) under the mask rule: 0 or 1 / (1 - p).  One thread per quad of four consecutive elements.
+__global__ __launch_bounds__(256) void k_dropout_mask(float* out, long ld, uint64_t n, int C, const pna_philox::Mask m) {
+  const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (4 * q >= n) return;
+  uint32_t w[4];
+  pna_philox::quad_words(m, q, w);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint64_t e = 4 * q + i;
+    if (e < n) {
+      const uint64_t v = e / (uint64_t)C;
+      out[v * (uint64_t)ld + (e - v * (uint64_t)C)] = w[i] >= m.thr ? m.scale : 0.f;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t pna_tower_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input) {
@@ -1048,4 +1148,33 @@ extern "C" int pna_tower_edge_train_bwd_f32(const pna_tower_edge_train_args* q, 
   const int rc = fill_edge(q, g, l, true);
   if (rc != PNA_OK) return rc;
   return launch_bwd(q->base, g, l, stream, q, "pna_tower_edge_train_bwd_f32: launch failed");
+}
+
+extern "C" int pna_tower_drop_train_fwd_f32(const pna_tower_drop_args* d, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill_drop(d, g, l, false);
+  if (rc != PNA_OK) return rc;
+  if (d->edge) return launch_fwd<true, true>(g, l, (hipStream_t)stream, "pna_tower_drop_train_fwd_f32: launch failed");
+  return launch_fwd<false, true>(g, l, (hipStream_t)stream, "pna_tower_drop_train_fwd_f32: launch failed");
+}
+
+extern "C" int pna_tower_drop_train_bwd_f32(const pna_tower_drop_args* d, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill_drop(d, g, l, true);
+  if (rc != PNA_OK) return rc;
+  return launch_bwd(d->base, g, l, stream, d->edge, "pna_tower_drop_train_bwd_f32: launch failed", true);
+}
+
+extern "C" int pna_dropout_mask_f32(float* out, int64_t ld, int64_t V, int32_t C, float p, uint64_t seed, uint64_t offset, pna_stream_t stream) {
+  if (!out || V < 0 || C < 1 || ld < C || !(p >= 0.f && p < 1.f) || V > (int64_t)((1ull << 40) / (uint64_t)C))
+    return pna_set_error(PNA_E_INVALID, "pna_dropout_mask_f32: needs out, V >= 0, C >= 1, ld >= C, V C <= 2^40, 0 <= p < 1");
+  const uint64_t n = (uint64_t)V * (uint64_t)C;
+  if (n == 0) return PNA_OK;
+  const uint64_t quads4 = (n + 3) / 4;
+  hipLaunchKernelGGL(k_dropout_mask, dim3((unsigned)((quads4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (long)ld, n, (int)C,
+                     pna_philox::make_mask(p, seed, offset));
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_dropout_mask_f32: launch failed");
+  return PNA_OK;
 }

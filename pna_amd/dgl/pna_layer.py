@@ -396,9 +396,20 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
         graph.  A gradient is wanted if h, e or any parameter requires one."""
         return self._small_tower_train_clauses(graph, h, snorm_n, PF.SMALL_TOWER_TRAIN_EDGE_ROWS, True, e)
 
-    def _small_tower_train_clauses(self, graph, h, snorm_n, rows, edge, e):
-        """The clauses of the two one-call training routes: `rows` the route's knob, `edge` whether it is the route with edge features
-        (required of the layer and every tower) or the one without (excluded), `e` the edge route's features."""
+    def _small_tower_drop_train_path(self, graph, h, e, snorm_n=None):
+        """Whether this call is served by pna_tower_drop_train_fwd_f32 / _bwd_f32 (autograd.TowerLayerDropSmallTrainFn): the clauses of
+        _small_tower_train_path with the knob PNA_AMD_SMALL_TOWER_TRAIN_DROPOUT_ROWS in place of the other two, edge features allowed
+        either way (the clauses of _small_tower_train_edge_path apply when the layer has them) and, instead of no dropout inside the
+        towers, one dropout 0 < p < 1 for all towers.  Not while the stream is being captured: the mask's key is drawn on the host, a
+        replay would repeat the captured mask.  Dropout in the mixing network stays outside."""
+        if not self._small_tower_train_clauses(graph, h, snorm_n, PF.SMALL_TOWER_TRAIN_DROPOUT_ROWS, bool(self.edge_features), e, drop=True):
+            return False
+        return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())     # (the query needs a device)
+
+    def _small_tower_train_clauses(self, graph, h, snorm_n, rows, edge, e, drop=False):
+        """The clauses of the one-call training routes: `rows` the route's knob, `edge` whether it is the route with edge features
+        (required of the layer and every tower) or the one without (excluded), `e` the edge route's features, `drop` whether the towers'
+        dropout has to be active (one p in (0, 1) for all towers) or absent."""
         V = h.shape[0]
         if not (rows > 0 and 0 < V <= rows):
             return False
@@ -420,7 +431,8 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
                 return False
         for t in towers:
             bn = t.batchnorm_h
-            if not (t.training and bn.training and t.batch_norm and bool(t.edge_features) == edge and t.dropout == 0 and t.graph_norm == t0.graph_norm
+            drop_ok = (0 < t.dropout < 1 and t.dropout == t0.dropout) if drop else t.dropout == 0
+            if not (t.training and bn.training and t.batch_norm and bool(t.edge_features) == edge and drop_ok and t.graph_norm == t0.graph_norm
                     and tuple(t.aggregators) == tuple(t0.aggregators) and tuple(t.scalers) == tuple(t0.scalers)
                     and len(t.pretrans.fully_connected) == 1 and len(t.posttrans.fully_connected) == 1):
                 return False
@@ -502,6 +514,12 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
             from .. import autograd as AG
             t0 = self.towers[0]
             return AG.tower_layer_edge_small_train(self, graph, h, e, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
+        if PF.SMALL_TOWER_TRAIN_DROPOUT_ROWS > 0 and self._small_tower_drop_train_path(graph, h, e, snorm_n):
+            # the same for towers with dropout, with or without edge features (autograd.TowerLayerDropSmallTrainFn): the mask between the
+            # BatchNorms and the mixing network is made in the kernels from a key of the device's default generator
+            from .. import autograd as AG
+            t0 = self.towers[0]
+            return AG.tower_layer_drop_small_train(self, graph, h, e, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
         h_cat = _towers_forward(list(self.towers), graph, h, e, snorm_n, self.divide_input)
         mix = self.mixing_network
         if (h_cat.shape[1] >= 4 and isinstance(mix.activation, nn.LeakyReLU) and mix.b_norm is None and (mix.dropout is None or not self.training)

@@ -1222,6 +1222,33 @@ def small_tower_train_edge_fits(T, Fi, Fo, S=3, edge_dim=0):
     return small_tower_train_fits(T, Fi, Fo, S) and 1 <= edge_dim <= 64
 
 
+# PNALayer TRAINING batches whose towers have DROPOUT (0 < p < 1), with or without edge features, up to this many nodes take the
+# one-call route (autograd.TowerLayerDropSmallTrainFn: pna_tower_drop_train_fwd_f32 / _bwd_f32).  A knob of its own: the two above keep
+# their meaning and never serve such a layer.  0 = off, the default
+SMALL_TOWER_TRAIN_DROPOUT_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_DROPOUT_ROWS", "0"))
+
+
+def tower_dropout_key(device, n):
+    """(seed, offset) of one dropout mask over n elements, taken from the device's default torch generator, which then moves past the
+    4 ceil(n / 4) words the mask may use: torch.manual_seed makes a run reproducible and torch's own random ops behind the call draw
+    from fresh counters.  Host state only: no synchronisation."""
+    device = torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    gen = torch.cuda.default_generators[index]
+    seed, offset = int(gen.initial_seed()), int(gen.get_offset())
+    gen.set_offset(offset + 4 * ((int(n) + 3) // 4))
+    return seed, offset
+
+
+def dropout_mask(V, C, p, seed, offset, device):
+    """The (V, C) fp32 factors of the mask rule of include/pna_amd.h (pna_dropout_mask_f32): 0 for a dropped element, 1 / (1 - p) for a
+    kept one -- what pna_tower_drop_train_*_f32 apply to the towers' concatenated BatchNorm output under the key (seed, offset)."""
+    out = torch.empty(int(V), int(C), dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().pna_dropout_mask_f32(out.data_ptr(), out.stride(0) if V else int(C), int(V), int(C), float(p), int(seed) & (2 ** 64 - 1),
+                                               int(offset) & (2 ** 64 - 1), _lib.stream_ptr(out.device)), "pna_dropout_mask_f32")
+    return out
+
+
 # The two ENDS of the molecule nets -- the sum of embedding tables (AtomEncoderStandIn, nets.embed) and the per-graph readout
 # (nets.readout_nodes) -- take the one-call route (autograd.EmbedSumFn / ReadoutFn: pna_embed_sum_*_f32, pna_readout_*_f32) on calls of up
 # to this many rows.  0 = off, the default (DESIGN.md 4.19)
