@@ -710,11 +710,20 @@ def _transposed_whole_rows(graph):
     return tcsr.col, rank_t, gT.work_items(threshold=1 << 30)
 
 
-class _SmallTrainPlan:
-    """What one call of SimpleLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays (kept on the graph, like
-    the pull of the generic route keeps them) and the call's workspace -- the graph's reusable scratch (Graph.workspace: allocated once
+class _GraphScratchPlan:
+    """What the one-call training plans share: the call's workspace out of the graph's reusable scratch (Graph.workspace: allocated once
     per graph, grown to the widest layer seen; every launch writes what it reads, nothing is carried from the forward to the backward).
-    Nothing here depends on weight values.  One caller at a time per Graph (functional.py's rule for the shared scratch)."""
+    One caller at a time per Graph (functional.py's rule for the shared scratch)."""
+
+    def take_workspace(self, graph, nbytes):
+        ws = graph.workspace(nbytes + 256)
+        self.ws = ws[(-ws.data_ptr() // 4) % 64:][:nbytes // 4]                 # 256-byte aligned
+        self.nbytes = nbytes
+
+
+class _SmallTrainPlan(_GraphScratchPlan):
+    """What one call of SimpleLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays (kept on the graph, like
+    the pull of the generic route keeps them) and the call's workspace.  Nothing here depends on weight values."""
 
     def __init__(self, graph, F, N, S, dev):
         csr = graph.csr
@@ -724,9 +733,7 @@ class _SmallTrainPlan:
         nbytes = _lib.lib().pna_simple_train_workspace_bytes(V, E, F, N, S)
         if nbytes < 0:
             raise RuntimeError("SimpleLayerSmallTrainFn: shape outside pna_simple_train_*_f32 (the layer checks it before taking this path)")
-        ws = graph.workspace(nbytes + 256)
-        self.ws = ws[(-ws.data_ptr() // 4) % 64:][:nbytes // 4]                 # 256-byte aligned
-        self.nbytes = nbytes
+        self.take_workspace(graph, nbytes)
 
     def new_saved(self):
         """The state one forward leaves for its backward -- a (V, 4F) | z (V, N) | save_mean, save_invstd [N] in one buffer, argmax |
@@ -820,10 +827,9 @@ def simple_layer_small_train(layer, graph, h, scales):
     return SimpleLayerSmallTrainFn.apply(h, lin.weight, lin.bias, bn.weight, bn.bias, layer, graph, tuple(scales))
 
 
-class _TowerTrainPlan:
-    """What one call of TowerLayerSmallTrainFn needs besides the layer's tensors: the transposed graph's arrays and the call's
-    workspace (Graph.workspace: every launch writes what it reads, nothing is carried from the forward to the backward).  Nothing here
-    depends on weight values.  One caller at a time per Graph.  edge_dim > 0: the plan of TowerLayerEdgeSmallTrainFn
+class _TowerTrainPlan(_GraphScratchPlan):
+    """What one call of the three tower training Functions needs besides the layer's tensors: the transposed graph's arrays and the
+    call's workspace.  Nothing here depends on weight values.  edge_dim > 0: the plan of a layer with edge features
     (pna_tower_edge_train_*_f32) -- its larger workspace, the int32 edge ids and the transposed edges' CSR positions (both kept on the
     graph), x_edge in the saved state."""
 
@@ -843,9 +849,7 @@ class _TowerTrainPlan:
             nbytes = _lib.lib().pna_tower_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div))
         if nbytes < 0:
             raise RuntimeError("TowerLayerSmallTrainFn: shape outside pna_tower_train_*_f32 (the layer checks it before taking this path)")
-        ws = graph.workspace(nbytes + 256)
-        self.ws = ws[(-ws.data_ptr() // 4) % 64:][:nbytes // 4]                 # 256-byte aligned
-        self.nbytes = nbytes
+        self.take_workspace(graph, nbytes)
 
     def new_saved(self):
         """The state one forward leaves for its backward -- x_cat (V, 2 T Fi) | a (V, T 4 Fi) | z (V, C) | p (V, C) | save_mean,
@@ -935,167 +939,14 @@ class _TowerTrainPlan:
         return a
 
 
-def _tower_train_tensors(layer):
-    """Per tower (w_pre, b_pre, w_post, b_post, gamma, beta, running_mean, running_var, eps, momentum) from the modules' own tensors."""
+def _tower_train_tensors(layer, params):
+    """Per tower (w_pre, b_pre, w_post, b_post, gamma, beta, running_mean, running_var, eps, momentum) for _TowerTrainPlan.args: the six
+    tensors out of `params` (the modules' own in a forward, the saved ones in a backward), the rest from the layer's modules."""
     out = []
-    for t in layer.towers:
-        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
-        out.append((pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
+    for t, tower in enumerate(layer.towers):
+        bn = tower.batchnorm_h
+        out.append((*params[6 * t:6 * t + 6], bn.running_mean, bn.running_var, bn.eps, bn.momentum))
     return out
-
-
-class TowerLayerSmallTrainFn(torch.autograd.Function):
-    """PNALayer's training forward (per tower: pretrans, gather, scalers, posttrans, graph norm, batch-statistics BatchNorm; the mixing
-    Linear + LeakyReLU, the residual: models/dgl/pna_layer.py:55-76, 130-145) on a molecule-sized batch as ONE C call
-    (pna_tower_train_fwd_f32) and its backward as one (pna_tower_train_bwd_f32).  The weights are the modules' own tensors (no stack, no
-    packed image); the output, the gradients and the state a forward saves for its backward are fresh tensors per call.  `params`: per
-    tower w_pre, b_pre, w_post, b_post, gamma, beta; then the mixing weight and bias."""
-
-    @staticmethod
-    def forward(ctx, h, layer, graph, scales, snorm, *params):
-        T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
-        dev = h.device
-        x = h if h.stride(1) == 1 else h.contiguous()
-        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev)
-        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
-        saved = plan.new_saved()
-        mix = layer.mixing_network
-        slope = mix.activation.negative_slope
-        a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer), mix.linear.weight, mix.linear.bias, slope, layer.residual, saved)
-        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
-        _lib.check(_lib.lib().pna_tower_train_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_tower_train_fwd_f32")
-        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope = plan, graph, layer, scales, snorm, saved, slope
-        ctx.save_for_backward(x, *params)
-        return out
-
-    @staticmethod
-    def backward(ctx, go):
-        x, *params = ctx.saved_tensors
-        plan, layer = ctx.plan, ctx.layer
-        T, Fi, Fo, S = plan.T, plan.Fi, plan.Fo, plan.S
-        C = T * Fo
-        dev = x.device
-        go = go if go.stride(1) == 1 else go.contiguous()
-        g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
-        # one buffer per kind of parameter: (T, ...) blocks the towers' gradients are views of
-        g_wpre = torch.empty(T, Fi, 2 * Fi, dtype=torch.float32, device=dev)
-        g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
-        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
-        g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
-        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
-        towers = []
-        for t in range(T):
-            w_pre, b_pre, w_post, b_post, gamma, beta = params[6 * t:6 * t + 6]
-            bn = layer.towers[t].batchnorm_h
-            towers.append((w_pre, b_pre, w_post, b_post, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
-        mix_w, mix_b = params[6 * T], params[6 * T + 1]
-        a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, towers, mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
-        has_affine = towers[0][4] is not None
-        grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
-                 for t in range(T)]
-        plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
-        _lib.check(_lib.lib().pna_tower_train_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_tower_train_bwd_f32")
-        need = ctx.needs_input_grad
-        res = [g_h if need[0] else None, None, None, None, None]
-        for t in range(T):
-            res += [grads[t][0], grads[t][1], grads[t][2], grads[t][3], grads[t][4], grads[t][5]]
-        res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
-        return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
-
-
-def tower_layer_small_train(layer, graph, h, snorm_n, scales):
-    """[h +] leaky(mixing(cat_t bn_t(graph_norm(posttrans_t(...))))) of a training PNALayer through TowerLayerSmallTrainFn; every tower's
-    num_batches_tracked advances like the module's own forward."""
-    params = []
-    for t in layer.towers:
-        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
-        if bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-        params += [pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias]
-    mix = layer.mixing_network.linear
-    snorm = None
-    if layer.towers[0].graph_norm:
-        snorm = snorm_n.reshape(-1)
-        snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
-    return TowerLayerSmallTrainFn.apply(h, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)
-
-
-class TowerLayerEdgeSmallTrainFn(torch.autograd.Function):
-    """TowerLayerSmallTrainFn for a PNALayer with edge features (models/dgl/pna_layer.py:35-40: the pretrans on [h_u | h_v | ef]): the
-    training forward as ONE C call (pna_tower_edge_train_fwd_f32) and the backward as one (pna_tower_edge_train_bwd_f32).  `e` (E,
-    edge_dim), in the graph's original edge order, is an input: its gradient comes back when it needs one.  `params` as in
-    TowerLayerSmallTrainFn; a tower's pretrans weight is (Fi, 2 Fi + edge_dim)."""
-
-    @staticmethod
-    def forward(ctx, h, e, layer, graph, scales, snorm, *params):
-        T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
-        dev = h.device
-        x = h if h.stride(1) == 1 else h.contiguous()
-        ef = e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous()
-        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=layer.towers[0].edge_dim)
-        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
-        saved = plan.new_saved()
-        mix = layer.mixing_network
-        slope = mix.activation.negative_slope
-        a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer), mix.linear.weight, mix.linear.bias, slope, layer.residual, saved)
-        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
-        q = plan.edge_args(a, ef, saved)
-        _lib.check(_lib.lib().pna_tower_edge_train_fwd_f32(ctypes.byref(q), _lib.stream_ptr(dev)), "pna_tower_edge_train_fwd_f32")
-        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope = plan, graph, layer, scales, snorm, saved, slope
-        ctx.save_for_backward(x, ef, *params)
-        return out
-
-    @staticmethod
-    def backward(ctx, go):
-        x, ef, *params = ctx.saved_tensors
-        plan, layer = ctx.plan, ctx.layer
-        T, Fi, Fo, S, ed = plan.T, plan.Fi, plan.Fo, plan.S, plan.edge_dim
-        C = T * Fo
-        dev = x.device
-        go = go if go.stride(1) == 1 else go.contiguous()
-        need = ctx.needs_input_grad
-        g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
-        g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if need[1] else None
-        g_wpre = torch.empty(T, Fi, 2 * Fi + ed, dtype=torch.float32, device=dev)
-        g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
-        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
-        g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
-        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
-        towers = []
-        for t in range(T):
-            w_pre, b_pre, w_post, b_post, gamma, beta = params[6 * t:6 * t + 6]
-            bn = layer.towers[t].batchnorm_h
-            towers.append((w_pre, b_pre, w_post, b_post, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
-        mix_w, mix_b = params[6 * T], params[6 * T + 1]
-        a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, towers, mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
-        has_affine = towers[0][4] is not None
-        grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
-                 for t in range(T)]
-        plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
-        q = plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True)
-        _lib.check(_lib.lib().pna_tower_edge_train_bwd_f32(ctypes.byref(q), _lib.stream_ptr(dev)), "pna_tower_edge_train_bwd_f32")
-        res = [g_h if need[0] else None, g_e, None, None, None, None]
-        for t in range(T):
-            res += [grads[t][0], grads[t][1], grads[t][2], grads[t][3], grads[t][4], grads[t][5]]
-        res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
-        return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
-
-
-def tower_layer_edge_small_train(layer, graph, h, e, snorm_n, scales):
-    """tower_layer_small_train for a layer with edge features, through TowerLayerEdgeSmallTrainFn; every tower's num_batches_tracked
-    advances like the module's own forward."""
-    params = []
-    for t in layer.towers:
-        pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
-        if bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-        params += [pre.weight, pre.bias, post.weight, post.bias, bn.weight, bn.bias]
-    mix = layer.mixing_network.linear
-    snorm = None
-    if layer.towers[0].graph_norm:
-        snorm = snorm_n.reshape(-1)
-        snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
-    return TowerLayerEdgeSmallTrainFn.apply(h, e, layer, graph, tuple(scales), snorm, *params, mix.weight, mix.bias)
 
 
 def _tower_drop_args(base, edge, key):
@@ -1109,77 +960,121 @@ def _tower_drop_args(base, edge, key):
     return d
 
 
-class TowerLayerDropSmallTrainFn(torch.autograd.Function):
-    """TowerLayerSmallTrainFn / TowerLayerEdgeSmallTrainFn for a PNALayer whose towers have dropout (models/dgl/pna_layer.py:75, in front
-    of the mixing network of :134-141): the training forward as ONE C call (pna_tower_drop_train_fwd_f32) and the backward as one
-    (pna_tower_drop_train_bwd_f32).  `e` is None for a layer without edge features.  `key` = (p, seed, offset), Python numbers: the
-    backward regenerates the forward's mask from them, no mask is saved.  `params` as in TowerLayerSmallTrainFn."""
+def _tower_train_call(which, base, edge, key, dev):
+    """One of the three C entry pairs, `which` = "fwd" or "bwd": with a mask key pna_tower_drop_train_*_f32, else with an edge block
+    pna_tower_edge_train_*_f32, else pna_tower_train_*_f32."""
+    if key is not None:
+        name, block = f"pna_tower_drop_train_{which}_f32", _tower_drop_args(base, edge, key)
+    elif edge is not None:
+        name, block = f"pna_tower_edge_train_{which}_f32", edge
+    else:
+        name, block = f"pna_tower_train_{which}_f32", base
+    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(block), _lib.stream_ptr(dev)), name)
+
+
+def _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, key, params):
+    """The forward of the three tower training Functions.  e None or a layer without edge features: no edge block; key None: no dropout."""
+    T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
+    dev = h.device
+    x = h if h.stride(1) == 1 else h.contiguous()
+    ed = layer.towers[0].edge_dim if e is not None else 0
+    ef = None if not ed else (e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous())
+    plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed)
+    out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
+    saved = plan.new_saved()
+    slope = layer.mixing_network.activation.negative_slope
+    a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer, params), params[6 * T], params[6 * T + 1], slope, layer.residual, saved)
+    a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+    _tower_train_call("fwd", a, plan.edge_args(a, ef, saved) if ed else None, key, dev)
+    ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope, ctx.key = plan, graph, layer, scales, snorm, saved, slope, key
+    ctx.save_for_backward(x, *([ef] if ed else []), *params)
+    return out
+
+
+def _tower_train_backward(ctx, go, lead):
+    """The backward of the three tower training Functions; `lead`: how many inputs the Function has in front of `params` (h first, e
+    second where there is one).  The C call reads the SAVED tensors (autograd's version check covers them), the running statistics, eps
+    and momentum come from the modules."""
+    x, *params = ctx.saved_tensors
+    plan, layer = ctx.plan, ctx.layer
+    T, Fi, Fo, S, ed = plan.T, plan.Fi, plan.Fo, plan.S, plan.edge_dim
+    ef = params.pop(0) if ed else None
+    C = T * Fo
+    dev = x.device
+    go = go if go.stride(1) == 1 else go.contiguous()
+    need = ctx.needs_input_grad
+    g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
+    g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if (ed and need[1]) else None
+    # one buffer per kind of parameter: (T, ...) blocks the towers' gradients are views of
+    g_wpre = torch.empty(T, Fi, 2 * Fi + ed, dtype=torch.float32, device=dev)
+    g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
+    g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
+    g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
+    g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
+    mix_w, mix_b = params[6 * T], params[6 * T + 1]
+    a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, _tower_train_tensors(layer, params), mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
+    has_affine = params[4] is not None
+    grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
+             for t in range(T)]
+    plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
+    _tower_train_call("bwd", a, plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True) if ed else None, ctx.key, dev)
+    res = [g_h if need[0] else None, g_e] + [None] * (lead - 2)
+    for t in range(T):
+        res += grads[t]
+    res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
+    return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
+
+
+class TowerLayerSmallTrainFn(torch.autograd.Function):
+    """PNALayer's training forward (per tower: pretrans, gather, scalers, posttrans, graph norm, batch-statistics BatchNorm; the mixing
+    Linear + LeakyReLU, the residual: models/dgl/pna_layer.py:55-76, 130-145) on a molecule-sized batch as ONE C call
+    (pna_tower_train_fwd_f32) and its backward as one (pna_tower_train_bwd_f32).  The weights are the modules' own tensors (no stack, no
+    packed image); the output, the gradients and the state a forward saves for its backward are fresh tensors per call.  `params`: per
+    tower w_pre, b_pre, w_post, b_post, gamma, beta; then the mixing weight and bias.  This and the two Functions below are one forward
+    and one backward (_tower_train_forward, _tower_train_backward) behind three signatures."""
 
     @staticmethod
-    def forward(ctx, h, e, layer, graph, scales, snorm, key, *params):
-        T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
-        dev = h.device
-        x = h if h.stride(1) == 1 else h.contiguous()
-        ed = layer.towers[0].edge_dim if e is not None else 0
-        ef = None if e is None else (e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous())
-        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed)
-        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
-        saved = plan.new_saved()
-        mix = layer.mixing_network
-        slope = mix.activation.negative_slope
-        a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer), mix.linear.weight, mix.linear.bias, slope, layer.residual, saved)
-        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
-        q = plan.edge_args(a, ef, saved) if ed else None
-        d = _tower_drop_args(a, q, key)
-        _lib.check(_lib.lib().pna_tower_drop_train_fwd_f32(ctypes.byref(d), _lib.stream_ptr(dev)), "pna_tower_drop_train_fwd_f32")
-        ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope, ctx.key = plan, graph, layer, scales, snorm, saved, slope, key
-        ctx.has_e = ed > 0
-        ctx.save_for_backward(x, *(([ef] if ed else []) + list(params)))
-        return out
+    def forward(ctx, h, layer, graph, scales, snorm, *params):
+        return _tower_train_forward(ctx, h, None, layer, graph, scales, snorm, None, params)
 
     @staticmethod
     def backward(ctx, go):
-        x, *rest = ctx.saved_tensors
-        ef, params = (rest[0], rest[1:]) if ctx.has_e else (None, rest)
-        plan, layer = ctx.plan, ctx.layer
-        T, Fi, Fo, S, ed = plan.T, plan.Fi, plan.Fo, plan.S, plan.edge_dim
-        C = T * Fo
-        dev = x.device
-        go = go if go.stride(1) == 1 else go.contiguous()
-        need = ctx.needs_input_grad
-        g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
-        g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if (ed and need[1]) else None
-        g_wpre = torch.empty(T, Fi, 2 * Fi + ed, dtype=torch.float32, device=dev)
-        g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
-        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
-        g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
-        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
-        towers = []
-        for t in range(T):
-            w_pre, b_pre, w_post, b_post, gamma, beta = params[6 * t:6 * t + 6]
-            bn = layer.towers[t].batchnorm_h
-            towers.append((w_pre, b_pre, w_post, b_post, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum))
-        mix_w, mix_b = params[6 * T], params[6 * T + 1]
-        a = plan.args(ctx.graph, x, ctx.snorm, ctx.scales, towers, mix_w, mix_b, ctx.slope, layer.residual, ctx.state)
-        has_affine = towers[0][4] is not None
-        grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
-                 for t in range(T)]
-        plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
-        q = plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True) if ed else None
-        d = _tower_drop_args(a, q, ctx.key)
-        _lib.check(_lib.lib().pna_tower_drop_train_bwd_f32(ctypes.byref(d), _lib.stream_ptr(dev)), "pna_tower_drop_train_bwd_f32")
-        res = [g_h if need[0] else None, g_e, None, None, None, None, None]
-        for t in range(T):
-            res += [grads[t][0], grads[t][1], grads[t][2], grads[t][3], grads[t][4], grads[t][5]]
-        res += [g_mix[:C], g_mix[C] if mix_b is not None else None]
-        return tuple(r if (r is None or need[i]) else None for i, r in enumerate(res))
+        return _tower_train_backward(ctx, go, 5)
 
 
-def tower_layer_drop_small_train(layer, graph, h, e, snorm_n, scales):
-    """tower_layer_small_train / tower_layer_edge_small_train for a layer whose towers have dropout, through TowerLayerDropSmallTrainFn;
-    the mask's key comes from the device's default generator (functional.tower_dropout_key), one per call; every tower's
-    num_batches_tracked advances like the module's own forward."""
-    from . import functional as PF
+class TowerLayerEdgeSmallTrainFn(torch.autograd.Function):
+    """TowerLayerSmallTrainFn for a PNALayer with edge features (models/dgl/pna_layer.py:35-40: the pretrans on [h_u | h_v | ef]), through
+    pna_tower_edge_train_fwd_f32 / pna_tower_edge_train_bwd_f32.  `e` (E, edge_dim), in the graph's original edge order, is an input: its
+    gradient comes back when it needs one.  A tower's pretrans weight is (Fi, 2 Fi + edge_dim)."""
+
+    @staticmethod
+    def forward(ctx, h, e, layer, graph, scales, snorm, *params):
+        return _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, None, params)
+
+    @staticmethod
+    def backward(ctx, go):
+        return _tower_train_backward(ctx, go, 6)
+
+
+class TowerLayerDropSmallTrainFn(torch.autograd.Function):
+    """TowerLayerSmallTrainFn / TowerLayerEdgeSmallTrainFn for a PNALayer whose towers have dropout (models/dgl/pna_layer.py:75, in front
+    of the mixing network of :134-141), through pna_tower_drop_train_fwd_f32 / pna_tower_drop_train_bwd_f32.  `e` is None for a layer
+    without edge features.  `key` = (p, seed, offset), Python numbers: the backward regenerates the forward's mask from them, no mask is
+    saved."""
+
+    @staticmethod
+    def forward(ctx, h, e, layer, graph, scales, snorm, key, *params):
+        return _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, key, params)
+
+    @staticmethod
+    def backward(ctx, go):
+        return _tower_train_backward(ctx, go, 7)
+
+
+def _tower_train_inputs(layer, snorm_n):
+    """(snorm, *params) as the three Functions take them -- the graph norm's factor flattened (None for a layer without graph norm), per
+    tower w_pre, b_pre, w_post, b_post, gamma, beta, then the mixing weight and bias -- after advancing every tower's num_batches_tracked
+    like the module's own forward."""
     params = []
     for t in layer.towers:
         pre, post, bn = t.pretrans.fully_connected[0].linear, t.posttrans.fully_connected[0].linear, t.batchnorm_h
@@ -1191,23 +1086,45 @@ def tower_layer_drop_small_train(layer, graph, h, e, snorm_n, scales):
     if layer.towers[0].graph_norm:
         snorm = snorm_n.reshape(-1)
         snorm = snorm if snorm.is_contiguous() else snorm.contiguous()
+    return (snorm, *params, mix.weight, mix.bias)
+
+
+def tower_layer_small_train(layer, graph, h, snorm_n, scales):
+    """[h +] leaky(mixing(cat_t bn_t(graph_norm(posttrans_t(...))))) of a training PNALayer through TowerLayerSmallTrainFn."""
+    return TowerLayerSmallTrainFn.apply(h, layer, graph, tuple(scales), *_tower_train_inputs(layer, snorm_n))
+
+
+def tower_layer_edge_small_train(layer, graph, h, e, snorm_n, scales):
+    """tower_layer_small_train for a layer with edge features, through TowerLayerEdgeSmallTrainFn."""
+    return TowerLayerEdgeSmallTrainFn.apply(h, e, layer, graph, tuple(scales), *_tower_train_inputs(layer, snorm_n))
+
+
+def tower_layer_drop_small_train(layer, graph, h, e, snorm_n, scales):
+    """tower_layer_small_train / tower_layer_edge_small_train for a layer whose towers have dropout, through TowerLayerDropSmallTrainFn;
+    the mask's key comes from the device's default generator (functional.tower_dropout_key), one per call, drawn after the counters
+    have advanced."""
+    from . import functional as PF
+    snorm, *params = _tower_train_inputs(layer, snorm_n)
     seed, offset = PF.tower_dropout_key(h.device, h.shape[0] * layer.out_dim)
     key = (float(layer.towers[0].dropout), seed, offset)
-    return TowerLayerDropSmallTrainFn.apply(h, e if layer.edge_features else None, layer, graph, tuple(scales), snorm, key, *params, mix.weight, mix.bias)
+    return TowerLayerDropSmallTrainFn.apply(h, e if layer.edge_features else None, layer, graph, tuple(scales), snorm, key, *params)
+
+
+# ---- the routes below have no graph at hand: their backwards' workspaces are cached per device ----------------------------------------
+def _device_workspace(cache, dev, nbytes):
+    """(buffer, pointer): `cache`'s fp32 buffer on `dev`, ONE per device and route, grown when a larger call arrives (molecule batches
+    have another row count every step, so a buffer per size would never stop growing), and the address of `nbytes` bytes in it from a
+    16-byte boundary on.  Every launch writes what it reads and nothing is carried in it between calls; one caller at a time per device
+    and stream, like a graph's scratch."""
+    n = (nbytes + 16 + 3) // 4
+    buf = cache.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = cache[dev] = torch.empty(n, dtype=torch.float32, device=dev)
+    return buf, buf.data_ptr() + (-buf.data_ptr()) % 16
 
 
 # ---- the two ends of the molecule nets: the sum of embedding tables and the per-graph readout (pna_net_ends.hip) -----------------
 _embed_ws = {}      # device -> the embedding backward's reusable workspace (no graph is at hand where the encoder runs)
-
-
-def _embed_workspace(dev, nbytes):
-    """A cached fp32 buffer of at least `nbytes` on `dev`, grown when a larger call arrives.  Every launch writes what it reads and
-    nothing is carried in it between calls; one caller at a time per device and stream, like a graph's scratch."""
-    n = (nbytes + 3) // 4
-    buf = _embed_ws.get(dev)
-    if buf is None or buf.numel() < n:
-        buf = _embed_ws[dev] = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-    return buf
 
 
 def _embed_args(idx, tables):
@@ -1258,8 +1175,7 @@ class EmbedSumFn(torch.autograd.Function):
         V = idx.shape[0]
         slab = max(_lib.PNA_EMBED_SLAB_ROWS, -(-V // _lib.PNA_EMBED_MAX_SLABS))
         nbytes = -(-V // slab) * sum(rows) * ((F + 3) // 4 * 4) * 4
-        ws = _embed_workspace(dev, nbytes + 16)
-        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        a.workspace, a.workspace_bytes = _device_workspace(_embed_ws, dev, nbytes)[1], nbytes
         a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
         _lib.check(_lib.lib().pna_embed_sum_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_embed_sum_bwd_f32")
         return (None, *[g if ctx.needs_input_grad[1 + j] else None for j, g in enumerate(grads)])
@@ -1319,17 +1235,6 @@ def readout(h, offsets, op):
 
 # ---- the GRU update between two message-passing steps: nn.GRU over a length-1 sequence as a cell over rows (pna_gru.hip) -------------
 _gru_ws = {}        # device -> the backward's reusable workspace; nothing is keyed per module: a shared GRU has several calls alive
-
-
-def _gru_workspace(dev, nbytes):
-    """A cached fp32 buffer of at least `nbytes` (+ 16 for alignment) on `dev`, ONE per device, grown when a larger call arrives
-    (_embed_workspace's scheme: molecule batches have another row count every step, so a buffer per size would never stop growing).
-    Every launch writes what it reads and nothing is carried in it between calls; one caller at a time per device and stream."""
-    n = (nbytes + 16 + 3) // 4
-    buf = _gru_ws.get(dev)
-    if buf is None or buf.numel() < n:
-        buf = _gru_ws[dev] = torch.empty(n, dtype=torch.float32, device=dev)
-    return buf
 
 
 def _gru_rows(t):
@@ -1402,8 +1307,7 @@ class GruCellFn(torch.autograd.Function):
         # pna_gru_cell_workspace_bytes' formula (tests/test_gru_host.py holds the two together)
         slab = max(_lib.PNA_GRU_SLAB_ROWS, -(-V // _lib.PNA_GRU_MAX_SLABS))
         nbytes = 4 * (V * 4 * H + -(-V // slab) * 3 * H * (I + Hc + 2))
-        ws = _gru_workspace(dev, nbytes)
-        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        a.workspace, a.workspace_bytes = _device_workspace(_gru_ws, dev, nbytes)[1], nbytes
         _lib.check(_lib.lib().pna_gru_cell_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_gru_cell_bwd_f32")
         return gx, gh, gwi, gwh, gbi, gbh, None
 
@@ -1416,15 +1320,7 @@ def gru_cell(x, h, gru):
 
 
 # ---- the dense-adjacency PNALayer (the multitask GNN's convolution) as one C call each way (pna_dense_layer.hip) -------------------------
-_dense_ws = {}      # device -> the backward's reusable workspace (the slabs' gradient images); _gru_workspace's scheme
-
-
-def _dense_workspace(dev, nbytes):
-    n = (nbytes + 16 + 3) // 4
-    buf = _dense_ws.get(dev)
-    if buf is None or buf.numel() < n:
-        buf = _dense_ws[dev] = torch.empty(n, dtype=torch.float32, device=dev)
-    return buf
+_dense_ws = {}      # device -> the backward's reusable workspace (the slabs' gradient images)
 
 
 def _dense_args(cfg, x, adj, avg_log, avg_lin, params):
@@ -1495,8 +1391,7 @@ class DenseLayerFn(torch.autograd.Function):
         a.grad_w_mix, a.grad_b_mix = _lib.dev_ptr(grads[4 * T], torch.float32, "grad_w_mix"), _lib.dev_ptr(grads[4 * T + 1], torch.float32, "grad_b_mix")
         from .functional import dense_layer_workspace_bytes
         nbytes = dense_layer_workspace_bytes(B, N, T, Fi, Fo, len(aggr), len(scalers))
-        ws = _dense_workspace(dev, nbytes)
-        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        a.workspace, a.workspace_bytes = _device_workspace(_dense_ws, dev, nbytes)[1], nbytes
         _lib.check(_lib.lib().pna_dense_layer_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_dense_layer_bwd_f32")
         return (gx, None, None, None, None, *grads)
 
@@ -1532,15 +1427,7 @@ def dense_layer(layer, x, adj):
 
 
 # ---- the Set2Set graph readout (layers.Set2Set: the multitask GNN's graph head) as one C call each way (pna_set2set.hip) ----------------
-_s2s_ws = {}        # device -> the backward's reusable workspace (the slabs' records and gradient images); _gru_workspace's scheme
-
-
-def _s2s_workspace(dev, nbytes):
-    n = (nbytes + 16 + 3) // 4
-    buf = _s2s_ws.get(dev)
-    if buf is None or buf.numel() < n:
-        buf = _s2s_ws[dev] = torch.empty(n, dtype=torch.float32, device=dev)
-    return buf
+_s2s_ws = {}        # device -> the backward's reusable workspace (the slabs' records and gradient images)
 
 
 def _s2s_args(x, w_ih, w_hh, b_ih, b_hh, steps):
@@ -1584,8 +1471,7 @@ class Set2SetFn(torch.autograd.Function):
             setattr(a, f, _lib.dev_ptr(t, torch.float32, f))
         from .functional import set2set_workspace_bytes
         nbytes = set2set_workspace_bytes(B, N, D, ctx.steps)
-        ws = _s2s_workspace(dev, nbytes)
-        a.workspace, a.workspace_bytes = ws.data_ptr() + (-ws.data_ptr()) % 16, nbytes
+        a.workspace, a.workspace_bytes = _device_workspace(_s2s_ws, dev, nbytes)[1], nbytes
         _lib.check(_lib.lib().pna_set2set_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_set2set_bwd_f32")
         return (*grads, None)
 

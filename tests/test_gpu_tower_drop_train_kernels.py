@@ -17,81 +17,15 @@ import torch
 import tower_drop_train_cases as C
 from pna_amd import _lib, autograd as AG
 from pna_amd import functional as PF
-from pna_amd.dgl.pna_layer import _row_scales
-from pna_amd.graph import Graph
+from tower_train_run import Run
 
 pytestmark = pytest.mark.gpu
 
 CASES = list(C.CASES)
 
 
-class _Run:
-    """Forward + backward on a case's inputs through the two C calls with dropout under `key` = (p, seed, offset), or (key None) through
-    the calls without dropout: every output as a tensor."""
-
-    def __init__(self, name, dev, key):
-        meta, a, sd, _, _ = C.case(name)
-        self.meta, self.arrays, self.sd = meta, a, sd
-        V, T, div, ed = meta["N"], meta["towers"], meta["divide_input"], meta["edge_dim"]
-        Fi, Fo = (meta["in_dim"] // T if div else meta["in_dim"]), meta["out_dim"] // T
-        scalers = meta["scalers"].split()
-        S, Cc = len(scalers), T * Fo
-        self.T, self.Fi, self.Fo, self.S, self.ed = T, Fi, Fo, S, ed
-        self.g = g = Graph(a["src"], a["dst"], V).to(dev)
-        h, e = a["h"].to(dev), a["e"].to(dev)
-        sn = a["snorm_n"].reshape(-1).to(dev).contiguous()
-        scales = _row_scales(g, scalers, {"log": a["avg_log"]}, dev)
-        dsd = {k: v.to(dev) for k, v in sd.items()}
-        self.plan = plan = AG._TowerTrainPlan(g, T, Fi, Fo, S, div, dev, edge_dim=ed)
-        go = a["R"].to(dev)
-        L, st = _lib.lib(), _lib.stream_ptr(dev)
-        towers, running = [], {}
-        for t in range(T):
-            pre, post, bn = f"towers.{t}.pretrans.fully_connected.0.linear.", f"towers.{t}.posttrans.fully_connected.0.linear.", f"towers.{t}.batchnorm_h."
-            rm, rv = dsd[bn + "running_mean"].clone(), dsd[bn + "running_var"].clone()
-            running[bn + "running_mean"], running[bn + "running_var"] = rm, rv
-            towers.append((dsd[pre + "weight"], dsd[pre + "bias"], dsd[post + "weight"], dsd[post + "bias"], dsd[bn + "weight"], dsd[bn + "bias"], rm, rv, 1e-5, 0.1))
-        saved = plan.new_saved()
-        saved[0].fill_(float("nan"))
-        plan.ws.fill_(float("nan"))                             # (the workspace needs no initialisation)
-        out = torch.empty(V, Cc, device=dev)
-        args = plan.args(g, h, sn, scales, towers, dsd["mixing_network.linear.weight"], dsd["mixing_network.linear.bias"], C.SLOPE, meta["residual"], saved)
-        args.out, args.ld_out = out.data_ptr(), Cc
-        q = plan.edge_args(args, e, saved) if ed else None
-        if key is not None:
-            _lib.check(L.pna_tower_drop_train_fwd_f32(ctypes.byref(AG._tower_drop_args(args, q, key)), st), "fwd")
-        elif ed:
-            _lib.check(L.pna_tower_edge_train_fwd_f32(ctypes.byref(q), st), "fwd")
-        else:
-            _lib.check(L.pna_tower_train_fwd_f32(ctypes.byref(args), st), "fwd")
-        gh = torch.empty(V, meta["in_dim"], device=dev)
-        ge = torch.full((e.shape[0], ed), float("nan"), device=dev) if ed else None
-        grads, named = [], {}
-        for t in range(T):
-            gt = (torch.empty(Fi, 2 * Fi + ed, device=dev), torch.empty(Fi, device=dev), torch.empty(Fo, (1 + 4 * S) * Fi, device=dev),
-                  torch.empty(Fo, device=dev), torch.empty(Fo, device=dev), torch.empty(Fo, device=dev))
-            for x in gt:
-                x.fill_(float("nan"))
-            grads.append(gt)
-            pre, post, bn = f"towers.{t}.pretrans.fully_connected.0.linear.", f"towers.{t}.posttrans.fully_connected.0.linear.", f"towers.{t}.batchnorm_h."
-            named.update({pre + "weight": gt[0], pre + "bias": gt[1], post + "weight": gt[2], post + "bias": gt[3], bn + "weight": gt[4], bn + "bias": gt[5]})
-        gmw, gmb = torch.empty(Cc, Cc, device=dev), torch.empty(Cc, device=dev)
-        named.update({"mixing_network.linear.weight": gmw, "mixing_network.linear.bias": gmb})
-        plan.ws.fill_(float("nan"))                             # (the backward reads nothing the forward left there)
-        plan.set_backward(args, go, gh, grads, gmw, gmb)
-        qb = plan.edge_args(args, e, saved, grad_e=ge, backward=True) if ed else None
-        self.keep = (towers, grads, go, ge, args, qb)
-        if key is not None:
-            _lib.check(L.pna_tower_drop_train_bwd_f32(ctypes.byref(AG._tower_drop_args(args, qb, key)), st), "bwd")
-        elif ed:
-            _lib.check(L.pna_tower_edge_train_bwd_f32(ctypes.byref(qb), st), "bwd")
-        else:
-            _lib.check(L.pna_tower_train_bwd_f32(ctypes.byref(args), st), "bwd")
-        torch.cuda.synchronize(dev)
-        self.out, self.gh, self.ge, self.grads, self.running = out, gh, ge, named, running
-        self.x_cat, self.a, self.z, self.p, self.stats, self.amx, self.amn = plan.views(saved)
-        self.everything = [t.clone() for t in [out, self.x_cat, self.a, self.z, self.p, self.stats, self.amx, self.amn, gh] + ([ge] if ed else [])
-                           + list(named.values()) + list(running.values())]
+def _Run(name, dev, key):
+    return Run(name, C.case(name), dev, key=key)
 
 
 _runs = {}

@@ -8,78 +8,16 @@ import pytest
 import torch
 
 import tower_edge_train_cases as C
-from pna_amd import _lib, autograd as AG, ops
-from pna_amd.dgl.pna_layer import _row_scales
-from pna_amd.graph import Graph
+from pna_amd import _lib, ops
+from tower_train_run import Run
 
 pytestmark = pytest.mark.gpu
 
 CASES = C.KERNEL_CASES
 
 
-class _Run:
-    """Forward + backward through the two C calls on a case's inputs: every output as a tensor."""
-
-    def __init__(self, name, dev, repeat=1):
-        meta, a, sd, ref = C.case(name)
-        self.meta, self.arrays, self.sd, self.ref = meta, a, sd, ref
-        V, T, div, ed = meta["N"], meta["towers"], meta["divide_input"], meta["edge_dim"]
-        Fi, Fo = (meta["in_dim"] // T if div else meta["in_dim"]), meta["out_dim"] // T
-        scalers = meta["scalers"].split()
-        S, Cc = len(scalers), T * Fo
-        self.T, self.Fi, self.Fo, self.S, self.ed = T, Fi, Fo, S, ed
-        self.g = g = Graph(a["src"], a["dst"], V).to(dev)
-        self.h = h = a["h"].to(dev)
-        self.e = e = a["e"].to(dev)
-        E = e.shape[0]
-        sn = a["snorm_n"].reshape(-1).to(dev).contiguous()
-        self.scales = _row_scales(g, scalers, {"log": a["avg_log"]}, dev)
-        dsd = {k: v.to(dev) for k, v in sd.items()}
-        self.plan = plan = AG._TowerTrainPlan(g, T, Fi, Fo, S, div, dev, edge_dim=ed)
-        want_ge = name != "e_no_grad"
-        go = a["R"].to(dev)
-        self.history = []
-        for _ in range(repeat):
-            towers, running = [], {}
-            for t in range(T):
-                pre, post, bn = f"towers.{t}.pretrans.fully_connected.0.linear.", f"towers.{t}.posttrans.fully_connected.0.linear.", f"towers.{t}.batchnorm_h."
-                rm, rv = dsd[bn + "running_mean"].clone(), dsd[bn + "running_var"].clone()
-                running[bn + "running_mean"], running[bn + "running_var"] = rm, rv
-                towers.append((dsd[pre + "weight"], dsd[pre + "bias"], dsd[post + "weight"], dsd[post + "bias"], dsd[bn + "weight"], dsd[bn + "bias"],
-                               rm, rv, 1e-5, 0.1))
-            saved = plan.new_saved()
-            saved[0].fill_(float("nan"))
-            plan.ws.fill_(float("nan"))                         # (the workspace needs no initialisation)
-            out = torch.empty(V, Cc, device=dev)
-            args = plan.args(g, h, sn, self.scales, towers, dsd["mixing_network.linear.weight"], dsd["mixing_network.linear.bias"], C.SLOPE,
-                             meta["residual"], saved)
-            args.out, args.ld_out = out.data_ptr(), Cc
-            q = plan.edge_args(args, e, saved)
-            _lib.check(_lib.lib().pna_tower_edge_train_fwd_f32(ctypes.byref(q), _lib.stream_ptr(dev)), "fwd")
-            gh = torch.empty(V, meta["in_dim"], device=dev)
-            ge = torch.full((E, ed), float("nan"), device=dev) if want_ge else None
-            grads, named = [], {}
-            for t in range(T):
-                gt = (torch.empty(Fi, 2 * Fi + ed, device=dev), torch.empty(Fi, device=dev), torch.empty(Fo, (1 + 4 * S) * Fi, device=dev),
-                      torch.empty(Fo, device=dev), torch.empty(Fo, device=dev), torch.empty(Fo, device=dev))
-                for x in gt:
-                    x.fill_(float("nan"))
-                grads.append(gt)
-                pre, post, bn = f"towers.{t}.pretrans.fully_connected.0.linear.", f"towers.{t}.posttrans.fully_connected.0.linear.", f"towers.{t}.batchnorm_h."
-                named.update({pre + "weight": gt[0], pre + "bias": gt[1], post + "weight": gt[2], post + "bias": gt[3], bn + "weight": gt[4], bn + "bias": gt[5]})
-            gmw, gmb = torch.empty(Cc, Cc, device=dev), torch.empty(Cc, device=dev)
-            named.update({"mixing_network.linear.weight": gmw, "mixing_network.linear.bias": gmb})
-            plan.ws.fill_(float("nan"))                         # (the backward reads nothing the forward left there)
-            plan.set_backward(args, go, gh, grads, gmw, gmb)
-            qb = plan.edge_args(args, e, saved, grad_e=ge, backward=True)
-            self.args, self.q, self.keep = args, qb, (towers, grads, go, ge)
-            _lib.check(_lib.lib().pna_tower_edge_train_bwd_f32(ctypes.byref(qb), _lib.stream_ptr(dev)), "bwd")
-            torch.cuda.synchronize(dev)
-            self.out, self.gh, self.ge, self.grads, self.running = out, gh, ge, named, running
-            self.x_cat, self.a, self.z, self.p, self.stats, self.amx, self.amn = plan.views(saved)
-            self.x_edge = plan.x_edge(saved)
-            self.history.append([t.clone() for t in [out, self.x_cat, self.x_edge, self.a, self.z, self.p, self.stats, self.amx, self.amn, gh]
-                                 + ([ge] if want_ge else []) + list(named.values()) + list(running.values())])
+def _Run(name, dev, **options):
+    return Run(name, C.case(name), dev, want_grad_e=name != "e_no_grad", **options)
 
 
 _runs = {}
