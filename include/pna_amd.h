@@ -592,7 +592,8 @@ int pna_fused_simple_f32(const pna_fused_simple_args* args, pna_stream_t stream)
  *   tile_desc     [M / 16][4] = {first record, in-degree D, weight image, 0} of every 16-row block;
  *   tile_ids      n_records records of 16 int32: record (first + e)[i] = source row (row of x) of the e-th in-edge of the block's
  *                 i-th row, e in [0, D), in the row's edge order; a padding row repeats the block's first row; a block owns
- *                 max(4, round_up(D, 4)) records, the ones past D being copies of record D - 1 (D = 0: any valid row);
+ *                 max(4, round_up(D, 4)) records, the ones past D being copies of record D - 1 (D = 0: any valid row) -- they
+ *                 feed the id prefetch and never the sums; for D > 4 their rows are not requested (the block's first row aside);
  *                 D is ANY in-degree >= 0 -- the degrees of a tile's four (eight) blocks may all differ, and nothing ties D to the
  *                 caller's hub threshold: the only limit is n_records < 2^26 (tests/test_gpu_fused_degree_plans.py pins D = 0 .. 9,
  *                 12, 13, 16, 17, 31 .. 33, 127 .. 129 and 300, one degree per tile and four per tile);

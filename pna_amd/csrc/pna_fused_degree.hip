@@ -144,6 +144,48 @@ __device__ __forceinline__ void ld4(int& dst, const void* base, unsigned voff) {
 __device__ __forceinline__ void ld4f(float& dst, const void* base, unsigned voff) {
   asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory");
 }
+// The NL row loads of one edge packet as ONE statement that narrows the execution mask to lane 0 when the ring slot has no edge
+// left in the tile (`rem` = edges of the tile from the group being requested on, wavefront-uniform; slot J is padding iff rem <= J).
+// A padding packet then asks the memory system for one lane's 16 bytes per load instead of 64 lanes' -- the id behind it is a
+// valid row (a repeat of the tile's last edge) --, the other lanes keep the slot's previous, already folded edge ("+v"), and the
+// statement still issues exactly NL vector memory instructions: every counted wait stays what it was and there is no branch.
+// The mask is set and restored INSIDE the statement (the addresses are formed in front of it under the full mask; hipcc never sees
+// the narrowed one).  Load l reads A + PO + 128 (l / 2) + 16 (l % 2) for l < NA, L + 16 (l - NA) behind.
+#define FD_PK_HEAD "s_mov_b64 %[sv], exec\n\ts_cmp_le_i32 %[rem], %[j]\n\ts_cselect_b64 exec, 1, exec\n\t"
+#define FD_PK_LD(l) "global_load_dwordx4 %[d" #l "], %[a" #l "], off offset:%[o" #l "]\n\t"
+#define FD_PK_TAIL "s_mov_b64 exec, %[sv]"
+#define FD_PK_OUT(l) [d##l] "+v"(s[l])
+#define FD_PK_IN(l) [a##l] "v"(l < NA ? pa : pl), [o##l] "n"(l < NA ? PO + (l >> 1) * 128 + (l & 1) * 16 : (l - NA) * 16)
+#define FD_PK_REST [rem] "s"(rem), [j] "n"(J) : "memory", "scc"
+template <int J, int NA, int PO, int NL>
+__device__ __forceinline__ void ld_packet_masked(f4 (&s)[NL], const char* pa, const char* pl, int rem) {
+  static_assert(NL >= 2 && NL <= 6 && NA >= 0 && NA <= NL && J >= 1 && J <= 3, "2..6 row loads per edge; ring slots 1..3 can be padding");
+  unsigned long long sv;
+  if constexpr (NL == 2)
+    asm volatile(FD_PK_HEAD FD_PK_LD(0) FD_PK_LD(1) FD_PK_TAIL
+                 : FD_PK_OUT(0), FD_PK_OUT(1), [sv] "=&s"(sv) : FD_PK_IN(0), FD_PK_IN(1), FD_PK_REST);
+  else if constexpr (NL == 3)
+    asm volatile(FD_PK_HEAD FD_PK_LD(0) FD_PK_LD(1) FD_PK_LD(2) FD_PK_TAIL
+                 : FD_PK_OUT(0), FD_PK_OUT(1), FD_PK_OUT(2), [sv] "=&s"(sv) : FD_PK_IN(0), FD_PK_IN(1), FD_PK_IN(2), FD_PK_REST);
+  else if constexpr (NL == 4)
+    asm volatile(FD_PK_HEAD FD_PK_LD(0) FD_PK_LD(1) FD_PK_LD(2) FD_PK_LD(3) FD_PK_TAIL
+                 : FD_PK_OUT(0), FD_PK_OUT(1), FD_PK_OUT(2), FD_PK_OUT(3), [sv] "=&s"(sv)
+                 : FD_PK_IN(0), FD_PK_IN(1), FD_PK_IN(2), FD_PK_IN(3), FD_PK_REST);
+  else if constexpr (NL == 5)
+    asm volatile(FD_PK_HEAD FD_PK_LD(0) FD_PK_LD(1) FD_PK_LD(2) FD_PK_LD(3) FD_PK_LD(4) FD_PK_TAIL
+                 : FD_PK_OUT(0), FD_PK_OUT(1), FD_PK_OUT(2), FD_PK_OUT(3), FD_PK_OUT(4), [sv] "=&s"(sv)
+                 : FD_PK_IN(0), FD_PK_IN(1), FD_PK_IN(2), FD_PK_IN(3), FD_PK_IN(4), FD_PK_REST);
+  else
+    asm volatile(FD_PK_HEAD FD_PK_LD(0) FD_PK_LD(1) FD_PK_LD(2) FD_PK_LD(3) FD_PK_LD(4) FD_PK_LD(5) FD_PK_TAIL
+                 : FD_PK_OUT(0), FD_PK_OUT(1), FD_PK_OUT(2), FD_PK_OUT(3), FD_PK_OUT(4), FD_PK_OUT(5), [sv] "=&s"(sv)
+                 : FD_PK_IN(0), FD_PK_IN(1), FD_PK_IN(2), FD_PK_IN(3), FD_PK_IN(4), FD_PK_IN(5), FD_PK_REST);
+}
+#undef FD_PK_HEAD
+#undef FD_PK_LD
+#undef FD_PK_TAIL
+#undef FD_PK_OUT
+#undef FD_PK_IN
+#undef FD_PK_REST
 // The same loads behind five wait states.  "VALU writes SGPR -> VMEM reads that SGPR" needs them on gfx9 / CDNA; hipcc inserts the
 // s_nop for its own memory instructions but does not look inside inline asm, and under SGPR pressure it reloads a spilled base
 // pointer with v_readlane_b32 directly in front of the statement: the load then goes out with the stale base (the two-full-block
@@ -420,26 +462,34 @@ __device__ __forceinline__ void fd_body(const FDArgs& g, const int t_first, cons
 #pragma unroll
       for (int j = 0; j < 8; ++j) { S_[fb][j] = 0.f; Q_[fb][j] = 0.f; MX[fb][j] = -INFINITY; MN[fb][j] = INFINITY; }
     const int ng = max((D + 3) >> 2, 1);                  // groups of 4 edges; the plan pads the tile's records to 4 ng (repeats of the
-                                                          // last edge: idempotent for max / min, masked out of the sums; a tile without
-                                                          // in-edges has 4 records of row 0, all masked)
+                                                          // last edge: idempotent for max / min, masked out of the sums -- and, in a tile
+                                                          // of two groups or more, requested for lane 0 only; a tile without in-edges
+                                                          // has 4 records of row 0, all masked)
     f4 sl[kRing][NL];
     // rows of the edge whose id sits in idr[j] -> ring slot j, then the id slot j gathers next (record at byte `nrec`) -> idr[j]
-    auto issue = [&](auto jc, unsigned nrec) __attribute__((always_inline)) {
+    // (MASK, ring slots 1..3 inside the steady state: `rem` = the tile's edges from the requested group on, and a slot with no
+    //  edge left requests lane 0's strips only -- ld_packet_masked)
+    auto issue = [&](auto jc, unsigned nrec, auto mc, int rem) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
+      constexpr bool MASK = decltype(mc)::value;
       constexpr bool LASTP = P == GP - 1;                 // the pass that holds the row's last block
       constexpr int NFA = LASTP ? NB - 1 : NB;             // blocks addressed through A (never past F)
       constexpr int PO = P * NFBF * 128;                    // byte offset of the pass's features inside a row
+      static_assert(NFA <= 2 && 2 * NFA + (LASTP ? (HALF ? 1 : 2) : 0) == NL, "blocks addressed through A; the packet's loads");
       const size_t ro = FD_ABL(8) ? (size_t)0 : (size_t)(unsigned)idr[j] * ldb;   // (experiments, bit 8: every packet reads row 0)
-      if constexpr (NFA > 0) {
-        const char* const pa = xA + ro;
-        ldx16<PO>(sl[j][0], pa); ldx16<PO + 16>(sl[j][1], pa);
-        if constexpr (NFA > 1) { ldx16<PO + 128>(sl[j][NFA > 1 ? 2 : 0], pa); ldx16<PO + 144>(sl[j][NFA > 1 ? 3 : 0], pa); }
-        static_assert(NFA <= 2, "blocks addressed through A");
-      }
-      if constexpr (LASTP) {
-        const char* const pl = xL + ro;
-        ldx16<0>(sl[j][2 * (NB - 1)], pl);
-        if constexpr (!HALF) ldx16<16>(sl[j][HALF ? 0 : 2 * (NB - 1) + 1], pl);
+      if constexpr (MASK) {
+        ld_packet_masked<j, 2 * NFA, PO>(sl[j], xA + ro, xL + ro, rem);
+      } else {
+        if constexpr (NFA > 0) {
+          const char* const pa = xA + ro;
+          ldx16<PO>(sl[j][0], pa); ldx16<PO + 16>(sl[j][1], pa);
+          if constexpr (NFA > 1) { ldx16<PO + 128>(sl[j][NFA > 1 ? 2 : 0], pa); ldx16<PO + 144>(sl[j][NFA > 1 ? 3 : 0], pa); }
+        }
+        if constexpr (LASTP) {
+          const char* const pl = xL + ro;
+          ldx16<0>(sl[j][2 * (NB - 1)], pl);
+          if constexpr (!HALF) ldx16<16>(sl[j][HALF ? 0 : 2 * (NB - 1) + 1], pl);
+        }
       }
       ld4_ws(idr[j], g.ids, nrec + (unsigned)j * 64u + lib);      // (_ws: under SGPR pressure the base of the ids is reloaded right in front)
     };
@@ -458,17 +508,24 @@ __device__ __forceinline__ void fd_body(const FDArgs& g, const int t_first, cons
     using J2 = std::integral_constant<int, 2>; using J3 = std::integral_constant<int, 3>;
     // the packets of edges 0..3; each refills its id with the next group's, or -- after the last group -- the NEXT tile's edge j
     const unsigned n0 = 1 < ng ? rb + 4u * 64u : rbn;
-    issue(J0{}, n0); issue(J1{}, n0); issue(J2{}, n0); issue(J3{}, n0);
+    using Plain = std::false_type; using Masked = std::true_type;
+    issue(J0{}, n0, Plain{}, 0); issue(J1{}, n0, Plain{}, 0); issue(J2{}, n0, Plain{}, 0); issue(J3{}, n0, Plain{}, 0);
     if constexpr (P == 0) sld16(td_n2, g.tdesc, desc_off(t_n2));        // (the descriptor after next: its latency sits behind the packets just issued)
-    // steady state: slot j holds edge 4 gi + j; behind it in flight: the three younger packets.  Every edge here is a real one.
+    // steady state: slot j holds edge 4 gi + j, a real one; behind it in flight: the three younger packets.  The packets requested
+    // here are real ones too -- except, in the LAST round, those of the slots past D - 4 (ng - 1): the records there repeat edge
+    // D - 1, and such a slot requests nothing but lane 0 (rem <= j; slot 0 always has an edge left).  The drain folds it all the
+    // same: its lanes hold an edge that has been folded before -- lane 0: edge D - 1, the others: the slot's edge of this round --,
+    // which max / min do not see a second time and the sums take as zero.
     for (int gi = 0; gi + 1 < ng; ++gi) {
       const unsigned nr = gi + 2 < ng ? rb + (unsigned)(4 * gi + 8) * 64u : rbn;
-      wait_slot<3 * LB, NL>(sl[0], idr[0]); fold(J0{}, true); issue(J0{}, nr);
-      wait_slot<3 * LB, NL>(sl[1], idr[1]); fold(J1{}, true); issue(J1{}, nr);
-      wait_slot<3 * LB, NL>(sl[2], idr[2]); fold(J2{}, true); issue(J2{}, nr);
-      wait_slot<3 * LB, NL>(sl[3], idr[3]); fold(J3{}, true); issue(J3{}, nr);
+      const int rem = D - (4 * gi + 4);
+      wait_slot<3 * LB, NL>(sl[0], idr[0]); fold(J0{}, true); issue(J0{}, nr, Plain{}, 0);
+      wait_slot<3 * LB, NL>(sl[1], idr[1]); fold(J1{}, true); issue(J1{}, nr, Masked{}, rem);
+      wait_slot<3 * LB, NL>(sl[2], idr[2]); fold(J2{}, true); issue(J2{}, nr, Masked{}, rem);
+      wait_slot<3 * LB, NL>(sl[3], idr[3]); fold(J3{}, true); issue(J3{}, nr, Masked{}, rem);
     }
-    // drain: the last group (its slots past D hold copies of edge D - 1).  The residual rows of the tile are requested behind
+    // drain: the last group (its slots past D hold edges folded before: copies of edge D - 1 in a tile of one group; from two groups
+    // on lane 0 alone holds that copy, the other lanes the slot's edge of the round before).  The residual rows of the tile are requested behind
     // slot 0 -- perm (requested before every packet) has landed by then -- and stay in flight into the multiply phase.
     const int e0 = 4 * (ng - 1);
     wait_slot<3 * LB, NL>(sl[0], idr[0]);
