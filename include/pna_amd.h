@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_drop_train_fwd_f32 / pna_tower_drop_train_bwd_f32 / pna_tower_drop_args, pna_dropout_mask_f32
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_gru_cell_in_scope, pna_tower_layer_lds_bytes, pna_tower_layer_bf16_lds_bytes (host-only queries: the
+                                  scope and tile checks of pna_gru_cell_*_f32, pna_tower_layer_f32 and pna_tower_layer_bf16, so that a binding asks
+                                  the library where it would otherwise copy a bound); no existing struct or entry point changed.
+                                  23, additive: + pna_tower_drop_train_fwd_f32 / pna_tower_drop_train_bwd_f32 / pna_tower_drop_args, pna_dropout_mask_f32
                                   (the one-call tower training routes, with and without edge features, with the towers' dropout between
                                   their BatchNorm and the mixing Linear: a Philox4x32-10 mask regenerated in the backward from a 128-bit
                                   key); no existing struct or entry point changed.
@@ -814,6 +817,10 @@ typedef struct pna_tower_layer_args {
 } pna_tower_layer_args;
 
 int pna_tower_layer_f32(const pna_tower_layer_args* args, pna_stream_t stream);
+/* Host only.  LDS bytes of pna_tower_layer_f32's tile with ONE tower per pass, the smallest it can run with, by the entry point's own
+ * code (it refuses a layer whose smallest tile exceeds 160 KiB); No = the mixing network's output width, 0 without one.  -1 when n_tower,
+ * Fi or Fo is below 1 or No is negative. */
+int64_t pna_tower_layer_lds_bytes(int32_t n_tower, int32_t Fi, int32_t Fo, int32_t No, int32_t divide_input);
 
 /* ---- weight / bias gradient of the posttrans contraction (round 4) ------------------------------------------
  * replaces: the autograd node of `self.posttrans(torch.cat([h, scaled aggregate], dim=1))` (models/dgl/pna_layer.py:206; the
@@ -1261,6 +1268,10 @@ typedef struct pna_tower_layer_bf16_args {
 } pna_tower_layer_bf16_args;
 
 int pna_tower_layer_bf16(const pna_tower_layer_bf16_args* args, pna_stream_t stream);
+/* Host only.  LDS bytes of pna_tower_layer_bf16's 16-row tile, by the entry point's own code (it refuses more than 160 KiB); No = 0: no
+ * mixing image.  -1 when n_tower, Fi, Fo or n_aggr is below 1 or No is negative. */
+int64_t pna_tower_layer_bf16_lds_bytes(int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_aggr, int32_t divide_input, int32_t No,
+                                       int32_t no_self_panel);
 
 /* ---- the per-edge MLP of a deep pre_nn on bf16 messages (ABI 23, additive) --------------------------------------------------------
  *
@@ -1786,6 +1797,8 @@ typedef struct pna_gru_cell_args {
 } pna_gru_cell_args;
 
 int64_t pna_gru_cell_workspace_bytes(int64_t V, int32_t I, int32_t Hc, int32_t hidden_size);   /* -1 outside the scope */
+/* Host only.  1 when the shapes are inside the scope above (the entry points' own check, input_size included), else 0. */
+int32_t pna_gru_cell_in_scope(int64_t V, int32_t I, int32_t Hc, int32_t input_size, int32_t hidden_size);
 int pna_gru_cell_fwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
 int pna_gru_cell_bwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
 

@@ -569,6 +569,8 @@ def lib():
         L.pna_tower_post_pack_f32.restype = ctypes.c_int
         L.pna_tower_layer_f32.argtypes = [ctypes.POINTER(PnaTowerLayerArgs), ctypes.c_void_p]
         L.pna_tower_layer_f32.restype = ctypes.c_int
+        L.pna_tower_layer_lds_bytes.argtypes = [ctypes.c_int32] * 5
+        L.pna_tower_layer_lds_bytes.restype = ctypes.c_int64
         L.pna_segreduce_fwd_bf16.argtypes = [ctypes.POINTER(PnaSegreduceBf16Args), ctypes.c_void_p]
         L.pna_segreduce_fwd_bf16.restype = ctypes.c_int
         L.pna_segreduce_bf16_partials_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
@@ -585,6 +587,8 @@ def lib():
         L.pna_contract_bf16_tiles.restype = ctypes.c_int
         L.pna_tower_layer_bf16.argtypes = [ctypes.POINTER(PnaTowerLayerBf16Args), ctypes.c_void_p]
         L.pna_tower_layer_bf16.restype = ctypes.c_int
+        L.pna_tower_layer_bf16_lds_bytes.argtypes = [ctypes.c_int32] * 7
+        L.pna_tower_layer_bf16_lds_bytes.restype = ctypes.c_int64
         L.pna_edge_mlp_bf16.argtypes = [ctypes.POINTER(PnaEdgeMlpBf16Args), ctypes.c_void_p]
         L.pna_edge_mlp_bf16.restype = ctypes.c_int
         L.pna_edge_mlp_bf16_lds_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
@@ -625,6 +629,8 @@ def lib():
             fn.restype = ctypes.c_int
         L.pna_gru_cell_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
         L.pna_gru_cell_workspace_bytes.restype = ctypes.c_int64
+        L.pna_gru_cell_in_scope.argtypes = [ctypes.c_int64] + [ctypes.c_int32] * 4
+        L.pna_gru_cell_in_scope.restype = ctypes.c_int32
         for fn in (L.pna_gru_cell_fwd_f32, L.pna_gru_cell_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaGruCellArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int

@@ -1171,10 +1171,7 @@ class EmbedSumFn(torch.autograd.Function):
             grads.append(flat[at:at + r * F].view(r, F))
             a.grad_table[j] = flat.data_ptr() + 4 * at
             at += r * F
-        # pna_embed_sum_workspace_bytes' formula (tests/test_net_ends_host.py holds the two together): one image of all tables per slab
-        V = idx.shape[0]
-        slab = max(_lib.PNA_EMBED_SLAB_ROWS, -(-V // _lib.PNA_EMBED_MAX_SLABS))
-        nbytes = -(-V // slab) * sum(rows) * ((F + 3) // 4 * 4) * 4
+        nbytes = _lib.lib().pna_embed_sum_workspace_bytes(a.V, a.n_table, a.rows, a.F)
         a.workspace, a.workspace_bytes = _device_workspace(_embed_ws, dev, nbytes)[1], nbytes
         a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
         _lib.check(_lib.lib().pna_embed_sum_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_embed_sum_bwd_f32")
@@ -1304,9 +1301,7 @@ class GruCellFn(torch.autograd.Function):
         a.grad_w_ih, a.grad_w_hh = _lib.dev_ptr(gwi, torch.float32, "grad_w_ih"), _lib.dev_ptr(gwh, torch.float32, "grad_w_hh")
         a.grad_b_ih, a.grad_b_hh = _lib.dev_ptr(gbi, torch.float32, "grad_b_ih"), _lib.dev_ptr(gbh, torch.float32, "grad_b_hh")
         a.need_x, a.need_h, a.need_w_ih, a.need_w_hh, a.need_b_ih, a.need_b_hh = [int(bool(n)) for n in need[:6]]
-        # pna_gru_cell_workspace_bytes' formula (tests/test_gru_host.py holds the two together)
-        slab = max(_lib.PNA_GRU_SLAB_ROWS, -(-V // _lib.PNA_GRU_MAX_SLABS))
-        nbytes = 4 * (V * 4 * H + -(-V // slab) * 3 * H * (I + Hc + 2))
+        nbytes = _lib.lib().pna_gru_cell_workspace_bytes(V, I, Hc, H)
         a.workspace, a.workspace_bytes = _device_workspace(_gru_ws, dev, nbytes)[1], nbytes
         _lib.check(_lib.lib().pna_gru_cell_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_gru_cell_bwd_f32")
         return gx, gh, gwi, gwh, gbi, gbh, None

@@ -195,7 +195,25 @@ hipError_t launch_rows_v(const RArgs& g, bool v8, size_t lds, hipStream_t st) {
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// Row pitches (bf16 elements) of the three panels of a 16-row tile: the aggregates of every tower, the rows' own features (n_hblk
+// blocks: none, one, or one per tower) and, with a mixing network, the concatenated tower outputs.
+struct Tile {
+  int LA, LH, LC;
+  size_t bytes() const { return (size_t)kRows * ((size_t)LA + LH + LC) * sizeof(u16); }
+};
+
+Tile tile_of(int T, int Fi, int Fo, int A, int n_hblk, bool mix) {
+  const int Kp = round_up(A * round_up(Fi, 8), 32);
+  return {T * Kp + kLdsPad, n_hblk ? n_hblk * round_up(Fi, 32) + kLdsPad : 0, mix ? round_up(T * Fo, 32) + kLdsPad : 0};
+}
+
 }  // namespace
+
+extern "C" int64_t pna_tower_layer_bf16_lds_bytes(int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_aggr, int32_t divide_input, int32_t No,
+                                                  int32_t no_self_panel) {
+  if (n_tower < 1 || Fi < 1 || Fo < 1 || n_aggr < 1 || No < 0) return -1;
+  return (int64_t)tile_of(n_tower, Fi, Fo, n_aggr, no_self_panel ? 0 : divide_input ? n_tower : 1, No > 0).bytes();
+}
 
 extern "C" int pna_tower_layer_bf16(const pna_tower_layer_bf16_args* p, pna_stream_t stream) {
   if (!p) return pna_set_error(PNA_E_INVALID, "pna_tower_layer_bf16: null args");
@@ -216,11 +234,10 @@ extern "C" int pna_tower_layer_bf16(const pna_tower_layer_bf16_args* p, pna_stre
   const int n_hblk = simple ? 0 : p->divide_input ? T : 1;
   const int Kin = p->divide_input ? T * Fi : Fi, width = p->mix_img ? p->No : T * Fo;
   const int Kmp = p->mix_img ? round_up(T * Fo, 32) : 0;
+  const Tile tile = tile_of(T, Fi, Fo, A, n_hblk, p->mix_img != nullptr);
   RArgs g{};
-  g.LA = T * Kp + kLdsPad;
-  g.LH = n_hblk ? n_hblk * Khp + kLdsPad : 0;
-  g.LC = p->mix_img ? Kmp + kLdsPad : 0;
-  const size_t lds = (size_t)kRows * ((size_t)g.LA + g.LH + g.LC) * sizeof(u16);
+  g.LA = tile.LA; g.LH = tile.LH; g.LC = tile.LC;
+  const size_t lds = tile.bytes();
   if (lds > kLdsMax) return pna_set_error(PNA_E_INVALID, "pna_tower_layer_bf16: the 16-row tile does not fit 160 KiB of LDS");
   if (p->V == 0) return PNA_OK;
   if (!p->rowptr || !p->col || !p->h || !p->post_img || !p->y)

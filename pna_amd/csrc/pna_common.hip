@@ -1,4 +1,5 @@
-// pna_common.hip -- error reporting and version query of the C ABI (include/pna_amd.h).
+// pna_common.hip -- error reporting and version query of the C ABI (include/pna_amd.h), and the entry points' shared host helpers.
+#include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -18,6 +19,18 @@ int pna_check_struct_size(const char* fn, unsigned got, unsigned long need) {
   char msg[256];
   snprintf(msg, sizeof(msg), "%s: args.struct_size = %u, this library's struct has %lu bytes (a binding built against an older include/pna_amd.h, or struct_size not set)", fn, got, need);
   return pna_set_error(PNA_E_INVALID, msg);
+}
+
+int pna_refuse(const char* fn, const char* clause) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", fn, clause);
+  return pna_set_error(PNA_E_INVALID, msg);
+}
+
+int pna_raise_lds(const void* kernel, unsigned long bytes, const char* who) {
+  if (bytes > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return pna_set_error(PNA_E_LAUNCH, who);
+  return PNA_OK;
 }
 
 extern "C" const char* pna_last_error(void) { return g_err; }

@@ -482,43 +482,37 @@ const char* scope_clause(int64_t B, int N, int T, int Fi, int Fo, int A, int S) 
   return nullptr;
 }
 
-int refuse(const char* fn, const char* clause) {
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", fn, clause);
-  return pna_set_error(PNA_E_INVALID, msg);
-}
-
 int fill(const pna_dense_layer_args* p, DArgs& g, bool bwd, const char* fn) {
-  if (!p) return refuse(fn, "args is NULL");
+  if (!p) return pna_refuse(fn, "args is NULL");
   if (int rc_ss = pna_check_struct_size(fn, p->struct_size, sizeof(*p))) return rc_ss;
   if (p->n_aggr < 0 || p->n_aggr > PNA_MAX_AGGR || p->n_scaler < 0 || p->n_scaler > PNA_MAX_SCALER)
-    return refuse(fn, "needs 1 to 4 distinct aggregators and 1 to 3 distinct scalers");
-  if (const char* c = scope_clause(p->B, p->N, p->n_tower, p->Fi, p->Fo, p->n_aggr, p->n_scaler)) return refuse(fn, c);
+    return pna_refuse(fn, "needs 1 to 4 distinct aggregators and 1 to 3 distinct scalers");
+  if (const char* c = scope_clause(p->B, p->N, p->n_tower, p->Fi, p->Fo, p->n_aggr, p->n_scaler)) return pna_refuse(fn, c);
   memset(&g, 0, sizeof(g));
   g.ia_mean = g.ia_max = g.ia_min = g.ia_std = -1;
   for (int a = 0; a < p->n_aggr; ++a) {
     int* slot = p->aggr[a] == PNA_AGG_MEAN ? &g.ia_mean : p->aggr[a] == PNA_AGG_MAX ? &g.ia_max : p->aggr[a] == PNA_AGG_MIN ? &g.ia_min
               : p->aggr[a] == PNA_AGG_STD ? &g.ia_std : nullptr;
-    if (!slot || *slot >= 0) return refuse(fn, "needs 1 to 4 distinct aggregators out of mean, max, min, std");
+    if (!slot || *slot >= 0) return pna_refuse(fn, "needs 1 to 4 distinct aggregators out of mean, max, min, std");
     *slot = a;
   }
   bool need_log = false, need_lin = false;
   for (int s = 0; s < p->n_scaler; ++s) {
     const int code = p->scaler[s];
-    if (code < PNA_DENSE_SCALER_IDENTITY || code > PNA_DENSE_SCALER_INVERSE_LINEAR) return refuse(fn, "unknown scaler code");
+    if (code < PNA_DENSE_SCALER_IDENTITY || code > PNA_DENSE_SCALER_INVERSE_LINEAR) return pna_refuse(fn, "unknown scaler code");
     for (int r = 0; r < s; ++r)
-      if (p->scaler[r] == code) return refuse(fn, "needs 1 to 3 distinct scalers");
+      if (p->scaler[r] == code) return pna_refuse(fn, "needs 1 to 3 distinct scalers");
     need_log |= code == PNA_DENSE_SCALER_AMPLIFICATION || code == PNA_DENSE_SCALER_ATTENUATION;
     need_lin |= code == PNA_DENSE_SCALER_LINEAR || code == PNA_DENSE_SCALER_INVERSE_LINEAR;
     g.scaler[s] = code;
   }
   const int T = p->n_tower, Fi = p->Fi;
-  if (p->in_dim != (p->divide_input ? T * Fi : Fi)) return refuse(fn, "in_dim must be n_tower Fi (divide_input) or Fi");
-  if (!p->x || !p->adj) return refuse(fn, "needs x (B, N, in_dim) and adj (B, N, N)");
-  if ((need_log && !p->avg_log) || (need_lin && !p->avg_lin)) return refuse(fn, "the scalers need avg_log / avg_lin (one device float each)");
+  if (p->in_dim != (p->divide_input ? T * Fi : Fi)) return pna_refuse(fn, "in_dim must be n_tower Fi (divide_input) or Fi");
+  if (!p->x || !p->adj) return pna_refuse(fn, "needs x (B, N, in_dim) and adj (B, N, N)");
+  if ((need_log && !p->avg_log) || (need_lin && !p->avg_lin)) return pna_refuse(fn, "the scalers need avg_log / avg_lin (one device float each)");
   for (int t = 0; t < T; ++t)
-    if (!p->w_pre[t] || !p->b_pre[t] || !p->w_post[t] || !p->b_post[t]) return refuse(fn, "needs w_pre, b_pre, w_post, b_post of every tower");
-  if (!p->w_mix || !p->b_mix) return refuse(fn, "needs w_mix and b_mix");
+    if (!p->w_pre[t] || !p->b_pre[t] || !p->w_post[t] || !p->b_post[t]) return pna_refuse(fn, "needs w_pre, b_pre, w_post, b_post of every tower");
+  if (!p->w_mix || !p->b_mix) return pna_refuse(fn, "needs w_mix and b_mix");
   g.B = p->B; g.N = p->N; g.IN = p->in_dim; g.T = T; g.Fi = Fi; g.Fo = p->Fo; g.divide = p->divide_input != 0; g.self_loop = p->self_loop != 0;
   g.A = p->n_aggr; g.S = p->n_scaler; g.slope = p->slope;
   g.x = p->x; g.adj = p->adj; g.avg_log = p->avg_log; g.avg_lin = p->avg_lin; g.w_mix = p->w_mix; g.b_mix = p->b_mix;
@@ -526,25 +520,19 @@ int fill(const pna_dense_layer_args* p, DArgs& g, bool bwd, const char* fn) {
   g.slab = slab_graphs(g.B);
   g.n_slab = (int)((g.B + g.slab - 1) / g.slab);
   if (!bwd) {
-    if (!p->out) return refuse(fn, "needs out (B, N, n_tower Fo)");
+    if (!p->out) return pna_refuse(fn, "needs out (B, N, n_tower Fo)");
     g.out = p->out;
     return PNA_OK;
   }
-  if (!p->grad_out) return refuse(fn, "needs grad_out (B, N, n_tower Fo)");
+  if (!p->grad_out) return pna_refuse(fn, "needs grad_out (B, N, n_tower Fo)");
   const int64_t need = pna_dense_layer_workspace_bytes(p->B, p->N, T, Fi, p->Fo, p->n_aggr, p->n_scaler);
   if (!p->workspace || ((uintptr_t)p->workspace & 15) || p->workspace_bytes < need)
-    return refuse(fn, "needs a 16-byte aligned workspace of pna_dense_layer_workspace_bytes(...)");
+    return pna_refuse(fn, "needs a 16-byte aligned workspace of pna_dense_layer_workspace_bytes(...)");
   g.go = p->grad_out; g.gx = p->grad_x; g.g_w_mix = p->grad_w_mix; g.g_b_mix = p->grad_b_mix;
   for (int t = 0; t < T; ++t) {
     g.g_w_pre[t] = p->grad_w_pre[t]; g.g_b_pre[t] = p->grad_b_pre[t]; g.g_w_post[t] = p->grad_w_post[t]; g.g_b_post[t] = p->grad_b_post[t];
   }
   g.part = (float*)p->workspace;
-  return PNA_OK;
-}
-
-int raise_lds(const void* fn, size_t lds, const char* who) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return pna_set_error(PNA_E_LAUNCH, who);
   return PNA_OK;
 }
 
@@ -568,7 +556,7 @@ extern "C" int pna_dense_layer_fwd_f32(const pna_dense_layer_args* p, pna_stream
   const int rc = fill(p, g, false, "pna_dense_layer_fwd_f32");
   if (rc != PNA_OK) return rc;
   const size_t lds = (size_t)layout(g.N, g.T, g.Fi, g.Fo, g.A, g.S).bytes;
-  if (raise_lds((const void*)k_dense_layer_fwd, lds, "pna_dense_layer_fwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
+  if (pna_raise_lds((const void*)k_dense_layer_fwd, lds, "pna_dense_layer_fwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
   hipLaunchKernelGGL(k_dense_layer_fwd, dim3((unsigned)g.n_slab), dim3(kThreads), lds, (hipStream_t)stream, g);
   if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_dense_layer_fwd_f32: launch failed");
   return PNA_OK;
@@ -582,7 +570,7 @@ extern "C" int pna_dense_layer_bwd_f32(const pna_dense_layer_args* p, pna_stream
   for (int t = 0; t < g.T; ++t) params = params || g.g_w_pre[t] || g.g_b_pre[t] || g.g_w_post[t] || g.g_b_post[t];
   if (!g.gx && !params) return PNA_OK;
   const size_t lds = (size_t)layout(g.N, g.T, g.Fi, g.Fo, g.A, g.S).bytes;
-  if (raise_lds((const void*)k_dense_layer_bwd, lds, "pna_dense_layer_bwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
+  if (pna_raise_lds((const void*)k_dense_layer_bwd, lds, "pna_dense_layer_bwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
   hipLaunchKernelGGL(k_dense_layer_bwd, dim3((unsigned)g.n_slab), dim3(kThreads), lds, (hipStream_t)stream, g);
   if (params) {
     const long n = image_floats(g.T, g.Fi, g.Fo, g.A, g.S);

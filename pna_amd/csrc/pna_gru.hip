@@ -336,42 +336,36 @@ const char* scope_clause(int64_t V, int I, int Hc, int IN, int H) {
   return nullptr;
 }
 
-int refuse(const char* fn, const char* clause) {
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", fn, clause);
-  return pna_set_error(PNA_E_INVALID, msg);
-}
-
 int fill(const pna_gru_cell_args* p, GArgs& g, bool bwd, const char* fn) {
-  if (!p) return refuse(fn, "args is NULL");
+  if (!p) return pna_refuse(fn, "args is NULL");
   if (int rc_ss = pna_check_struct_size(fn, p->struct_size, sizeof(*p))) return rc_ss;
-  if (p->dtype != PNA_GRU_F32) return refuse(fn, "fp32 only (dtype must be PNA_GRU_F32)");
-  if (const char* c = scope_clause(p->V, p->I, p->Hc, p->input_size, p->hidden_size)) return refuse(fn, c);
+  if (p->dtype != PNA_GRU_F32) return pna_refuse(fn, "fp32 only (dtype must be PNA_GRU_F32)");
+  if (const char* c = scope_clause(p->V, p->I, p->Hc, p->input_size, p->hidden_size)) return pna_refuse(fn, c);
   const int I = p->I, Hc = p->Hc, IN = p->input_size, H = p->hidden_size;
-  if (!p->x || p->ldx < I) return refuse(fn, "needs x (V, ldx >= I)");
-  if (!p->h || p->ldh < Hc) return refuse(fn, "needs h (V, ldh >= Hc)");
-  if (!p->w_ih || p->ld_wih < IN) return refuse(fn, "needs w_ih (3 hidden_size, ld_wih >= input_size)");
-  if (!p->w_hh || p->ld_whh < H) return refuse(fn, "needs w_hh (3 hidden_size, ld_whh >= hidden_size)");
+  if (!p->x || p->ldx < I) return pna_refuse(fn, "needs x (V, ldx >= I)");
+  if (!p->h || p->ldh < Hc) return pna_refuse(fn, "needs h (V, ldh >= Hc)");
+  if (!p->w_ih || p->ld_wih < IN) return pna_refuse(fn, "needs w_ih (3 hidden_size, ld_wih >= input_size)");
+  if (!p->w_hh || p->ld_whh < H) return pna_refuse(fn, "needs w_hh (3 hidden_size, ld_whh >= hidden_size)");
   memset(&g, 0, sizeof(g));
   g.V = p->V; g.I = I; g.Hc = Hc; g.IN = IN; g.H = H;
   g.x = p->x; g.ldx = (long)p->ldx; g.h = p->h; g.ldh = (long)p->ldh;
   g.wih = p->w_ih; g.ldwi = (long)p->ld_wih; g.whh = p->w_hh; g.ldwh = (long)p->ld_whh;
   g.saved = p->saved;
   if (!bwd) {
-    if (!p->b_ih || !p->b_hh) return refuse(fn, "needs b_ih and b_hh [3 hidden_size] (bias=True)");
-    if (!p->out || p->ld_out < H) return refuse(fn, "needs out (V, ld_out >= hidden_size)");
+    if (!p->b_ih || !p->b_hh) return pna_refuse(fn, "needs b_ih and b_hh [3 hidden_size] (bias=True)");
+    if (!p->out || p->ld_out < H) return pna_refuse(fn, "needs out (V, ld_out >= hidden_size)");
     g.bih = p->b_ih; g.bhh = p->b_hh; g.out = p->out; g.ldo = (long)p->ld_out;
     return PNA_OK;
   }
-  if (!p->saved) return refuse(fn, "needs the forward's saved state (4, V, hidden_size)");
-  if (!p->grad_out || p->ld_go < H) return refuse(fn, "needs grad_out (V, ld_go >= hidden_size)");
-  if (p->need_x && (!p->grad_x || p->ld_gx < I)) return refuse(fn, "need_x needs grad_x (V, ld_gx >= I)");
-  if (p->need_h && (!p->grad_h || p->ld_gh < Hc)) return refuse(fn, "need_h needs grad_h (V, ld_gh >= Hc)");
+  if (!p->saved) return pna_refuse(fn, "needs the forward's saved state (4, V, hidden_size)");
+  if (!p->grad_out || p->ld_go < H) return pna_refuse(fn, "needs grad_out (V, ld_go >= hidden_size)");
+  if (p->need_x && (!p->grad_x || p->ld_gx < I)) return pna_refuse(fn, "need_x needs grad_x (V, ld_gx >= I)");
+  if (p->need_h && (!p->grad_h || p->ld_gh < Hc)) return pna_refuse(fn, "need_h needs grad_h (V, ld_gh >= Hc)");
   if ((p->need_w_ih && !p->grad_w_ih) || (p->need_w_hh && !p->grad_w_hh) || (p->need_b_ih && !p->grad_b_ih) || (p->need_b_hh && !p->grad_b_hh))
-    return refuse(fn, "every need_w_* / need_b_* flag needs its gradient buffer");
+    return pna_refuse(fn, "every need_w_* / need_b_* flag needs its gradient buffer");
   const int64_t need = pna_gru_cell_workspace_bytes(p->V, I, Hc, H);
   if (!p->workspace || ((uintptr_t)p->workspace & 15) || p->workspace_bytes < need)
-    return refuse(fn, "needs a 16-byte aligned workspace of pna_gru_cell_workspace_bytes(V, I, Hc, hidden_size)");
+    return pna_refuse(fn, "needs a 16-byte aligned workspace of pna_gru_cell_workspace_bytes(V, I, Hc, hidden_size)");
   g.go = p->grad_out; g.ldgo = (long)p->ld_go;
   g.gx = p->grad_x; g.ldgx = (long)p->ld_gx; g.gh = p->grad_h; g.ldgh = (long)p->ld_gh;
   g.gwih = p->grad_w_ih; g.gwhh = p->grad_w_hh; g.gbih = p->grad_b_ih; g.gbhh = p->grad_b_hh;
@@ -385,6 +379,10 @@ int fill(const pna_gru_cell_args* p, GArgs& g, bool bwd, const char* fn) {
 }
 
 }  // namespace
+
+extern "C" int32_t pna_gru_cell_in_scope(int64_t V, int32_t I, int32_t Hc, int32_t input_size, int32_t hidden_size) {
+  return !scope_clause(V, I, Hc, input_size, hidden_size);
+}
 
 extern "C" int64_t pna_gru_cell_workspace_bytes(int64_t V, int32_t I, int32_t Hc, int32_t hidden_size) {
   if (scope_clause(V, I, Hc, kMaxWidth, hidden_size)) return -1;

@@ -377,45 +377,33 @@ const char* scope_clause(int64_t B, int N, int D, int steps) {
   return nullptr;
 }
 
-int refuse(const char* fn, const char* clause) {
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: %s", fn, clause);
-  return pna_set_error(PNA_E_INVALID, msg);
-}
-
 int fill(const pna_set2set_args* p, SArgs& g, bool bwd, const char* fn) {
-  if (!p) return refuse(fn, "args is NULL");
+  if (!p) return pna_refuse(fn, "args is NULL");
   if (int rc_ss = pna_check_struct_size(fn, p->struct_size, sizeof(*p))) return rc_ss;
-  if (p->dtype != PNA_S2S_F32) return refuse(fn, "fp32 only (dtype must be PNA_S2S_F32)");
-  if (const char* c = scope_clause(p->B, p->N, p->D, p->steps)) return refuse(fn, c);
-  if (!p->x) return refuse(fn, "needs x (B, N, D)");
-  if (!p->w_ih || !p->w_hh) return refuse(fn, "needs w_ih (4D, 2D) and w_hh (4D, D)");
-  if (!p->b_ih || !p->b_hh) return refuse(fn, "needs b_ih and b_hh [4D] (bias=True)");
+  if (p->dtype != PNA_S2S_F32) return pna_refuse(fn, "fp32 only (dtype must be PNA_S2S_F32)");
+  if (const char* c = scope_clause(p->B, p->N, p->D, p->steps)) return pna_refuse(fn, c);
+  if (!p->x) return pna_refuse(fn, "needs x (B, N, D)");
+  if (!p->w_ih || !p->w_hh) return pna_refuse(fn, "needs w_ih (4D, 2D) and w_hh (4D, D)");
+  if (!p->b_ih || !p->b_hh) return pna_refuse(fn, "needs b_ih and b_hh [4D] (bias=True)");
   memset(&g, 0, sizeof(g));
   g.B = p->B; g.N = p->N; g.D = p->D; g.T = p->steps;
   g.x = p->x; g.wih = p->w_ih; g.whh = p->w_hh; g.bih = p->b_ih; g.bhh = p->b_hh;
   g.slab = slab_graphs(g.B);
   g.n_slab = (int)((g.B + g.slab - 1) / g.slab);
   if (!bwd) {
-    if (!p->out) return refuse(fn, "needs out (B, 2D)");
+    if (!p->out) return pna_refuse(fn, "needs out (B, 2D)");
     g.out = p->out;
     return PNA_OK;
   }
-  if (!p->grad_out) return refuse(fn, "needs grad_out (B, 2D)");
+  if (!p->grad_out) return pna_refuse(fn, "needs grad_out (B, 2D)");
   const int64_t need = pna_set2set_workspace_bytes(p->B, p->N, p->D, p->steps);
   if (!p->workspace || ((uintptr_t)p->workspace & 15) || p->workspace_bytes < need)
-    return refuse(fn, "needs a 16-byte aligned workspace of pna_set2set_workspace_bytes(B, N, D, steps)");
+    return pna_refuse(fn, "needs a 16-byte aligned workspace of pna_set2set_workspace_bytes(B, N, D, steps)");
   g.go = p->grad_out; g.gx = p->grad_x;
   g.gwih = p->grad_w_ih; g.gwhh = p->grad_w_hh; g.gbih = p->grad_b_ih; g.gbhh = p->grad_b_hh;
   const long images = g.B < PNA_S2S_MAX_SLABS ? g.B : PNA_S2S_MAX_SLABS;
   g.part = (float*)p->workspace;
   g.rec = g.part + images * image_floats(g.D);
-  return PNA_OK;
-}
-
-int raise_lds(const void* fn, size_t lds, const char* who) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return pna_set_error(PNA_E_LAUNCH, who);
   return PNA_OK;
 }
 
@@ -437,7 +425,7 @@ extern "C" int pna_set2set_fwd_f32(const pna_set2set_args* p, pna_stream_t strea
   const int rc = fill(p, g, false, "pna_set2set_fwd_f32");
   if (rc != PNA_OK) return rc;
   const size_t lds = (size_t)round16(4L * layout(g.N, g.D).fwd_end);
-  if (raise_lds((const void*)k_set2set_fwd, lds, "pna_set2set_fwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
+  if (pna_raise_lds((const void*)k_set2set_fwd, lds, "pna_set2set_fwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
   hipLaunchKernelGGL(k_set2set_fwd, dim3((unsigned)g.n_slab), dim3(kThreads), lds, (hipStream_t)stream, g);
   if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_set2set_fwd_f32: launch failed");
   return PNA_OK;
@@ -450,7 +438,7 @@ extern "C" int pna_set2set_bwd_f32(const pna_set2set_args* p, pna_stream_t strea
   const bool params = g.gwih || g.gwhh || g.gbih || g.gbhh;
   if (!g.gx && !params) return PNA_OK;
   const size_t lds = (size_t)round16(4L * layout(g.N, g.D).end);
-  if (raise_lds((const void*)k_set2set_bwd, lds, "pna_set2set_bwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
+  if (pna_raise_lds((const void*)k_set2set_bwd, lds, "pna_set2set_bwd_f32: the LDS size was refused")) return PNA_E_LAUNCH;
   hipLaunchKernelGGL(k_set2set_bwd, dim3((unsigned)g.n_slab), dim3(kThreads), lds, (hipStream_t)stream, g);
   if (params) {
     const long n = image_floats(g.D);

@@ -578,6 +578,11 @@ extern "C" int pna_tower_post_pack_f32(const float* w_ref, int64_t ldw_ref, int3
   return PNA_OK;
 }
 
+extern "C" int64_t pna_tower_layer_lds_bytes(int32_t n_tower, int32_t Fi, int32_t Fo, int32_t No, int32_t divide_input) {
+  if (n_tower <= 0 || Fi <= 0 || Fo <= 0 || No < 0) return -1;
+  return (int64_t)tower_lds_bytes(n_tower, 1, Fi, Fo, No ? No : n_tower * Fo, divide_input != 0);
+}
+
 extern "C" int pna_tower_layer_f32(const pna_tower_layer_args* p, pna_stream_t stream) {
   if (!p) return pna_set_error(PNA_E_INVALID, "pna_tower_layer_f32: null args");
   if (int rc_ss = pna_check_struct_size("pna_tower_layer_f32", p->struct_size, sizeof(*p))) return rc_ss;

@@ -207,12 +207,11 @@ SMALL_TOWER_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_ROWS", "32768"))   # 
 
 
 def small_tower_fits(T, Fi, Fo, divided, No=None):
-    """Mirror of pna_tower_layer_f32's LDS check for a single tower per pass (the smallest tile it can run with)."""
-    quads = lambda k: (k + 15) // 16   # noqa: E731
-    No = T * Fo if No is None else No
-    floats = 16 * (quads(4 * Fi) * 16 + 4) + (T if divided else 1) * 16 * (quads(Fi) * 16 + 4) + 16 * (quads(T * Fo) * 16 + 4) + \
-        16 * 256 + 3 * quads(T * Fo) * 16 + quads(No) * 16 + 64
-    return floats * 4 <= 160 * 1024
+    """pna_tower_layer_f32's own LDS check (pna_tower_layer_lds_bytes): its tile at a single tower per pass, the smallest it can run
+    with, within the budget.  No: the mixing network's output width, None without one.  The last shape's answer is kept (one memo
+    entry on this function): a layer whose whole call is some 30 us asks on every call."""
+    shape = (T, Fi, Fo, No or 0, bool(divided))
+    return 0 < memo(small_tower_fits, "_pna_amd_answer", (), shape, lambda: _lib.lib().pna_tower_layer_lds_bytes(*shape)) <= ops.LDS_BUDGET
 
 
 # bf16 batches up to this many nodes take pna_tower_layer_bf16 (one C call); 0 turns the path off.  The default follows
@@ -230,7 +229,7 @@ def bf16_small_applies(graph, V, *, T, Fi, Fo, A, divide_input, posttrans_affine
         return False
     if edge_features and etab is None:
         return False
-    if ops.tower_layer_bf16_lds_bytes(T, Fi, Fo, A, divide_input, No=No, no_self_panel=no_self_panel) > 160 * 1024:
+    if not 0 < ops.tower_layer_bf16_lds_bytes(T, Fi, Fo, A, divide_input, No=No, no_self_panel=no_self_panel) <= ops.LDS_BUDGET:
         return False
     return graph.heavy_schedule().n_heavy == 0
 
@@ -1190,12 +1189,9 @@ SMALL_TRAIN_ROWS = int(os.environ.get("PNA_AMD_SMALL_TRAIN_ROWS", "0"))
 
 
 def small_train_fits(F, N):
-    """Mirror of pna_simple_train_fwd_f32's scope and LDS need (one 16 x 4F aggregate tile, one 16 x N output tile, the row scalers):
-    4 <= F <= 128, 1 <= N <= 128 -- at most 42 KB of the CU's 160 KB."""
-    quads = lambda k: (k + 15) // 16   # noqa: E731
-    if not (4 <= F <= 128 and 1 <= N <= 128):
-        return False
-    return 4 * (16 * (quads(4 * F) * 16 + 4) + 16 * (quads(N) * 16 + 1) + 48) <= 160 * 1024
+    """Whether the widths are inside pna_simple_train_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, two rows without edges and one scaler)
+    return _lib.lib().pna_simple_train_workspace_bytes(2, 0, F, N, 1) >= 0
 
 
 # PNALayer TRAINING batches up to this many nodes take the one-call route (autograd.TowerLayerSmallTrainFn:
@@ -1204,10 +1200,9 @@ SMALL_TOWER_TRAIN_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_ROWS", "0
 
 
 def small_tower_train_fits(T, Fi, Fo, S=3):
-    """Mirror of pna_tower_train_fwd_f32's scope: 1 <= T <= 8 towers, 4 <= Fi <= 128 (a lane of the gather owns two columns), T Fi <= 512,
-    1 <= Fo, T Fo <= 128, 1 <= S <= 3 scalers -- the widest tile set (one tower's 16 x 4 Fi aggregate, its 16 x Fi input slice, the
-    16 x T Fo output) is 50 KB of the CU's 160 KB."""
-    return 1 <= T <= 8 and 4 <= Fi <= 128 and T * Fi <= 512 and 1 <= Fo and T * Fo <= 128 and 1 <= S <= 3
+    """Whether towers, widths and scalers are inside pna_tower_train_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, two rows without edges)
+    return _lib.lib().pna_tower_train_workspace_bytes(2, 0, T, Fi, Fo, S, 0) >= 0
 
 
 # PNALayer TRAINING batches WITH EDGE FEATURES up to this many nodes take the one-call route (autograd.TowerLayerEdgeSmallTrainFn:
@@ -1217,9 +1212,9 @@ SMALL_TOWER_TRAIN_EDGE_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_EDGE
 
 
 def small_tower_train_edge_fits(T, Fi, Fo, S=3, edge_dim=0):
-    """Mirror of pna_tower_edge_train_fwd_f32's scope: small_tower_train_fits and 1 <= edge_dim <= 64 (the K of the edge tile: 16 rows
-    of at most 64 features, inside the LDS the rows kernels already use)."""
-    return small_tower_train_fits(T, Fi, Fo, S) and 1 <= edge_dim <= 64
+    """Whether towers, widths, scalers and edge_dim are inside pna_tower_edge_train_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, two rows without edges)
+    return _lib.lib().pna_tower_edge_train_workspace_bytes(2, 0, T, Fi, Fo, S, 0, edge_dim) >= 0
 
 
 # PNALayer TRAINING batches whose towers have DROPOUT (0 < p < 1), with or without edge features, up to this many nodes take the
@@ -1255,26 +1250,17 @@ def dropout_mask(V, C, p, seed, offset, device):
 NET_ENDS_ROWS = int(os.environ.get("PNA_AMD_NET_ENDS_ROWS", "0"))
 
 
-def embed_sum_fits(rows, F):
-    """Mirror of pna_embed_sum_*_f32's scope: 1..16 tables of >= 1 rows, 1 <= F <= 256, and ONE fp32 image of all tables --
-    sum_j rows_j x round4(F) floats -- within 128 KiB of LDS (the atom encoder at F = 128: 88 576 bytes)."""
-    if not (1 <= len(rows) <= _lib.PNA_MAX_EMBED_TABLE and 1 <= F <= 256 and all(r >= 1 for r in rows)):
-        return False
-    return sum(rows) * ((F + 3) // 4 * 4) * 4 <= 128 * 1024
-
-
-def embed_sum_slab_rows(V):
-    """Rows per slab of pna_embed_sum_bwd_f32 (a slab = one workgroup = one workspace slot): at least PNA_EMBED_SLAB_ROWS, and long
-    enough that there are never more than PNA_EMBED_MAX_SLABS of them."""
-    return max(_lib.PNA_EMBED_SLAB_ROWS, -(-V // _lib.PNA_EMBED_MAX_SLABS))
-
-
 def embed_sum_workspace_bytes(V, rows, F):
-    """pna_embed_sum_workspace_bytes' formula: one image per slab; -1 outside the scope."""
-    if V < 1 or not embed_sum_fits(rows, F):
-        return -1
-    L = embed_sum_slab_rows(V)
-    return -(-V // L) * sum(rows) * ((F + 3) // 4 * 4) * 4
+    """pna_embed_sum_workspace_bytes: the backward's bytes for V index rows over tables of `rows` rows each; -1 outside the scope."""
+    return _lib.lib().pna_embed_sum_workspace_bytes(V, len(rows), (ctypes.c_int32 * len(rows))(*rows), F)
+
+
+def embed_sum_fits(rows, F):
+    """Whether the tables and the width are inside pna_embed_sum_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest call of the scope, one index row; the last shape's answer is
+    # kept, one memo entry on this function: the encoder's whole step can be 120 us and asks on every call)
+    shape = (tuple(rows), F)
+    return memo(embed_sum_fits, "_pna_amd_answer", (), shape, lambda: embed_sum_workspace_bytes(1, rows, F)) >= 0
 
 
 # The GRU update between two message-passing steps (nets.GRU, layers.GRU: nn.GRU over a length-1 sequence) takes the one-call route
@@ -1283,93 +1269,60 @@ GRU_ROWS = int(os.environ.get("PNA_AMD_GRU_ROWS", "0"))
 
 
 def gru_cell_fits(I, Hc, input_size, hidden_size):
-    """Mirror of pna_gru_cell_*_f32's scope in the widths: 1 <= input_size <= 128, 2 <= hidden_size <= 128, 1 <= I <= input_size columns
-    of x and 1 <= Hc <= hidden_size columns of h (the missing ones are the reference's zero padding)."""
-    return 1 <= input_size <= 128 and 2 <= hidden_size <= 128 and 1 <= I <= input_size and 1 <= Hc <= hidden_size
-
-
-def gru_cell_slab_rows(V):
-    """Rows per slab of pna_gru_cell_bwd_f32's weight gradient (a slab = one workspace slot): at least PNA_GRU_SLAB_ROWS, and long enough
-    that there are never more than PNA_GRU_MAX_SLABS of them."""
-    return max(_lib.PNA_GRU_SLAB_ROWS, -(-V // _lib.PNA_GRU_MAX_SLABS))
+    """Whether the widths are inside pna_gru_cell_*_f32's scope, by the entry points' own check (pna_gru_cell_in_scope)."""
+    # (the check takes the whole shape: asked at the smallest call of the scope, two rows)
+    return bool(_lib.lib().pna_gru_cell_in_scope(2, I, Hc, input_size, hidden_size))
 
 
 def gru_cell_workspace_bytes(V, I, Hc, hidden_size):
-    """pna_gru_cell_workspace_bytes' formula: dgi / dgh as (V, 4H) and one image of the four parameter gradients per slab; -1 outside
-    the scope."""
-    if V < 2 or V >= 2 ** 31 or not gru_cell_fits(I, Hc, 128, hidden_size):
-        return -1
-    L = gru_cell_slab_rows(V)
-    return 4 * (V * 4 * hidden_size + -(-V // L) * 3 * hidden_size * (I + Hc + 2))
+    """pna_gru_cell_workspace_bytes: the backward's bytes (dgi / dgh and one image of the parameter gradients per slab); -1 outside the
+    scope."""
+    return _lib.lib().pna_gru_cell_workspace_bytes(V, I, Hc, hidden_size)
 
 
 # The dense-adjacency PNALayer (pna_amd.pytorch.pna.layer.PNALayer: the multitask GNN's convolution) takes the one-call route
 # (autograd.DenseLayerFn: pna_dense_layer_fwd_f32 / _bwd_f32) on calls of up to this many rows B N.  0 = off, the default (DESIGN.md 4.21)
 DENSE_LAYER_ROWS = int(os.environ.get("PNA_AMD_DENSE_LAYER_ROWS", "0"))
-DENSE_LAYER_LDS_BUDGET = 160 * 1024
 DENSE_LAYER_AGGREGATORS = ("mean", "max", "min", "std")
 
 
 def dense_layer_lds_bytes(N, T, Fi, Fo, A, S):
-    """pna_dense_layer_lds_bytes' formula: one graph's block (odd row pitch), x, P, Q, the row means and 1 / (2 std), the aggregates, two
-    (N, T Fo) row sets, 3 + S per-node factors and two byte planes of arg indices; -1 where the widths are outside the scope."""
-    if not (1 <= N <= _lib.PNA_DENSE_MAX_NODES and 1 <= T <= _lib.PNA_MAX_TOWER and Fi >= 1 and T * Fi <= 64 and Fo >= 1 and T * Fo <= 64
-            and 1 <= A <= 4 and 1 <= S <= 3):
-        return -1
-    TF, C = T * Fi, T * Fo
-    return 4 * N * ((N | 1) + 5 * TF + A * TF + 2 * C + 3 + S) + (2 * N * TF + 15) // 16 * 16
-
-
-def dense_layer_fits(N, T, Fi, Fo, A, S):
-    """Mirror of pna_dense_layer_*_f32's scope in the shapes: the widths, and one graph inside a workgroup's 160 KiB of LDS."""
-    return 0 < dense_layer_lds_bytes(N, T, Fi, Fo, A, S) <= DENSE_LAYER_LDS_BUDGET
-
-
-def dense_layer_slab_graphs(B):
-    """Graphs per slab (a slab = one workgroup = one image of the parameter gradients): never more than PNA_DENSE_MAX_SLABS slabs."""
-    return -(-B // _lib.PNA_DENSE_MAX_SLABS)
+    """pna_dense_layer_lds_bytes: the LDS bytes of one graph's workgroup; -1 where the widths are outside the scope."""
+    return _lib.lib().pna_dense_layer_lds_bytes(N, T, Fi, Fo, A, S)
 
 
 def dense_layer_workspace_bytes(B, N, T, Fi, Fo, A, S):
-    """pna_dense_layer_workspace_bytes' formula: min(B, PNA_DENSE_MAX_SLABS) images of every parameter gradient (at least one per slab
-    in use, monotone in B); -1 outside the scope."""
-    if B < 1 or B * N >= 2 ** 31 or not dense_layer_fits(N, T, Fi, Fo, A, S):
-        return -1
-    C = T * Fo
-    return min(B, _lib.PNA_DENSE_MAX_SLABS) * (T * (2 * Fi * Fi + Fi + Fo * (1 + A * S) * Fi + Fo) + C * C + C) * 4
+    """pna_dense_layer_workspace_bytes: the backward's bytes (images of every parameter gradient); -1 outside the scope."""
+    return _lib.lib().pna_dense_layer_workspace_bytes(B, N, T, Fi, Fo, A, S)
+
+
+def dense_layer_fits(N, T, Fi, Fo, A, S):
+    """Whether one graph's shapes are inside pna_dense_layer_*_f32's scope (the widths, and the graph inside a workgroup's LDS), by the
+    library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, one graph)
+    return dense_layer_workspace_bytes(1, N, T, Fi, Fo, A, S) > 0
 
 
 # The Set2Set graph readout (layers.Set2Set: the multitask GNN's graph head) takes the one-call route (autograd.Set2SetFn:
 # pna_set2set_fwd_f32 / _bwd_f32) on calls of up to this many rows B N.  0 = off, the default (DESIGN.md 4.22)
 S2S_ROWS = int(os.environ.get("PNA_AMD_S2S_ROWS", "0"))
-S2S_LDS_BUDGET = 160 * 1024
 
 
 def set2set_lds_bytes(N, D):
-    """pna_set2set_lds_bytes' formula, the backward's footprint: both weight matrices on odd row pitches, the bias sum, the graph's rows,
-    the three gradient accumulators, grad_x and the step state; -1 where N or D is outside the scope."""
-    if not (1 <= N <= _lib.PNA_S2S_MAX_NODES and 1 <= D <= _lib.PNA_S2S_MAX_WIDTH):
-        return -1
-    PI, PH = (2 * D) | 1, D | 1
-    return (4 * (4 * D * (PI + PH) + N * PH + 12 * D * D + N * D + 26 * D + 2 * N + 4) + 15) // 16 * 16
-
-
-def set2set_fits(N, D, steps):
-    """Mirror of pna_set2set_*_f32's scope in the shapes: the bounds on N, D and steps, and the backward inside a workgroup's 160 KiB."""
-    return 1 <= steps <= _lib.PNA_S2S_MAX_STEPS and 0 < set2set_lds_bytes(N, D) <= S2S_LDS_BUDGET
-
-
-def set2set_slab_graphs(B):
-    """Graphs per slab (a slab = one workgroup = one image of the parameter gradients): never more than PNA_S2S_MAX_SLABS slabs."""
-    return -(-B // _lib.PNA_S2S_MAX_SLABS)
+    """pna_set2set_lds_bytes: the LDS bytes of the backward's workgroup; -1 where N or D is outside the scope."""
+    return _lib.lib().pna_set2set_lds_bytes(N, D)
 
 
 def set2set_workspace_bytes(B, N, D, steps):
-    """pna_set2set_workspace_bytes' formula: min(B, PNA_S2S_MAX_SLABS) times one image of the parameter gradients and the steps' records
-    [gates 4D | c D | q* 2D | a N] of the graph a slab is working on; -1 outside the scope."""
-    if B < 1 or B * N >= 2 ** 31 or not set2set_fits(N, D, steps):
-        return -1
-    return min(B, _lib.PNA_S2S_MAX_SLABS) * (12 * D * D + 4 * D + steps * (7 * D + N)) * 4
+    """pna_set2set_workspace_bytes: the backward's bytes (images of the parameter gradients and the steps' records); -1 outside the
+    scope."""
+    return _lib.lib().pna_set2set_workspace_bytes(B, N, D, steps)
+
+
+def set2set_fits(N, D, steps):
+    """Whether one graph's shapes and the step count are inside pna_set2set_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, one graph)
+    return set2set_workspace_bytes(1, N, D, steps) > 0
 
 
 def simple_layer_small(layer, graph, h, row_scales):

@@ -22,6 +22,7 @@ from .graph import HeavySchedule
 # persistent tiles (>= X3_MIN_ROWS rows), f32 otherwise.
 POSTTRANS_ARITH = os.environ.get("PNA_AMD_POSTTRANS", "auto")
 X3_MIN_ROWS = 16384
+LDS_BUDGET = 160 * 1024   # bytes of LDS one workgroup can take on gfx950: what a tile size asked of the library is compared with
 
 _TUNE = {}   # process-wide tuning overrides (set by tools/sweep.py [removed in round 5: git history] and bench.py), see set_tuning()
 
@@ -433,7 +434,7 @@ def pack_rows(x: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = 
 def project_applies(x: torch.Tensor, K: int, N: int) -> bool:
     """pna_project_f32's domain: 4 <= K <= 128, N <= 512, the weight image (16 ceil(K / 16) x (80 ceil(N / 80) + 4) floats) within 160 KB of LDS."""
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and 4 <= K <= 128 and 1 <= N <= 512
-            and (K + 15) // 16 * 16 * ((N + 79) // 80 * 80 + 4) * 4 <= 160 * 1024)
+            and (K + 15) // 16 * 16 * ((N + 79) // 80 * 80 + 4) * 4 <= LDS_BUDGET)
 
 
 def project(x: torch.Tensor, K: int, weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -453,7 +454,7 @@ def project(x: torch.Tensor, K: int, weight: torch.Tensor, out: Optional[torch.T
 def project_scaled_applies(x: torch.Tensor, K: int, N: int, blocks: int) -> bool:
     """pna_project_scaled_f32's domain: N <= 80, 1..4 blocks (four: K <= 80), the image of all blocks within 160 KB of LDS."""
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and 4 <= K <= 128 and 1 <= N <= 80 and 1 <= blocks <= 4
-            and (blocks < 4 or K <= 80) and ((K + 15) // 16 * 16 * (80 * blocks + 4) + 240) * 4 <= 160 * 1024)
+            and (blocks < 4 or K <= 80) and ((K + 15) // 16 * 16 * (80 * blocks + 4) + 240) * 4 <= LDS_BUDGET)
 
 
 def project_scaled(x: torch.Tensor, K: int, weight: torch.Tensor, scales: Optional[torch.Tensor], beta: Optional[torch.Tensor], self_block: bool,
@@ -885,13 +886,11 @@ def contract_bf16(a: torch.Tensor, K: int, w_img: torch.Tensor, N: int, row_scal
 # ---- the bf16 tower layer of molecule-sized batches as one call (pna_bf16_small.hip) ------------------------------------------
 def tower_layer_bf16_lds_bytes(T: int, Fi: int, Fo: int, A: int, divide_input: bool, *, No: Optional[int] = None,
                                no_self_panel: bool = False) -> int:
-    """Host mirror of pna_tower_layer_bf16's LDS check: bytes of one 16-row tile (aggregates of every tower, the rows' own features,
-    the concatenated tower outputs when a mixing network follows); the kernel refuses more than 160 KiB."""
-    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
-    la = T * r(A * r(Fi, 8), 32) + 8
-    lh = 0 if no_self_panel else (T if divide_input else 1) * r(Fi, 32) + 8
-    lc = 0 if No is None else r(T * Fo, 32) + 8
-    return 16 * (la + lh + lc) * 2
+    """pna_tower_layer_bf16_lds_bytes: bytes of the entry point's 16-row tile (aggregates of every tower, the rows' own features, the
+    concatenated tower outputs when a mixing network follows) by its own code; it refuses more than LDS_BUDGET.  -1: a width below 1.
+    The last shape's answer is kept (one memo entry on this function): a layer whose whole call is some 40 us asks on every call."""
+    shape = (T, Fi, Fo, A, bool(divide_input), No or 0, bool(no_self_panel))
+    return memo(tower_layer_bf16_lds_bytes, "_pna_amd_answer", (), shape, lambda: _lib.lib().pna_tower_layer_bf16_lds_bytes(*shape))
 
 
 def tower_layer_bf16(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *, n_tower: int, Fi: int, Fo: int, divide_input: bool,
@@ -955,11 +954,9 @@ def tower_layer_bf16(rowptr: torch.Tensor, col: torch.Tensor, h: torch.Tensor, *
 
 # ---- the hidden layers of a deep pre_nn per edge (pna_bf16_edge_mlp.hip: bf16 inference of the PyG PNAConv) -----------------------
 def edge_mlp_bf16_lds_bytes(F: int, n_hidden: int) -> int:
-    """Host mirror of pna_edge_mlp_bf16's LDS check: one tower's hidden weights (rows padded by 16 elements) and the four 16-edge tiles
-    of a workgroup; the entry point refuses more than 160 KiB."""
-    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
-    Kp = r(r(F, 8), 32)
-    return 2 * (n_hidden * r(F, 16) * (Kp + 16) + 64 * (Kp + 8))
+    """pna_edge_mlp_bf16_lds_bytes: one tower's hidden weights and the four 16-edge tiles of a workgroup, by the entry point's own
+    code; it refuses more than LDS_BUDGET.  -1 outside the widths and depths it serves."""
+    return _lib.lib().pna_edge_mlp_bf16_lds_bytes(F, n_hidden)
 
 
 def edge_mlp_image_bf16(weights: Sequence[Sequence[torch.Tensor]], biases: Sequence[Sequence[torch.Tensor]]):

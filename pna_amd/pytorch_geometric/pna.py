@@ -137,14 +137,14 @@ class PNAConv(PF.DropsCachesOnConversion, torch.nn.Module):
     def _bf16_path(self, x, edge_attr=None):
         """Whether a call is served by the bf16 inference kernels (functional.pyg_conv_bf16): _bf16_inference and what the kernels
         hold -- at most 128 output columns, towers * round8(F_in) <= 512 (one gathered row), at most 3 scalers, and a pre_nn that
-        is one Linear or whose hidden layers fit pna_edge_mlp_bf16 (F_in <= 128, one tower's hidden weights in LDS).  Every other
-        call takes the fp32 code and fails there as before."""
+        is one Linear or whose hidden layers pna_edge_mlp_bf16 serves (ops.edge_mlp_bf16_lds_bytes: -1 outside its widths and depths,
+        else one tower's hidden weights in LDS).  Every other call takes the fp32 code and fails there as before."""
         if not _bf16_inference(self, x, edge_attr, self.edge_dim is not None):
             return False
         if self.out_channels > 128 or self.towers * ((self.F_in + 7) // 8 * 8) > 512 or len(self.scaler_names) > 3:
             return False
         hidden = len(self.pre_nns[0]) // 2
-        if hidden and (self.F_in > 128 or ops.edge_mlp_bf16_lds_bytes(self.F_in, hidden) > 160 * 1024):
+        if hidden and not 0 < ops.edge_mlp_bf16_lds_bytes(self.F_in, hidden) <= ops.LDS_BUDGET:
             return False
         return True
 

@@ -42,6 +42,9 @@ CENSUS = {
     "_pna_amd_small": ("gpu", f"{GPU} paths tower_small, tower_small_etab, simple_small; {HOST}::test_warm_layer_copies_without_its_plan",
                        "the fp32 one-call plans (_SmallTowerPlan / _SmallSimplePlan)"),
     "_pna_amd_small_ok": ("exempt", "", "booleans of the layer's STRUCTURE (layer counts, aggregator names, widths): reads no tensor value"),
+    # functional.py, ops.py
+    "_pna_amd_answer": ("exempt", "", "the library's tile bytes for one tuple of shape integers (functional.small_tower_fits, "
+                        "ops.tower_layer_bf16_lds_bytes; tests/test_lds_queries_host.py sweeps shapes through it): reads no tensor value"),
     # functional.py
     "_pna_amd_fold": ("host", f"{HOST}::test_fold_batchnorm_follows_its_tensors; {GPU} every fp32 path with BatchNorm", "eval BatchNorm as scale / shift"),
     "_pna_amd_fold_f32": ("host", f"{HOST}::test_fold_batchnorm_follows_its_tensors; {GPU} bf16 paths", "the same, folded in fp32 from bf16 tensors"),

@@ -108,11 +108,24 @@ def test_dispatch_predicates_take_bf16_inference_only():
 
 def test_the_lds_mirror_is_the_librarys():
     L = _lib.lib()
+    r = lambda x, m: (x + m - 1) // m * m   # noqa: E731
     for F in (1, 5, 16, 75, 80, 128):
-        for nh in (1, 2, 5):
-            assert L.pna_edge_mlp_bf16_lds_bytes(F, nh) == ops.edge_mlp_bf16_lds_bytes(F, nh), (F, nh)
+        for nh in (1, 2, 5, 64):
+            Kp = r(r(F, 8), 32)                                                    # (the test's own statement of the kernel's tile)
+            want = 2 * (nh * r(F, 16) * (Kp + 16) + 64 * (Kp + 8))
+            assert L.pna_edge_mlp_bf16_lds_bytes(F, nh) == want == ops.edge_mlp_bf16_lds_bytes(F, nh), (F, nh)
     assert L.pna_edge_mlp_bf16_lds_bytes(129, 1) == -1 and L.pna_edge_mlp_bf16_lds_bytes(0, 1) == -1 and L.pna_edge_mlp_bf16_lds_bytes(8, 0) == -1
     assert ops.edge_mlp_bf16_lds_bytes(128, 3) <= 160 * 1024 < ops.edge_mlp_bf16_lds_bytes(128, 4)
+    assert ops.LDS_BUDGET == 160 * 1024
+
+
+def test_a_pre_nn_deeper_than_the_edge_mlp_serves_takes_the_fp32_code():
+    """pna_edge_mlp_bf16 refuses more than 64 hidden layers, whatever their bytes: the answer is the library's -1 (a formula of the tile
+    alone gives 104 960 bytes, which would pass for a fit), and the predicate built on it sends the layer to the fp32 code."""
+    assert ops.edge_mlp_bf16_lds_bytes(8, 64) == 103424 and ops.edge_mlp_bf16_lds_bytes(8, 65) == -1
+    assert ops.edge_mlp_bf16_lds_bytes(129, 1) == -1 and ops.edge_mlp_bf16_lds_bytes(0, 1) == -1 and ops.edge_mlp_bf16_lds_bytes(8, 0) == -1
+    with torch.no_grad():
+        assert _conv(pre_layers=65)._bf16_path(_feat(BF)) and not _conv(pre_layers=66)._bf16_path(_feat(BF))
 
 
 def test_bf16_calls_outside_the_predicate_keep_todays_error():

@@ -87,7 +87,7 @@ def test_slab_case_equals_two_half_batches(cuda_device):
     """B = 300 > PNA_S2S_MAX_SLABS: two graphs per workgroup.  The halves (150 each: one graph per workgroup) give the same out and grad_x
     bits, and parameter gradients whose sum is within the bars of the whole batch's."""
     c = C.s2s_case("slab")
-    assert c["B"] > _lib.PNA_S2S_MAX_SLABS and PF.set2set_slab_graphs(c["B"]) == 2 and PF.set2set_slab_graphs(c["B"] // 2) == 1
+    assert c["B"] > _lib.PNA_S2S_MAX_SLABS and -(-c["B"] // _lib.PNA_S2S_MAX_SLABS) == 2 and -(-(c["B"] // 2) // _lib.PNA_S2S_MAX_SLABS) == 1
     ref64, _, bars = C.references("slab")
     whole = _on(c, cuda_device)
     out, g = _forward(c, whole), _backward(c, whole)

@@ -229,7 +229,7 @@ def test_knob_off_runs_the_old_lines_on_the_host():
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_short_structs_are_refused():
     L = _lib.lib()
-    for name in ("pna_gru_cell_fwd_f32", "pna_gru_cell_bwd_f32", "pna_gru_cell_workspace_bytes"):
+    for name in ("pna_gru_cell_fwd_f32", "pna_gru_cell_bwd_f32", "pna_gru_cell_workspace_bytes", "pna_gru_cell_in_scope"):
         assert hasattr(L, name), name
     assert L.pna_abi_version() == _lib.PNA_ABI_VERSION == 23
     assert "23, additive: + pna_gru_cell_fwd_f32" in open(os.path.join(ROOT, "include", "pna_amd.h")).read()
@@ -299,7 +299,7 @@ def test_workspace_bytes_formula_and_scope():
         for V in (2, 15, C.SLAB - 1, C.SLAB, C.SLAB + 1, 3 * C.SLAB + 17, C.SLAB * C.MAX_SLABS, C.SLAB * C.MAX_SLABS + 1, 52000, 10 ** 6):
             slab = max(C.SLAB, -(-V // C.MAX_SLABS))
             n_slab = -(-V // slab)
-            assert n_slab <= C.MAX_SLABS and C.slab_rows(V) == slab == PF.gru_cell_slab_rows(V)
+            assert n_slab <= C.MAX_SLABS and C.slab_rows(V) == slab == max(_lib.PNA_GRU_SLAB_ROWS, -(-V // _lib.PNA_GRU_MAX_SLABS))
             want = 4 * (V * 4 * H + n_slab * 3 * H * (I + Hc + 2))
             assert L.pna_gru_cell_workspace_bytes(V, I, Hc, H) == want == PF.gru_cell_workspace_bytes(V, I, Hc, H), (V, H, I, Hc)
     for V, I, Hc, H in ((1, 4, 4, 4), (0, 4, 4, 4), (2 ** 31, 4, 4, 4), (8, 0, 4, 4), (8, 129, 4, 4), (8, 4, 0, 4), (8, 4, 5, 4), (8, 4, 1, 1), (8, 4, 4, 129)):

@@ -239,7 +239,7 @@ def test_workspace_bytes_formula_and_scope():
             n_slab = -(-V // L)
             assert n_slab <= C.MAX_SLABS                                           # bounded however large V is
             assert _ws(V, rows, F) == n_slab * image == PF.embed_sum_workspace_bytes(V, rows, F), (V, rows, F)
-            assert PF.embed_sum_slab_rows(V) == L
+            assert max(_lib.PNA_EMBED_SLAB_ROWS, -(-V // _lib.PNA_EMBED_MAX_SLABS)) == L
     # the LDS limit: one fp32 image of all tables within 128 KiB -- a positive size just inside, -1 just outside
     assert _ws(100, (256,), 128) == 2 * 128 * 1024 and _ws(100, (257,), 128) == -1
     assert _ws(100, (119, 137), 128) > 0 and _ws(100, (119, 138), 128) == -1

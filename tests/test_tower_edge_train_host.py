@@ -203,7 +203,8 @@ def test_workspace_bytes_is_monotone_refuses_shapes_outside_the_scope_and_the_mi
                 for S in (0, 1, 3, 4):
                     for ed in (0, 1, 50, 64, 65):
                         fits = PF.small_tower_train_edge_fits(T, Fi, Fo, S, ed)
-                        assert fits == (ws(400, 1000, T, Fi, Fo, S, 1, ed) >= 0), (T, Fi, Fo, S, ed)
+                        want = 1 <= T <= 8 and 4 <= Fi <= 128 and T * Fi <= 512 and 1 <= Fo and T * Fo <= 128 and 1 <= S <= 3 and 1 <= ed <= 64
+                        assert fits == want == (ws(400, 1000, T, Fi, Fo, S, 1, ed) >= 0), (T, Fi, Fo, S, ed)
                         if fits:                                                   # inside the scope of the route without edge features
                             assert base(400, 1000, T, Fi, Fo, S, 1) >= 0
 

@@ -174,7 +174,8 @@ def test_workspace_bytes_is_monotone_refuses_shapes_outside_the_scope_and_the_mi
         for Fi in (3, 4, 15, 64, 65, 75, 128, 129):
             for Fo in (0, 1, 14, 16, 17, 26, 128, 129):
                 for S in (0, 1, 3, 4):
-                    assert PF.small_tower_train_fits(T, Fi, Fo, S) == (ws(400, 1000, T, Fi, Fo, S, 1) >= 0), (T, Fi, Fo, S)
+                    want = 1 <= T <= 8 and 4 <= Fi <= 128 and T * Fi <= 512 and 1 <= Fo and T * Fo <= 128 and 1 <= S <= 3
+                    assert PF.small_tower_train_fits(T, Fi, Fo, S) == want == (ws(400, 1000, T, Fi, Fo, S, 1) >= 0), (T, Fi, Fo, S)
 
 
 def test_kernels_use_no_scratch_and_pass_the_isa_audit(tmp_path):
