@@ -26,7 +26,11 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_gru_cell_in_scope, pna_tower_layer_lds_bytes, pna_tower_layer_bf16_lds_bytes (host-only queries: the
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_mlp_head_fwd_f32 / pna_mlp_head_bwd_f32 / pna_mlp_head_workspace_bytes / pna_mlp_head_in_scope /
+                                  pna_mlp_head_args, PNA_MAX_MLP_LAYERS, PNA_MLP_MAX_WIDTH, PNA_MLP_ACT_*, PNA_MLP_SLAB_ROWS, PNA_MLP_MAX_SLABS (the dense
+                                  heads of the nets: 1 to 4 Linear layers with none / ReLU / LeakyReLU over rows, one call each way); no
+                                  existing struct or entry point changed.
+                                  23, additive: + pna_gru_cell_in_scope, pna_tower_layer_lds_bytes, pna_tower_layer_bf16_lds_bytes (host-only queries: the
                                   scope and tile checks of pna_gru_cell_*_f32, pna_tower_layer_f32 and pna_tower_layer_bf16, so that a binding asks
                                   the library where it would otherwise copy a bound); no existing struct or entry point changed.
                                   23, additive: + pna_tower_drop_train_fwd_f32 / pna_tower_drop_train_bwd_f32 / pna_tower_drop_args, pna_dropout_mask_f32
@@ -1801,6 +1805,81 @@ int64_t pna_gru_cell_workspace_bytes(int64_t V, int32_t I, int32_t Hc, int32_t h
 int32_t pna_gru_cell_in_scope(int64_t V, int32_t I, int32_t Hc, int32_t input_size, int32_t hidden_size);
 int pna_gru_cell_fwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
 int pna_gru_cell_bwd_f32(const pna_gru_cell_args* args, pna_stream_t stream);
+
+/* ---- The dense heads of the nets: 1 to 4 Linear layers with their activations over rows, one call each way --------------------------
+ * replaces: realworld_benchmark/nets/mlp_readout_layer.py:14-29 (MLPReadout: the tail of the molecule, HIV and superpixel nets),
+ * models/layers.py:101-234 (FCLayer / MLP without dropout and batch-norm: the multitask GNN's nodes_read_out), the two nn.Linear
+ * embeddings of nets/superpixels_graph_classification/pna_net.py:38-41 as one-layer calls, and what autograd derives from them.
+ *
+ * Semantics: y = f_L(... f_1(x)), f_l(h) = act_l(h W_l^T + b_l), l = 1 .. n_layers.  widths[0] is the width of x, widths[l] the
+ * output width of layer l; W_l = w[l - 1] is (widths[l], ldw >= widths[l - 1]) row-major as nn.Linear keeps it, b_l = b[l - 1] may be
+ * NULL (bias=False).  act[l - 1] is PNA_MLP_ACT_NONE, _RELU (max(a, 0); derivative 0 at a <= 0) or _LEAKY (a > 0 ? a : a slope[l - 1];
+ * derivative slope at a <= 0): torch's values, the point a == 0 included.  x and y are fp32 with unit column stride and any row pitch
+ * >= their width; columns past a width are never read.  Rows are independent: a NaN or Inf in a row of x stays in that row of y and
+ * of grad_x.
+ *
+ * pna_mlp_head_fwd_f32 (one launch): a workgroup owns 16 rows; the x tile sits in LDS zero-filled to the K pitch; every layer runs on
+ *   v_mfma_f32_16x16x4_f32 (exact fp32 products, -ffp-contract=off) with B fragments read straight from the parameters; a wavefront
+ *   owns 16 output columns and its activation epilogue writes the next layer's A tile into the other of two LDS buffers; only the last
+ *   layer's rows are stored.  Nothing is saved: the same bits whether a backward follows or not.
+ * pna_mlp_head_bwd_f32 (at most three launches, no atomics of any kind, bitwise repeatable):
+ *   (a) rows kernel over the same tiles: rebuilds the pre-activations a_1 .. a_L of its rows in LDS from x, then walks down with
+ *       dz_l = grad_l act_l'(a_l) and grad_(l-1) = dz_l W_l on the MFMA; stores grad_x; when a parameter gradient is wanted, stores
+ *       h_1 .. h_(L-1) and dz_1 .. dz_L once to the workspace.
+ *   (b) per slab of max(PNA_MLP_SLAB_ROWS, ceil(V / PNA_MLP_MAX_SLABS)) consecutive rows and per wanted layer: grad_W_l = dz_l^T h_(l-1)
+ *       on the MFMA and the column sums grad_b_l (a ones column), into the slab's slot of the workspace.
+ *   (c) one thread per parameter element adds the slots in slab order in float64 and stores fp32: grad_w[l - 1] (widths[l],
+ *       widths[l - 1]) contiguous, grad_b[l - 1] [widths[l]].
+ *   A gradient whose need_* flag is 0 is neither computed into nor written (its pointer may be NULL); (b) and (c) are not launched when
+ *   no parameter gradient is wanted, and nothing at all when no gradient is.
+ * Scope (PNA_E_INVALID outside it, pna_last_error names the clause, nothing is launched; pna_mlp_head_workspace_bytes returns -1 and
+ * pna_mlp_head_in_scope 0): 1 <= n_layers <= PNA_MAX_MLP_LAYERS, every width in 1 .. PNA_MLP_MAX_WIDTH, 1 <= V < 2^31, every act a
+ * PNA_MLP_ACT_* code.
+ * workspace (backward only): 4 (V (2 sum_(l=1..L) widths[l] - widths[L]) + n_slab sum_(l=1..L) widths[l] (widths[l - 1] + 1)) bytes,
+ * 16-byte aligned, no initialisation: no launch reads what the call has not written. */
+#define PNA_MAX_MLP_LAYERS 4
+#define PNA_MAX_MLP_WIDTHS 5  /* PNA_MAX_MLP_LAYERS + 1 */
+#define PNA_MLP_MAX_WIDTH 128
+#define PNA_MLP_ACT_NONE 0
+#define PNA_MLP_ACT_RELU 1
+#define PNA_MLP_ACT_LEAKY 2
+#define PNA_MLP_SLAB_ROWS 64
+#define PNA_MLP_MAX_SLABS 64
+typedef struct pna_mlp_head_args {
+  uint32_t struct_size;    /* sizeof(pna_mlp_head_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  int64_t V;               /* rows */
+  int32_t n_layers;        /* L */
+  int32_t widths[PNA_MAX_MLP_WIDTHS];       /* widths[0]: columns of x; widths[l]: outputs of layer l */
+  int32_t act[PNA_MAX_MLP_LAYERS];          /* PNA_MLP_ACT_* of layer l + 1 */
+  float slope[PNA_MAX_MLP_LAYERS];          /* the LeakyReLU slope of layer l + 1 (read for PNA_MLP_ACT_LEAKY only) */
+  int32_t need_x;          /* backward: 0 = that gradient is not computed and its buffer (may be NULL) is not written */
+  int32_t need_w[PNA_MAX_MLP_LAYERS];
+  int32_t need_b[PNA_MAX_MLP_LAYERS];
+  int32_t _pad0;
+  const float* x;          /* (V, ldx >= widths[0]) */
+  int64_t ldx;
+  const float* w[PNA_MAX_MLP_LAYERS];       /* (widths[l + 1], ldw[l] >= widths[l]): nn.Linear.weight as it is */
+  int64_t ldw[PNA_MAX_MLP_LAYERS];
+  const float* b[PNA_MAX_MLP_LAYERS];       /* [widths[l + 1]] or NULL */
+  float* y;                /* forward (V, ldy >= widths[L]) */
+  int64_t ldy;
+  const float* grad_out;   /* backward (V, ld_go >= widths[L]) */
+  int64_t ld_go;
+  float* grad_x;           /* backward (V, ld_gx >= widths[0]) */
+  int64_t ld_gx;
+  float* grad_w[PNA_MAX_MLP_LAYERS];        /* backward (widths[l + 1], widths[l]) contiguous */
+  float* grad_b[PNA_MAX_MLP_LAYERS];        /* backward [widths[l + 1]] */
+  void* workspace;         /* backward */
+  int64_t workspace_bytes;
+} pna_mlp_head_args;
+
+/* widths: n_layers + 1 entries.  -1 outside the scope. */
+int64_t pna_mlp_head_workspace_bytes(int64_t V, int32_t n_layers, const int32_t* widths);
+/* Host only, launches nothing.  1 when the shapes and activation codes are inside the scope above (the entry points' own check), else 0. */
+int32_t pna_mlp_head_in_scope(int64_t V, int32_t n_layers, const int32_t* widths, const int32_t* acts);
+int pna_mlp_head_fwd_f32(const pna_mlp_head_args* args, pna_stream_t stream);
+int pna_mlp_head_bwd_f32(const pna_mlp_head_args* args, pna_stream_t stream);
 
 /* ---- The dense-adjacency PNALayer (the multitask GNN's convolution), one call each way ------------------------------------------------
  * replaces: models/pytorch/pna/layer.py:33-49,99-109 (PNATower / PNALayer with 1-layer pretrans and posttrans and the Linear + LeakyReLU

@@ -23,6 +23,12 @@ PNA_EMBED_MAX_SLABS = 256
 PNA_GRU_F32 = 0
 PNA_GRU_SLAB_ROWS = 64          # pna_gru_cell_bwd_f32: a slab is max(this, ceil(V / PNA_GRU_MAX_SLABS)) rows
 PNA_GRU_MAX_SLABS = 64
+PNA_MAX_MLP_LAYERS = 4
+PNA_MAX_MLP_WIDTHS = PNA_MAX_MLP_LAYERS + 1
+PNA_MLP_MAX_WIDTH = 128
+PNA_MLP_ACT_NONE, PNA_MLP_ACT_RELU, PNA_MLP_ACT_LEAKY = 0, 1, 2
+PNA_MLP_SLAB_ROWS = 64          # pna_mlp_head_bwd_f32: a slab is max(this, ceil(V / PNA_MLP_MAX_SLABS)) rows
+PNA_MLP_MAX_SLABS = 64
 PNA_DENSE_MAX_NODES = 128
 PNA_DENSE_MAX_SLABS = 256       # pna_dense_layer_*: a slab is ceil(B / this) consecutive graphs, one workgroup and one gradient image each
 PNA_S2S_F32 = 0
@@ -425,6 +431,22 @@ class PnaGruCellArgs(_Args):
     ]
 
 
+class PnaMlpHeadArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("V", ctypes.c_int64), ("n_layers", ctypes.c_int32), ("widths", ctypes.c_int32 * PNA_MAX_MLP_WIDTHS),
+        ("act", ctypes.c_int32 * PNA_MAX_MLP_LAYERS), ("slope", ctypes.c_float * PNA_MAX_MLP_LAYERS),
+        ("need_x", ctypes.c_int32), ("need_w", ctypes.c_int32 * PNA_MAX_MLP_LAYERS), ("need_b", ctypes.c_int32 * PNA_MAX_MLP_LAYERS),
+        ("_pad0", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64),
+        ("w", ctypes.c_void_p * PNA_MAX_MLP_LAYERS), ("ldw", ctypes.c_int64 * PNA_MAX_MLP_LAYERS), ("b", ctypes.c_void_p * PNA_MAX_MLP_LAYERS),
+        ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
+        ("grad_out", ctypes.c_void_p), ("ld_go", ctypes.c_int64), ("grad_x", ctypes.c_void_p), ("ld_gx", ctypes.c_int64),
+        ("grad_w", ctypes.c_void_p * PNA_MAX_MLP_LAYERS), ("grad_b", ctypes.c_void_p * PNA_MAX_MLP_LAYERS),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 class PnaDenseLayerArgs(_Args):
     _fields_ = [
         ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
@@ -633,6 +655,13 @@ def lib():
         L.pna_gru_cell_in_scope.restype = ctypes.c_int32
         for fn in (L.pna_gru_cell_fwd_f32, L.pna_gru_cell_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaGruCellArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_mlp_head_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+        L.pna_mlp_head_workspace_bytes.restype = ctypes.c_int64
+        L.pna_mlp_head_in_scope.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        L.pna_mlp_head_in_scope.restype = ctypes.c_int32
+        for fn in (L.pna_mlp_head_fwd_f32, L.pna_mlp_head_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaMlpHeadArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         L.pna_dense_layer_lds_bytes.argtypes = [ctypes.c_int32] * 6
         L.pna_dense_layer_lds_bytes.restype = ctypes.c_int64

@@ -1314,6 +1314,81 @@ def gru_cell(x, h, gru):
     return GruCellFn.apply(*ts, torch.is_grad_enabled() and any(t.requires_grad for t in ts))
 
 
+# ---- the dense heads: 1 to 4 Linear layers with none / ReLU / LeakyReLU over rows as one C call each way (pna_mlp_head.hip) --------------
+_mlp_ws = {}        # device -> the backward's reusable workspace; nothing is keyed per module
+
+
+def _mlp_head_args(x, acts, ws, bs):
+    a = _lib.PnaMlpHeadArgs()
+    a.V, a.n_layers = x.shape[0], len(ws)
+    a.widths[0] = x.shape[1]
+    a.x, a.ldx = _lib.dev_ptr(x, torch.float32, "x"), x.stride(0)
+    for l, (w, b, (code, slope)) in enumerate(zip(ws, bs, acts)):
+        a.widths[l + 1], a.act[l], a.slope[l] = w.shape[0], code, slope
+        a.w[l], a.ldw[l] = _lib.dev_ptr(w, torch.float32, "weight"), w.stride(0)
+        a.b[l] = _lib.dev_ptr(b, torch.float32, "bias")
+    return a
+
+
+class MlpHeadFn(torch.autograd.Function):
+    """y = f_L(... f_1(x)), f_l(h) = act_l(h W_l^T + b_l), as ONE C call (pna_mlp_head_fwd_f32: one launch) and its backward as one
+    (pna_mlp_head_bwd_f32: at most three launches, no atomics, bitwise repeatable).  x: (V, widths[0]) fp32 with unit column stride and
+    any row pitch; acts: one (PNA_MLP_ACT_* code, slope) per layer; params: W_1, b_1, .., W_L, b_L as nn.Linear keeps them (a bias may be
+    None).  Once differentiable.  Only the inputs are saved: the backward rebuilds the hidden rows.  The workspace is one cached buffer
+    per device, grown on demand."""
+
+    @staticmethod
+    def forward(ctx, x, acts, *params):
+        x = _gru_rows(x)
+        ws = [_gru_rows(w) for w in params[0::2]]
+        bs = [None if b is None else b.contiguous() for b in params[1::2]]
+        dev, V = x.device, x.shape[0]
+        y = torch.empty(V, ws[-1].shape[0], dtype=torch.float32, device=dev)
+        a = _mlp_head_args(x, acts, ws, bs)
+        a.y, a.ldy = _lib.dev_ptr(y, torch.float32, "y"), y.stride(0)
+        _lib.check(_lib.lib().pna_mlp_head_fwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_mlp_head_fwd_f32")
+        ctx.acts, ctx.has_bias = acts, [b is not None for b in bs]
+        ctx.save_for_backward(x, *ws, *[b for b in bs if b is not None])
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        x, *rest = ctx.saved_tensors
+        L = len(ctx.acts)
+        ws, kept = rest[:L], list(rest[L:])
+        bs = [kept.pop(0) if has else None for has in ctx.has_bias]
+        dev, V = go.device, x.shape[0]
+        go = _gru_rows(go)                                     # (the cotangent of y.sum() is an expand: strides (0, 0))
+        need = ctx.needs_input_grad
+        a = _mlp_head_args(x, ctx.acts, ws, bs)
+        a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)
+        gx = torch.empty(V, x.shape[1], dtype=torch.float32, device=dev) if need[0] else None
+        if gx is not None:
+            a.grad_x, a.ld_gx, a.need_x = _lib.dev_ptr(gx, torch.float32, "grad_x"), gx.stride(0), 1
+        grads = []
+        for l in range(L):
+            gw = torch.empty(ws[l].shape, dtype=torch.float32, device=dev) if need[2 + 2 * l] else None
+            gb = torch.empty(ws[l].shape[0], dtype=torch.float32, device=dev) if bs[l] is not None and need[3 + 2 * l] else None
+            a.grad_w[l], a.grad_b[l] = _lib.dev_ptr(gw, torch.float32, "grad_w"), _lib.dev_ptr(gb, torch.float32, "grad_b")
+            a.need_w[l], a.need_b[l] = int(gw is not None), int(gb is not None)
+            grads += [gw, gb]
+        if any(g is not None for g in grads):
+            nbytes = _lib.lib().pna_mlp_head_workspace_bytes(V, L, a.widths)
+            a.workspace, a.workspace_bytes = _device_workspace(_mlp_ws, dev, nbytes)[1], nbytes
+        _lib.check(_lib.lib().pna_mlp_head_bwd_f32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_mlp_head_bwd_f32")
+        return (gx, None, *grads)
+
+
+def mlp_head(x, linears, acts):
+    """The head `linears` (nn.Linear modules, in order) with `acts` (one (PNA_MLP_ACT_* code, slope) per layer: functional.mlp_head_act)
+    on the rows x (V, in_features) through MlpHeadFn."""
+    params = []
+    for lin in linears:
+        params += [lin.weight, lin.bias]
+    return MlpHeadFn.apply(x, tuple(acts), *params)
+
+
 # ---- the dense-adjacency PNALayer (the multitask GNN's convolution) as one C call each way (pna_dense_layer.hip) -------------------------
 _dense_ws = {}      # device -> the backward's reusable workspace (the slabs' gradient images)
 

@@ -1280,6 +1280,76 @@ def gru_cell_workspace_bytes(V, I, Hc, hidden_size):
     return _lib.lib().pna_gru_cell_workspace_bytes(V, I, Hc, hidden_size)
 
 
+# The dense heads (nets.MLPReadout, layers.MLP without dropout and batch-norm, the superpixel net's Linear embeddings) take the one-call
+# route (autograd.MlpHeadFn: pna_mlp_head_fwd_f32 / _bwd_f32) on calls of up to this many rows.  0 = off, the default
+MLP_HEAD_ROWS = int(os.environ.get("PNA_AMD_MLP_HEAD_ROWS", "0"))
+
+
+def _mlp_head_ints(values):
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
+def mlp_head_act(act):
+    """(PNA_MLP_ACT_* code, slope) of a layer's activation -- None, nn.ReLU or nn.LeakyReLU (exact types) -- else None."""
+    if act is None:
+        return _lib.PNA_MLP_ACT_NONE, 0.0
+    if type(act) is torch.nn.ReLU:
+        return _lib.PNA_MLP_ACT_RELU, 0.0
+    if type(act) is torch.nn.LeakyReLU:
+        return _lib.PNA_MLP_ACT_LEAKY, float(act.negative_slope)
+    return None
+
+
+def mlp_head_path(x, linears, acts):
+    """Whether the head `linears` with the activation modules `acts` on x is served by pna_mlp_head_fwd_f32 / _bwd_f32 (autograd.MlpHeadFn:
+    one C call each way, train and eval, with and without grad): the knob PNA_AMD_MLP_HEAD_ROWS is on and covers the rows; x is fp32 on a
+    GPU, 2-D with unit column stride and a row pitch of at least the width, or 3-D contiguous (taken as its (B N, D) view); every layer
+    is a plain nn.Linear whose parameters are fp32 on that GPU and whose input is the layer before's output; every activation is None,
+    nn.ReLU or nn.LeakyReLU; the shape fits the call (mlp_head_fits).  No float is read."""
+    if not MLP_HEAD_ROWS > 0:
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32):
+        return False
+    if x.dim() == 3:
+        if not x.is_contiguous():
+            return False
+        V, D = x.shape[0] * x.shape[1], x.shape[2]
+    elif x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]:
+        V, D = x.shape
+    else:
+        return False
+    if not (1 <= V <= MLP_HEAD_ROWS and 1 <= len(linears) == len(acts)):
+        return False
+    widths, codes = [D], []
+    for lin, act in zip(linears, acts):
+        if type(lin) is not torch.nn.Linear or lin.in_features != widths[-1]:
+            return False
+        for p in (lin.weight, lin.bias):
+            if p is not None and not (p.is_cuda and p.dtype == torch.float32 and p.device == x.device):
+                return False
+        code = mlp_head_act(act)
+        if code is None:
+            return False
+        widths.append(lin.out_features)
+        codes.append(code[0])
+    return mlp_head_fits(widths, codes)
+
+
+def mlp_head_fits(widths, acts):
+    """Whether a head of len(acts) layers with these widths (the input's first) and activation codes (_lib.PNA_MLP_ACT_*) is inside
+    pna_mlp_head_*_f32's scope, by the entry points' own check (pna_mlp_head_in_scope)."""
+    # (the check takes the whole shape: asked at the smallest call of the scope, one row)
+    if len(widths) != len(acts) + 1:
+        return False
+    return bool(_lib.lib().pna_mlp_head_in_scope(1, len(acts), _mlp_head_ints(widths), _mlp_head_ints(acts)))
+
+
+def mlp_head_workspace_bytes(V, widths):
+    """pna_mlp_head_workspace_bytes: the backward's bytes (the hidden rows, the layers' cotangents and one image of the parameter
+    gradients per slab); -1 outside the scope."""
+    return _lib.lib().pna_mlp_head_workspace_bytes(V, len(widths) - 1, _mlp_head_ints(widths))
+
+
 # The dense-adjacency PNALayer (pna_amd.pytorch.pna.layer.PNALayer: the multitask GNN's convolution) takes the one-call route
 # (autograd.DenseLayerFn: pna_dense_layer_fwd_f32 / _bwd_f32) on calls of up to this many rows B N.  0 = off, the default (DESIGN.md 4.21)
 DENSE_LAYER_ROWS = int(os.environ.get("PNA_AMD_DENSE_LAYER_ROWS", "0"))

@@ -59,7 +59,8 @@ class FCLayer(nn.Module):
 
 
 class MLP(nn.Module):
-    """`layers` FCLayers; a single layer uses `last_activation` (models/layers.py:214-216)."""
+    """`layers` FCLayers; a single layer uses `last_activation` (models/layers.py:214-216).  With PNA_AMD_MLP_HEAD_ROWS on and the call
+    in scope (`_one_call_path`) all layers run as one C call each way (autograd.mlp_head); otherwise exactly the loop over the FCLayers."""
 
     def __init__(self, in_size, hidden_size, out_size, layers, mid_activation="relu", last_activation="none",
                  dropout=0., mid_b_norm=False, last_b_norm=False, device="cpu"):
@@ -74,7 +75,27 @@ class MLP(nn.Module):
                                                 b_norm=last_b_norm if last else mid_b_norm, device=device,
                                                 dropout=dropout))
 
+    def _one_call_path(self, x):
+        """Whether this MLP is served by pna_mlp_head_fwd_f32 / _bwd_f32 (functional.mlp_head_path on the layers' nn.Linear and
+        activation modules; a 3-D contiguous x as its (B N, D) view): additionally no layer has a batch-norm and none a dropout that
+        is active in this mode.  The knob PNA_AMD_MLP_HEAD_ROWS at 0 answers before anything is looked at."""
+        from . import functional as PF
+        if not PF.MLP_HEAD_ROWS > 0:
+            return False
+        fcs = list(self.fully_connected)
+        if any(type(fc) is not FCLayer or fc.b_norm is not None for fc in fcs):
+            return False
+        if any(fc.dropout is not None and fc.dropout.p > 0 and fc.dropout.training for fc in fcs):
+            return False
+        return PF.mlp_head_path(x, [fc.linear for fc in fcs], [fc.activation for fc in fcs])
+
     def forward(self, x):
+        if self._one_call_path(x):
+            from . import functional as PF
+            from .autograd import mlp_head
+            fcs = list(self.fully_connected)
+            y = mlp_head(x.reshape(-1, x.shape[-1]), [fc.linear for fc in fcs], [PF.mlp_head_act(fc.activation) for fc in fcs])
+            return y.reshape(*x.shape[:-1], -1)
         for fc in self.fully_connected:
             x = fc(x)
         return x

@@ -29,10 +29,33 @@ class MLPReadout(nn.Module):
                                        [nn.Linear(dims[L], output_dim, bias=True)])
         self.L = L
 
+    def _one_call_path(self, x):
+        """Whether this head is served by pna_mlp_head_fwd_f32 / _bwd_f32 (functional.mlp_head_path: the knob PNA_AMD_MLP_HEAD_ROWS on
+        and covering the rows, fp32 rows and plain nn.Linear parameters on one GPU, L + 1 <= 4 layers of widths <= 128).  The knob at
+        0 answers before anything is looked at."""
+        if not PF.MLP_HEAD_ROWS > 0:
+            return False
+        return x.dim() == 2 and PF.mlp_head_path(x, list(self.FC_layers), [_RELU] * self.L + [None])
+
     def forward(self, x):
+        if PF.MLP_HEAD_ROWS > 0 and self._one_call_path(x):
+            from . import autograd as AG
+            return AG.mlp_head(x, list(self.FC_layers), [PF.mlp_head_act(_RELU)] * self.L + [PF.mlp_head_act(None)])
         for l in range(self.L):
             x = F.relu(self.FC_layers[l](x))
         return self.FC_layers[self.L](x)
+
+
+_RELU = nn.ReLU()           # MLPReadout's F.relu as the activation module the head route's predicate reads
+
+
+def linear_rows(lin, x):
+    """lin(x) for an nn.Linear over rows (the superpixel net's embeddings): a one-layer call without activation of the head route under
+    the same knob and predicate, else torch's own."""
+    if PF.MLP_HEAD_ROWS > 0 and x.dim() == 2 and PF.mlp_head_path(x, [lin], [None]):
+        from . import autograd as AG
+        return AG.mlp_head(x, [lin], [PF.mlp_head_act(None)])
+    return lin(x)
 
 
 class GRU(nn.Module):
@@ -200,9 +223,9 @@ class PNANetSuperpixels(PF.DropsCachesOnConversion, nn.Module):
 
     def forward(self, g, h, e, snorm_n, snorm_e=None):
         graph = as_graph(g)
-        h = self.embedding_h(h)
+        h = linear_rows(self.embedding_h, h)
         if self.edge_feat:
-            e = self.embedding_e(e)
+            e = linear_rows(self.embedding_e, e)
         for i, conv in enumerate(self.layers):
             h_t = conv(graph, h, e, snorm_n)
             if self.gru_enable and i != len(self.layers) - 1:

@@ -2,7 +2,8 @@
 optional GRU shared by all of them, and two heads -- an MLP per node and a Set2Set readout per graph.  Same constructor arguments,
 assertions, attribute names (`conv_layers`, `gru`, `nodes_read_out`, `graph_read_out`) and forward as the reference, so its checkpoints load
 with strict=True.  The pieces are this package's: a `layer_type` such as pna_amd.pytorch.pna.layer.PNALayer, layers.GRU, layers.MLP and
-layers.S2SReadout, each with its one-call route behind its own knob (PNA_AMD_DENSE_LAYER_ROWS, PNA_AMD_GRU_ROWS, PNA_AMD_S2S_ROWS).
+layers.S2SReadout, each with its one-call route behind its own knob (PNA_AMD_DENSE_LAYER_ROWS, PNA_AMD_GRU_ROWS, PNA_AMD_MLP_HEAD_ROWS,
+PNA_AMD_S2S_ROWS).
 Nothing in the forward reads a float from the device, so an eval forward can be captured (capture.GraphedForward)."""
 import types
 
