@@ -984,8 +984,10 @@ int pna_project_grouped_f32(const float* x, int64_t ldx, int64_t x_rows, int32_t
  *   grad_beta = sum_r g',  grad_gamma = sum_r g' xhat,  grad_y = gamma save_invstd (g' - mean_r g' - xhat mean_r(g' xhat))
  *   (the residual's gradient is grad_out itself: the caller's)
  *
- * Two streaming passes each way (column sums, then the element-wise pass) instead of the ~10 library passes; column sums are
- * taken of y - y[0, c] in fp32 per 512 rows and in float64 across them.  M >= 2 rows (nn.BatchNorm1d raises below that: the
+ * Two streaming passes each way (column sums, then the element-wise pass) instead of the ~10 library passes; the forward's column
+ * sums are taken of y - k in fp32 over the at most 64 rows of one thread, k the median of the first three of those rows (one unusual
+ * row, or a run of them at the front, does not become the shift), and are re-based on one shift and added in float64 across the
+ * threads of a workgroup and across the workgroups, in a fixed order.  M >= 2 rows (nn.BatchNorm1d raises below that: the
  * caller's), 1 <= N <= 128, rows 4-byte aligned, ld >= N.  workspace: pna_bn_tail_workspace_bytes(M, N) bytes, no
  * initialisation needed, not kept between the two calls.
  */

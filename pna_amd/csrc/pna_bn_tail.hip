@@ -8,9 +8,14 @@
 // of y) + apply (y, residual -> out) forward; reduce (y, grad_out) + apply (y, grad_out -> grad_y) backward.  HBM-bound, no
 // reuse: rows are walked in 128-byte column strips by 32 lanes, eight rows per workgroup pass, nothing staged.
 //
-// Numerics.  Column sums are taken of d = y - K_c with K_c = y[0, c] (one shift per column for the whole tensor: the partial
-// sums of all workgroups simply add up), in fp32 over a workgroup's 512 rows and in float64 across workgroups: var = E[d^2] -
-// E[d]^2 is then free of the cancellation that the raw moments would have for a column whose mean is large against its spread.
+// Numerics.  Column sums are taken of d = y - k with a shift k of each THREAD's own: the median of the first three rows it folds (its
+// only or its second row when it has fewer), so one unusual row -- a hub node sorted to the front of the graph -- or eight of them in
+// a row cannot become the shift the way a column-wide y[0, c] would, and make every d large and var = E[d^2] - E[d]^2 cancel.  A thread
+// sums d and d^2 over its at most 64 rows in fp32; the eight row lanes of a workgroup are re-based on the first lane's shift and added
+// in float64 (sum (y - K) = sum (y - k) + n (k - K), sum (y - K)^2 = sum (y - k)^2 + 2 (k - K) sum (y - k) + n (k - K)^2), the
+// workgroup's two sums are stored as fp32 pairs (high part, remainder) beside its shift, and k_bn_finalize re-bases them on the first
+// workgroup's shift and adds them in float64 the same way.  Every order is fixed: results do not depend on the launch.  The shifted
+// sums are free of the cancellation that the raw moments would have for a column whose mean is large against its spread.
 // The ReLU mask of the backward is recomputed from y with the forward's own expression (bn_affine below), not stored.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,10 +39,14 @@ struct TArgs {
   const float* gamma; const float* beta;
   float* mean; float* invstd;                             // [N]
   float* rmean; float* rvar; float momentum; float eps;
-  float* part;                                            // [2][N][nwg] partial column sums
+  float* part;                                            // backward: [2][N][nwg] partial column sums; forward: [5][N][nwg] (kFwdPlanes)
   float* colc;                                            // [2][N]: backward: mean of g', mean of g' xhat
   float* ggamma; float* gbeta;
 };
+
+constexpr int kFwdPlanes = 5;                             // sum d (high, remainder), sum d^2 (high, remainder), the workgroup's shift
+
+__device__ __forceinline__ float med3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
 
 // z = (y - mean) (gamma invstd) + beta: the centred form (no cancellation between y a and mean a for columns of large mean)
 __device__ __forceinline__ float bn_affine(float y, float mean, float a, float b) { return __builtin_fmaf(y - mean, a, b); }
@@ -49,7 +58,7 @@ constexpr int kGroup = 4;
 
 template <bool BWD, int NJ>
 __global__ __launch_bounds__(kThreads) void k_bn_colsums(const TArgs a) {
-  __shared__ float red[2][kRowLanes][kColLanes * NJ];
+  __shared__ float red[BWD ? 2 : 3][kRowLanes][kColLanes * NJ];
   const int tx = threadIdx.x % kColLanes, ty = threadIdx.x / kColLanes;
   const long r0 = (long)blockIdx.x * kRowsPerWg, r1 = min(r0 + kRowsPerWg, a.M);
   float s0[NJ], s1[NJ], ca[NJ], cb[NJ], cm[NJ], ci[NJ];
@@ -65,7 +74,19 @@ __global__ __launch_bounds__(kThreads) void k_bn_colsums(const TArgs a) {
       ca[j] = (a.gamma ? a.gamma[cc[j]] : 1.f) * ci[j];
       cb[j] = a.beta ? a.beta[cc[j]] : 0.f;
     } else {
-      cm[j] = a.y[cc[j]]; ci[j] = 0.f;                    // the column's shift K_c = y[0, c]
+      cm[j] = 0.f; ci[j] = 0.f;                           // cm: the thread's shift, set below
+    }
+  }
+  if constexpr (!BWD) {
+    // the shift: the median of the thread's first three rows r0 + ty + 8 i (clamped to its last row: with two rows the second, with
+    // one that row; a thread without rows folds nothing and is passed over below).  A full block takes it from the first row steps it
+    // loads anyway (below): the same three rows, no load of their own.
+    const long nt = (r1 - r0 - ty + kRowLanes - 1) / kRowLanes;
+    if (nt > 0 && r1 - r0 != kRowsPerWg) {
+      const long ra = r0 + ty, rl = ra + (nt - 1) * kRowLanes;
+      const long rb = min(ra + kRowLanes, rl), rc = min(ra + 2 * kRowLanes, rl);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) cm[j] = med3(a.y[ra * a.ldy + cc[j]], a.y[rb * a.ldy + cc[j]], a.y[rc * a.ldy + cc[j]]);
     }
   }
   auto fold = [&](int j, float v, float g) __attribute__((always_inline)) {
@@ -91,6 +112,13 @@ __global__ __launch_bounds__(kThreads) void k_bn_colsums(const TArgs a) {
           g[u][j] = BWD ? a.go[r * a.ld_go + cc[j]] : 0.f;
         }
       }
+      if constexpr (!BWD) {
+        static_assert(kGroup >= 3, "the shift is the median of the first three row steps");
+        if (i == 0) {
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) cm[j] = med3(v[0][j], v[1][j], v[2][j]);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < kGroup; ++u)
 #pragma unroll
@@ -102,8 +130,31 @@ __global__ __launch_bounds__(kThreads) void k_bn_colsums(const TArgs a) {
       for (int j = 0; j < NJ; ++j) fold(j, a.y[r * a.ldy + cc[j]], BWD ? a.go[r * a.ld_go + cc[j]] : 0.f);
   }
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) { red[0][ty][tx + kColLanes * j] = s0[j]; red[1][ty][tx + kColLanes * j] = s1[j]; }
+  for (int j = 0; j < NJ; ++j) {
+    red[0][ty][tx + kColLanes * j] = s0[j]; red[1][ty][tx + kColLanes * j] = s1[j];
+    if constexpr (!BWD) red[2][ty][tx + kColLanes * j] = cm[j];
+  }
   __syncthreads();
+  if constexpr (!BWD) {
+    // one thread per column: the row lanes' sums re-based on lane 0's shift (it always has a row), in lane order, in float64
+    for (int c = threadIdx.x; c < a.N; c += kThreads) {
+      const double K = (double)red[2][0][c];
+      double S = 0.0, Q = 0.0;
+      for (int k = 0; k < kRowLanes; ++k) {
+        const long nk = (r1 - r0 - k + kRowLanes - 1) / kRowLanes;
+        if (nk <= 0) break;
+        const double n = (double)nk, dk = (double)red[2][k][c] - K, s = (double)red[0][k][c], q = (double)red[1][k][c];
+        S += s + n * dk;
+        Q += q + 2.0 * dk * s + n * dk * dk;
+      }
+      const float sh = (float)S, qh = (float)Q;
+      const long at = (long)c * a.nwg + blockIdx.x, plane = (long)a.N * a.nwg;
+      a.part[at] = sh;             a.part[plane + at] = (float)(S - (double)sh);
+      a.part[2 * plane + at] = qh; a.part[3 * plane + at] = (float)(Q - (double)qh);
+      a.part[4 * plane + at] = red[2][0][c];
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < 2 * a.N; i += kThreads) {
     const int w = i / a.N, c = i - w * a.N;
     float t = 0.f;
@@ -119,9 +170,19 @@ __global__ __launch_bounds__(kThreads) void k_bn_finalize(const TArgs a) {
   __shared__ double red[2][kThreads];
   const int c = blockIdx.x;
   double t0 = 0.0, t1 = 0.0;
+  const long plane = (long)a.N * a.nwg;
+  const float* const pc = a.part + (long)c * a.nwg;
+  const double K0 = BWD ? 0.0 : (double)pc[4 * plane];     // forward: the column's shift is the first workgroup's
   for (int b = threadIdx.x; b < a.nwg; b += kThreads) {
-    t0 += (double)a.part[((long)0 * a.N + c) * a.nwg + b];
-    t1 += (double)a.part[((long)1 * a.N + c) * a.nwg + b];
+    if constexpr (BWD) {
+      t0 += (double)pc[b];
+      t1 += (double)pc[plane + b];
+    } else {                                               // re-based on K0, like the row lanes in k_bn_colsums
+      const double n = (double)min((long)kRowsPerWg, a.M - (long)b * kRowsPerWg), dk = (double)pc[4 * plane + b] - K0;
+      const double s = (double)pc[b] + (double)pc[plane + b], q = (double)pc[2 * plane + b] + (double)pc[3 * plane + b];
+      t0 += s + n * dk;
+      t1 += q + 2.0 * dk * s + n * dk * dk;
+    }
   }
   red[0][threadIdx.x] = t0; red[1][threadIdx.x] = t1;
   __syncthreads();
@@ -140,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_finalize(const TArgs a) {
     const double md = S / M;
     double var = Q / M - md * md;                          // biased, like nn.BatchNorm1d's normalisation
     if (var < 0.0) var = 0.0;
-    const double mean = (double)a.y[c] + md;
+    const double mean = K0 + md;
     a.mean[c] = (float)mean;
     a.invstd[c] = (float)(1.0 / sqrt(var + (double)a.eps));
     if (a.rmean && a.momentum >= 0.f) {                    // running statistics: the UNBIASED variance (torch.nn.functional.batch_norm)
@@ -222,7 +283,7 @@ int fill(const pna_bn_tail_args* p, TArgs& a, bool bwd, const char* who) {
   a.res = p->residual; a.ld_res = p->ld_res; a.out = p->out; a.ld_out = p->ld_out;
   a.go = p->grad_out; a.ld_go = p->ld_go; a.gy = p->grad_y; a.ld_gy = p->ld_gy; a.ggamma = p->grad_gamma; a.gbeta = p->grad_beta;
   a.part = (float*)p->workspace;
-  a.colc = a.part + 2 * (long)p->N * nwg;
+  a.colc = a.part + kFwdPlanes * (long)p->N * nwg;
   return PNA_OK;
 }
 
@@ -251,7 +312,7 @@ int run(const TArgs& a, hipStream_t st) {
 extern "C" int64_t pna_bn_tail_workspace_bytes(int64_t M, int32_t N) {
   if (M < 1 || N <= 0) return 0;
   const int64_t nwg = (M + kRowsPerWg - 1) / kRowsPerWg;
-  return (2 * (int64_t)N * nwg + 2 * (int64_t)N) * (int64_t)sizeof(float);
+  return (kFwdPlanes * (int64_t)N * nwg + 2 * (int64_t)N) * (int64_t)sizeof(float);
 }
 
 extern "C" int pna_bn_tail_fwd_f32(const pna_bn_tail_args* p, pna_stream_t stream) {

@@ -37,7 +37,8 @@ __device__ __forceinline__ void fold_msg(float m, int e, float& s, float& q, flo
 }
 
 // One BatchNorm column from the 16-row tiles' sums of d = z - z[first row of the tile] and d^2 (part[tile][2][N]): re-based on
-// z[0, c] and added over the tiles in float64 by a workgroup of 256 threads (pna_bn_tail's shifted sums); the batch mean, 1 / sqrt of
+// z[0, c] and added over the tiles in float64 by a workgroup of 256 threads (the re-basing pna_bn_tail.hip applies to its row lanes'
+// and workgroups' sums; its shift is a median of three rows, here it is the tile's first row); the batch mean, 1 / sqrt of
 // the BIASED variance + eps, and the running statistics moved with the UNBIASED variance (torch.nn.functional.batch_norm).
 // red: double[2][256] of LDS.  rmean == NULL or momentum < 0: running statistics not kept.
 __device__ __forceinline__ void bn_finalize_column(const float* z, int N, int c, int V, const float* part, int n_part, float eps, float momentum,
