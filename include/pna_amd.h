@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_mlp_head_fwd_f32 / pna_mlp_head_bwd_f32 / pna_mlp_head_workspace_bytes / pna_mlp_head_in_scope /
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_batch_plan_i32 / pna_batch_plan_limits / pna_batch_plan_workspace_bytes / pna_batch_plan_args (every
+                                  index array of a fresh batch of small graphs -- CSR, transposed CSR, work lists, per-batch tables -- from
+                                  one call, no library sort); no existing struct or entry point changed.
+                                  23, additive: + pna_mlp_head_fwd_f32 / pna_mlp_head_bwd_f32 / pna_mlp_head_workspace_bytes / pna_mlp_head_in_scope /
                                   pna_mlp_head_args, PNA_MAX_MLP_LAYERS, PNA_MLP_MAX_WIDTH, PNA_MLP_ACT_*, PNA_MLP_SLAB_ROWS, PNA_MLP_MAX_SLABS (the dense
                                   heads of the nets: 1 to 4 Linear layers with none / ReLU / LeakyReLU over rows, one call each way); no
                                   existing struct or entry point changed.
@@ -2025,6 +2028,101 @@ int64_t pna_set2set_lds_bytes(int32_t N, int32_t D);                            
 int64_t pna_set2set_workspace_bytes(int64_t B, int32_t N, int32_t D, int32_t steps);            /* -1 outside the scope */
 int pna_set2set_fwd_f32(const pna_set2set_args* args, pna_stream_t stream);
 int pna_set2set_bwd_f32(const pna_set2set_args* args, pna_stream_t stream);
+
+/* ---- The batch plan: every index array a fresh batch of small graphs needs, one call ---------------------------------------------------
+ * replaces: realworld_benchmark/data/molecules.py:153-164 (dgl.batch of the members and the snorm_n column) and what pna_amd built
+ * from it lazily, array by array: Graph.collate_flat (pna_amd/graph.py: the node offsets, the global edge ids, pna_collate_csr_i32's radix
+ * sort, the max-degree read), Graph.work_items / heavy_schedule / edge_ids32 / snorm_n / degree_scalers, nets._readout_offsets, and
+ * autograd._transposed_whole_rows with _TowerTrainPlan's pos_t (pna_amd/autograd.py: a second Graph, a second sort, rank_t, items_t).
+ *
+ * Input: the members' edge lists with LOCAL node ids one after the other (src_local / dst_local [E]) and the members' edge and node counts
+ * ON THE DEVICE (edge_count / node_count [B]).  Member g owns the node range [noff_g, noff_g + n_g) and the edge range [eoff_g, eoff_g +
+ * e_g) of the batch; the rows of its nodes in the destination-sorted CSR lie exactly in its edge range, and so do its rows of the
+ * transposed CSR.  No global sort is needed: every array below is produced member by member out of LDS.
+ *
+ * Three launches at most, no library sort, nothing waits for the device:
+ *   (1) one workgroup scans the B counts into node and edge offsets (workspace; readout_offsets is the node scan), cuts the members
+ *       into GROUPS of consecutive members and initialises `record`.  A member above 256 nodes or 1 024 edges is a group of its own;
+ *       smaller consecutive members share a group while their first node stays in one window of 256 nodes, their first edge in one
+ *       window of 1 024 edges and their index in one window of 128 members -- so a group of small members spans fewer than 512 nodes and
+ *       2 048 edges and there are at most 1 + 3 (V / 256 + E / 1 024) + B / 128 groups (the grid; surplus workgroups return at once).
+ *   (2) one 256-thread workgroup per group.  A group is a block of the batch's block-diagonal adjacency, so it is sorted as ONE small
+ *       graph: each of the four wavefronts takes a quarter of the group's edges in the caller's order and counts its edges per
+ *       destination (an integer LDS add: a count does not depend on arrival order); a scan over the group's nodes gives rowptr and,
+ *       per wavefront and destination, the first free position; then every wavefront walks its quarter IN ORDER, 64 edges a step,
+ *       and an edge's position is that base plus the number of LOWER lanes of the step with the same destination (64 lane reads), the
+ *       last such lane storing the new base.  No position depends on the arrival order of an atomic: edges of one destination keep the
+ *       caller's order (DGL's mailbox order, what pna_collate_csr_i32's stable radix sort gives).  With want_transposed the same
+ *       walk runs once more over the CSR positions with the source as key: the transposed CSR, stable in the forward CSR's order.
+ *       No workgroup reads what another workgroup of the launch wrote; offsets cross from launch (1) only.
+ *   (3) is not needed.
+ * Every local id is checked against its member's n_g BEFORE it indexes anything: an id outside [0, n_g) sets bit 0 of record[2] and its
+ * edge is written nowhere (its CSR slot at the end of the member's range, and src / dst of that edge, keep what they held); every other
+ * member's arrays are what they would be without it.  Bit 1 of record[2]: a negative count, counts that do not add up to V and E (then
+ * nothing is planned), or a member larger than member_nodes_max / member_edges_max declared (that group is skipped).  The call never
+ * faults on bad input.
+ *
+ * Outputs, each nullable (NULL = not written):
+ *   src, dst int64 [E]            global ids (Graph.src / .dst)
+ *   rowptr [V + 1], col, row, eid [E] int32, eid64 int64 [E]   the destination-sorted CSR (CSR.eid and Graph.edge_ids32())
+ *   items [V, 4]                  {row, beg, end, -1}: Graph.work_items() of a batch without heavy rows, natural order
+ *   readout_offsets [B + 1]       the members' node ranges
+ *   snorm_n fp32 [V]              sqrt(1 / n_g): one IEEE division, one IEEE square root (data/molecules.py:157-159)
+ *   amp, att fp32 [V]             with avg_log > 0: pna_degree_scalers_f32's values from the same device function
+ *   with want_transposed: rowptr_t [V + 1], col_t [E] (the destination of every out-edge), row_t [E], pos_t [E] (the position of every
+ *   transposed edge in the forward CSR) and pos_t64, rank_t [E] = pos_t - rowptr[col_t], items_t [V, 4], row64 / col64 int64 [E] (row
+ *   and col once more as the transposed graph's edge list)
+ *   record int32 [4], required    {max in-degree, max out-degree (0 without want_transposed), status, 0}
+ * Scope (PNA_E_INVALID outside it, pna_last_error names the clause, nothing is launched; pna_batch_plan_workspace_bytes returns -1):
+ * 1 <= B, 0 <= E, V < 2^31, and member_nodes_max / member_edges_max -- the caller's HOST knowledge of its largest member, which the
+ * launch's LDS is sized by -- inside pna_batch_plan_limits.  The limits are what one workgroup's LDS holds: 4 (2 e + 7 n + 3) bytes for
+ * a group of n nodes and e edges (two CSR columns, four wavefronts' counters and three scans), 122 892 of the 160 KiB at 2 048 nodes
+ * and 8 192 edges.  workspace: 4 (3 (B + 1) + 4) bytes rounded up to 256, no initialisation. */
+typedef struct pna_batch_plan_args {
+  uint32_t struct_size;    /* sizeof(pna_batch_plan_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const int32_t* src_local;      /* [E] */
+  const int32_t* dst_local;      /* [E] */
+  const int32_t* edge_count;     /* [B], device */
+  const int32_t* node_count;     /* [B], device */
+  int32_t B;
+  int32_t E;
+  int32_t V;
+  int32_t want_transposed;       /* 0 / 1 */
+  int32_t member_nodes_max;      /* host: no member has more nodes / edges than this (<= pna_batch_plan_limits) */
+  int32_t member_edges_max;
+  float avg_log;                 /* <= 0: no scalers */
+  int32_t _pad0;
+  int64_t* src;
+  int64_t* dst;
+  int32_t* rowptr;
+  int32_t* col;
+  int32_t* row;
+  int32_t* eid;
+  int64_t* eid64;
+  int32_t* items;
+  int32_t* readout_offsets;
+  float* snorm_n;
+  int32_t* rowptr_t;
+  int32_t* col_t;
+  int32_t* row_t;
+  int32_t* pos_t;
+  int64_t* pos_t64;
+  int32_t* rank_t;
+  int32_t* items_t;
+  int64_t* row64;
+  int64_t* col64;
+  float* amp;
+  float* att;
+  int32_t* record;
+  void* workspace;
+  int64_t workspace_bytes;
+} pna_batch_plan_args;
+
+/* Host only, callable without a GPU: the largest member (nodes, edges) one workgroup's share of the LDS holds.  Returns PNA_OK. */
+int pna_batch_plan_limits(int32_t* max_member_nodes, int32_t* max_member_edges);
+int64_t pna_batch_plan_workspace_bytes(int32_t B, int64_t E, int64_t V);                          /* -1 outside the scope */
+int pna_batch_plan_i32(const pna_batch_plan_args* args, pna_stream_t stream);
 
 const char* pna_last_error(void);
 int pna_abi_version(void);

@@ -477,6 +477,22 @@ class PnaSet2setArgs(_Args):
     ]
 
 
+class PnaBatchPlanArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
+        ("src_local", ctypes.c_void_p), ("dst_local", ctypes.c_void_p), ("edge_count", ctypes.c_void_p), ("node_count", ctypes.c_void_p),
+        ("B", ctypes.c_int32), ("E", ctypes.c_int32), ("V", ctypes.c_int32), ("want_transposed", ctypes.c_int32),
+        ("member_nodes_max", ctypes.c_int32), ("member_edges_max", ctypes.c_int32), ("avg_log", ctypes.c_float), ("_pad0", ctypes.c_int32),
+        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+        ("rowptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("row", ctypes.c_void_p), ("eid", ctypes.c_void_p), ("eid64", ctypes.c_void_p),
+        ("items", ctypes.c_void_p), ("readout_offsets", ctypes.c_void_p), ("snorm_n", ctypes.c_void_p),
+        ("rowptr_t", ctypes.c_void_p), ("col_t", ctypes.c_void_p), ("row_t", ctypes.c_void_p), ("pos_t", ctypes.c_void_p),
+        ("pos_t64", ctypes.c_void_p), ("rank_t", ctypes.c_void_p), ("items_t", ctypes.c_void_p), ("row64", ctypes.c_void_p), ("col64", ctypes.c_void_p),
+        ("amp", ctypes.c_void_p), ("att", ctypes.c_void_p), ("record", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -677,6 +693,12 @@ def lib():
         for fn in (L.pna_set2set_fwd_f32, L.pna_set2set_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaSet2setArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
+        L.pna_batch_plan_limits.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        L.pna_batch_plan_limits.restype = ctypes.c_int
+        L.pna_batch_plan_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]
+        L.pna_batch_plan_workspace_bytes.restype = ctypes.c_int64
+        L.pna_batch_plan_i32.argtypes = [ctypes.POINTER(PnaBatchPlanArgs), ctypes.c_void_p]
+        L.pna_batch_plan_i32.restype = ctypes.c_int
         if L.pna_abi_version() != PNA_ABI_VERSION:
             raise RuntimeError(f"libpna_amd.so ABI {L.pna_abi_version()} != binding {PNA_ABI_VERSION}: rebuild")
         _lib = L

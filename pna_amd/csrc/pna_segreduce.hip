@@ -28,6 +28,7 @@
 #include "pna_amd.h"
 #include "pna_internal.h"
 #include "pna_rowstats.h"
+#include "pna_scalers_dev.h"
 
 namespace {
 
@@ -827,12 +828,8 @@ __global__ void k_degree_scalers(const int32_t* rowptr, int V, float avg_log, fl
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= V) return;
   const int d = rowptr[v + 1] - rowptr[v];
-  float fa = 0.f, ft = 0.f;
-  if (d > 0) {
-    const float lg = (float)log((double)d + 1.0);          // np.log(D + 1) in float64, then fp32
-    fa = inv_avg * lg;                                     // avg.reciprocal() * scalar
-    ft = avg_log / lg;                                     // avg / scalar
-  }
+  float fa, ft;
+  pna_degree_scalers_row(d, avg_log, inv_avg, fa, ft);     // (pna_scalers_dev.h: shared with the batch plan)
   if (amp) amp[v] = fa;
   if (att) att[v] = ft;
 }

@@ -9,6 +9,7 @@ installed.  All index preparation is torch tensor ops on whatever device the edg
 (testable on CPU); only `degree_scalers` and the layers themselves need the GPU library.
 """
 import ctypes
+import os
 from typing import NamedTuple, Optional
 
 import torch
@@ -20,6 +21,11 @@ from . import _lib
 # (tools/sweep.py [removed in round 5: git history], profiles/).
 HEAVY_THRESHOLD = 128
 SEG_LEN = 128
+
+# Batches of at most this many nodes that Graph.collate_flat / Graph.collate build on the GPU from host-side counts are planned by ONE C
+# call (pna_batch_plan_i32: CSR, transposed CSR, work lists, snorm_n, readout offsets, degree scalers -- DESIGN.md 4.26) and every
+# lazy property finds its array already seated.  0 = off (the default): every array keeps the construction it has.
+BATCH_PLAN_ROWS = int(os.environ.get("PNA_AMD_BATCH_PLAN_ROWS", "0"))
 
 
 class CSR(NamedTuple):
@@ -101,6 +107,128 @@ def build_heavy_schedule(rowptr, max_degree, threshold=None, seg_len=None):
                          heavy.to(torch.int32), segptr.to(torch.int32), seg_heavy.to(torch.int32))
 
 
+def batch_plan_limits():
+    """(max_member_nodes, max_member_edges) of pna_batch_plan_i32, asked of the library (a host function: no GPU needed)."""
+    n, e = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.lib().pna_batch_plan_limits(ctypes.byref(n), ctypes.byref(e)), "pna_batch_plan_limits")
+    return n.value, e.value
+
+
+def _host_counts(x):
+    """The counts as a list of ints when they live on the host (a sequence or a CPU tensor), else None: no device read."""
+    if torch.is_tensor(x):
+        return None if x.is_cuda or x.dim() != 1 else [int(v) for v in x.tolist()]
+    try:
+        return [int(v) for v in x]
+    except TypeError:
+        return None
+
+
+def _host_avg_log(avg_d):
+    """avg_d (a float, or the nets' dict with a host `log`) as the Python float Graph.degree_scalers is keyed by, else None."""
+    if avg_d is None:
+        return None
+    t = avg_d.get("log") if isinstance(avg_d, dict) else avg_d
+    if t is None or (torch.is_tensor(t) and (t.is_cuda or t.numel() != 1)):
+        return None
+    v = float(t)
+    return v if v > 0.0 else None
+
+
+def _carve(buf, sizes):
+    """Consecutive views of `buf` with the given element counts, each starting on a 256-byte boundary."""
+    per = 256 // buf.element_size()
+    out, o = [], 0
+    for n in sizes:
+        out.append(buf[o:o + n])
+        o += (n + per - 1) // per * per
+    return out
+
+
+def _carve_total(sizes, itemsize):
+    per = 256 // itemsize
+    return sum((n + per - 1) // per * per for n in sizes)
+
+
+def _collate_planned(src, dst, edge_counts, num_nodes, dev, train, avg_d):
+    """collate_flat through pna_batch_plan_i32, or None when the batch is outside that route (Graph.collate_flat then builds it as
+    before).  The results are seated where the lazy constructions put theirs, under their keys."""
+    sizes_host, counts_host = _host_counts(num_nodes), _host_counts(edge_counts)
+    if sizes_host is None or counts_host is None:
+        return None
+    B, V, E = len(sizes_host), sum(sizes_host), int(src.numel())
+    if len(counts_host) != B or sum(counts_host) != E or dst.numel() != E or src.dim() != 1:
+        raise ValueError("collate_flat: edge_counts / num_nodes do not describe the edge arrays")
+    if B < 1 or V > BATCH_PLAN_ROWS or V >= 2 ** 31 or E >= 2 ** 31 or min(sizes_host) < 0 or min(counts_host) < 0:
+        return None
+    lim_n, lim_e = batch_plan_limits()
+    n_max, e_max = max(sizes_host), max(counts_host)
+    if n_max > lim_n or e_max > lim_e:
+        return None
+    L = _lib.lib()
+    i32 = lambda t: (t if t.is_cuda else t.to(torch.int32)).to(device=dev, dtype=torch.int32).contiguous()   # noqa: E731
+    src32, dst32 = i32(src), i32(dst)
+    dev = src32.device                                          # (with its index: the key nets._readout_offsets looks under)
+    counts = torch.tensor([counts_host, sizes_host], dtype=torch.int32).to(dev)
+    avg_log = _host_avg_log(avg_d)
+    ws_ints = L.pna_batch_plan_workspace_bytes(B, E, V) // 4
+    n_i = [V + 1, E, E, E, 4 * V, B + 1, 4, ws_ints] + ([V + 1, E, E, E, E, 4 * V] if train else [])
+    n_l = [E, E, E] + ([E, E, E] if train else [])
+    n_f = [V] + ([V, V] if avg_log is not None else [])
+    ibuf = torch.empty(_carve_total(n_i, 4), dtype=torch.int32, device=dev)
+    lbuf = torch.empty(_carve_total(n_l, 8), dtype=torch.int64, device=dev)
+    fbuf = torch.empty(_carve_total(n_f, 4), dtype=torch.float32, device=dev)
+    iv, lv, fv = _carve(ibuf, n_i), _carve(lbuf, n_l), _carve(fbuf, n_f)
+    rowptr, col, row, eid, items, readout, record, ws = iv[:8]
+    a = _lib.PnaBatchPlanArgs()
+    p = lambda t: t.data_ptr() if t.numel() else None           # noqa: E731
+    a.src_local, a.dst_local, a.edge_count, a.node_count = p(src32), p(dst32), counts[0].data_ptr(), counts[1].data_ptr()
+    a.B, a.E, a.V, a.want_transposed, a.member_nodes_max, a.member_edges_max = B, E, V, int(bool(train)), n_max, e_max
+    a.avg_log = avg_log if avg_log is not None else 0.0
+    a.src, a.dst, a.eid64 = p(lv[0]), p(lv[1]), p(lv[2])
+    a.rowptr, a.col, a.row, a.eid, a.items = rowptr.data_ptr(), p(col), p(row), p(eid), p(items)
+    a.readout_offsets, a.snorm_n, a.record = readout.data_ptr(), p(fv[0]), record.data_ptr()
+    if train:
+        rowptr_t, col_t, row_t, pos_t, rank_t, items_t = iv[8:]
+        a.rowptr_t, a.col_t, a.row_t, a.pos_t, a.rank_t, a.items_t = rowptr_t.data_ptr(), p(col_t), p(row_t), p(pos_t), p(rank_t), p(items_t)
+        a.pos_t64, a.row64, a.col64 = p(lv[3]), p(lv[4]), p(lv[5])
+    if avg_log is not None:
+        a.amp, a.att = p(fv[1]), p(fv[2])
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws_ints * 4
+    _lib.check(L.pna_batch_plan_i32(ctypes.byref(a), _lib.stream_ptr(dev)), "pna_batch_plan_i32")
+    for t in (src32, dst32, counts):
+        t.record_stream(torch.cuda.current_stream(dev))
+    max_in, max_out, status, _ = record.tolist()                # the batch's one host read
+    if status & 1:
+        raise ValueError("collate_flat: an edge names a node outside its member graph (a local id outside [0, num_nodes[i]))")
+    if status:
+        raise ValueError("collate_flat: edge_counts / num_nodes do not describe the edge arrays")
+    g = Graph(lv[0], lv[1], V, sizes_host)
+    g._csr = CSR(rowptr, col, lv[2], row, max_in)
+    g._heavy[("eid32",)] = eid
+    ok = min(sizes_host) >= 1
+    g._heavy[("readout_offsets", dev)] = readout if ok else None
+    g._snorm_n = fv[0].unsqueeze(1)
+    if avg_log is not None:
+        g._scalers[avg_log] = (fv[1], fv[2])
+
+    def seat_items(gr, threshold, its):
+        gr._heavy[(threshold, SEG_LEN)] = HeavySchedule(threshold, SEG_LEN, 0, 0, None, None, None)
+        gr._heavy[("items", threshold, SEG_LEN, "natural", 96)] = its
+
+    if max_in <= HEAVY_THRESHOLD:
+        seat_items(g, HEAVY_THRESHOLD, items.view(V, 4))
+    if train:
+        gT = Graph(lv[4], lv[5], V)                             # edge (v -> u): pulls row v into u (autograd._transposed_whole_rows)
+        gT._csr = CSR(rowptr_t, col_t, lv[3], row_t, max_out)
+        seat_items(gT, 1 << 30, items_t.view(V, 4))
+        if max_out <= HEAVY_THRESHOLD:
+            seat_items(gT, HEAVY_THRESHOLD, items_t.view(V, 4))
+        gT._pna_amd_rank_t, gT._pna_amd_pos_t = rank_t, pos_t
+        g._pna_amd_transposed = gT
+    return g
+
+
 class Graph:
     """Directed multigraph: edge k goes src[k] -> dst[k]; messages flow along edges and are reduced at dst."""
 
@@ -168,10 +296,11 @@ class Graph:
         return Graph(torch.cat(srcs), torch.cat(dsts), offs, sizes)
 
     @staticmethod
-    def collate(srcs, dsts, num_nodes_list, device=None):
+    def collate(srcs, dsts, num_nodes_list, device=None, train=False, avg_d=None):
         """dgl.batch of edge lists with LOCAL node ids, on the device: one concatenation, then the member-graph
         offsets are applied inside the CSR build (pna_collate_csr_i32) -- data/molecules.py:153-164 without the
-        per-graph host work.  Returns the batched Graph (global ids in .src/.dst, CSR already built)."""
+        per-graph host work.  Returns the batched Graph (global ids in .src/.dst, CSR already built).  `train` / `avg_d`: see
+        collate_flat."""
         # one conversion and ONE concatenation per side (on the host when the members live there: a single copy to the device),
         # then the flat path.  What remains is the caller's data layout: concatenating 2 x 2048 small host tensors costs ~3.5 ms of
         # the 4.1 ms this takes for a 2048-molecule batch; a data set stored as one edge array + counts uses collate_flat (0.5 ms)
@@ -180,17 +309,25 @@ class Graph:
         counts = torch.tensor([t.numel() for t in ss], dtype=torch.long)
         src = torch.cat(ss) if ss else torch.zeros(0, dtype=torch.long)
         dst = torch.cat(dd) if dd else torch.zeros(0, dtype=torch.long)
-        return Graph.collate_flat(src, dst, counts, [int(n) for n in num_nodes_list], device=device if device is not None else src.device)
+        return Graph.collate_flat(src, dst, counts, [int(n) for n in num_nodes_list], device=device if device is not None else src.device,
+                                  train=train, avg_d=avg_d)
 
     @staticmethod
-    def collate_flat(src_local, dst_local, edge_counts, num_nodes, device=None):
+    def collate_flat(src_local, dst_local, edge_counts, num_nodes, device=None, train=False, avg_d=None):
         """The same batch from FLAT arrays -- what a data set stored as one edge array + per-graph counts hands over after one
         gather of the batch's members: `src_local` / `dst_local` = the members' edge lists with LOCAL node ids, one after the
         other; `edge_counts[i]` / `num_nodes[i]` = edges / nodes of member i (tensors or sequences).  No per-graph Python work
         (collate() concatenates 2 x B small tensors and sizes them one by one: 4.3 ms for 2048 molecules, this path ~0.5 ms):
-        offsets, the CSR and the global ids are built by tensor ops and pna_collate_csr_i32 on the device."""
+        offsets, the CSR and the global ids are built by tensor ops and pna_collate_csr_i32 on the device.
+        With BATCH_PLAN_ROWS covering the batch, a GPU target and HOST-side counts, one pna_batch_plan_i32 call builds those and every
+        derived array the layers ask the graph for (`train`: also the transposed graph of the one-call training backwards; `avg_d`: a
+        float or a dict with a host `log` seats the degree scalers too) -- the same arrays under the same keys, one host read."""
         src = torch.as_tensor(src_local)
         dev = torch.device(device) if device is not None else src.device
+        if BATCH_PLAN_ROWS > 0 and dev.type == "cuda":
+            g = _collate_planned(src, torch.as_tensor(dst_local), edge_counts, num_nodes, dev, train, avg_d)
+            if g is not None:
+                return g
         src = src.to(dev)
         dst = torch.as_tensor(dst_local).to(dev)
         sizes_host = [int(n) for n in (num_nodes.tolist() if torch.is_tensor(num_nodes) else num_nodes)]
