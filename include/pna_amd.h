@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_batch_plan_i32 / pna_batch_plan_limits / pna_batch_plan_workspace_bytes / pna_batch_plan_args (every
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_aggr_train_fwd_f32 / pna_tower_aggr_train_bwd_f32 / pna_tower_aggr_train_workspace_bytes /
+                                  pna_tower_aggr_train_args (the one-call tower training routes for any 1-4 distinct aggregators out of mean,
+                                  sum, max, min, std, var, with or without edge features and dropout); no existing struct or entry point changed.
+                                  23, additive: + pna_batch_plan_i32 / pna_batch_plan_limits / pna_batch_plan_workspace_bytes / pna_batch_plan_args (every
                                   index array of a fresh batch of small graphs -- CSR, transposed CSR, work lists, per-batch tables -- from
                                   one call, no library sort); no existing struct or entry point changed.
                                   23, additive: + pna_mlp_head_fwd_f32 / pna_mlp_head_bwd_f32 / pna_mlp_head_workspace_bytes / pna_mlp_head_in_scope /
@@ -1652,6 +1655,50 @@ typedef struct pna_tower_drop_args {
 int pna_tower_drop_train_fwd_f32(const pna_tower_drop_args* args, pna_stream_t stream);
 int pna_tower_drop_train_bwd_f32(const pna_tower_drop_args* args, pna_stream_t stream);
 int pna_dropout_mask_f32(float* out, int64_t ld, int64_t V, int32_t C, float p, uint64_t seed, uint64_t offset, pna_stream_t stream);
+
+/* ---- The three calls above for ANY LIST OF AGGREGATORS: forward and backward as ONE call each ------------------------------------
+ * replaces: models/dgl/aggregators.py:6-26, 50-51 (mean, max, min, std, var, sum) under models/dgl/pna_layer.py:55-76, 130-145 in train
+ * mode, and what autograd derives from them, for a layer whose towers aggregate with 1 to 4 DISTINCT aggregators out of those six in any
+ * order: the MPNN rows of realworld_benchmark/README.md:54 and :91-100 (--aggregators="sum" or "max", --scalers="identity") and every
+ * aggregator ablation.  Write A for n_aggr.  The scope is the base call's in everything else (4 <= Fi <= 128, n_tower Fi <= 512,
+ * n_tower Fo <= 128, 1-3 scalers, V >= 2, edge_dim 1..64, 0 <= p < 1); since A <= 4 no tile or saved tensor is larger than the base's.
+ *
+ * Differences to the base call: a is (V, T A Fi), per tower the listed blocks in list order; w_post[t] and grad_w_post[t] are
+ * (Fo, (1 + A n_scaler) Fi); argmax is required only when max is listed, argmin only when min is (each may be NULL otherwise); col_t /
+ * rank_t are not read; the workspace has pna_tower_aggr_train_workspace_bytes(...) bytes.
+ *
+ * Statistics of row v with in-degree D > 0 (every listed block of a row without in-edges is 0).  The messages are formed and folded as in
+ * the base call, m = (x_src[u] + x_dst[v]) [+ x_edge[k]] in CSR order; mean, max, min, std and the arg indices are the base call's bits;
+ * sum is the fold's own sum of m; var = relu(E[m0^2] - E[m0]^2) of m0 = x_src[u] [+ x_edge[k]], the message without the destination term
+ * (the std's radicand before + 1e-5; a shift does not change a variance); row_mean = E[m0], written when it is required.
+ * Backward, one tower column, CSR edge k, only listed terms:
+ *   mean0 = row_mean[v] when it was saved, else mean[v] - x_dst[v]
+ *   dm[k] = (G_mean / D + G_sum) + ([std^2 - 1e-5 > 0] G_std / (std D) + [var > 0] 2 G_var / D) (m0[k] - mean0)
+ *           + [k = argmax[v]] G_max + [k = argmin[v]] G_min
+ *   gx_dst[v] = G_mean + D G_sum + G_max + G_min (0 when D == 0), gx_src[u] = sum of dm[pos_t[j]] over u's whole-row record of items_t in
+ *   list order -- the per-edge formulation of pna_tower_edge_train_bwd_f32, with or without edge features (without them no copy of e, no
+ *   grad_e, no W_e gradient).  Everything else is the base backward with K = A Fi.  No float atomics; repeated calls give identical bits.
+ * With {mean, max, min, std} the forward's out and saved tensors, and with edge features every gradient, are the bits of the three
+ * calls above.  PNA_E_INVALID: n_aggr outside 1..4, a repeated code, a code above PNA_AGG_VAR, a missing row_mean / argmax / argmin /
+ * pos_t (pos_t: backward with E > 0 and edge == NULL), inconsistent blocks, a short struct or workspace, and whatever the base refuses. */
+typedef struct pna_tower_aggr_train_args {
+  uint32_t struct_size;    /* sizeof(pna_tower_aggr_train_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const pna_tower_train_args* base;        /* with the differences above */
+  const pna_tower_edge_train_args* edge;   /* NULL, or edge->base == base */
+  const pna_tower_drop_args* drop;         /* NULL, or drop->base == base and drop->edge == edge */
+  int32_t n_aggr;                          /* 1..4 */
+  int32_t aggr[PNA_MAX_AGGR];              /* distinct codes PNA_AGG_MEAN .. PNA_AGG_VAR, the layer's order */
+  int32_t _pad0;
+  float* row_mean;                         /* saved (V, T Fi): the mean of the variance's message; required iff std or var is listed and mean
+                                              is not, else may be NULL */
+  const int32_t* pos_t;                    /* backward, when edge == NULL: [E] CSR position of transposed edge j */
+} pna_tower_aggr_train_args;
+
+int64_t pna_tower_aggr_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input,
+                                             int32_t edge_dim /* 0 = none */, int32_t n_aggr, const int32_t* aggr);   /* -1 outside the scope */
+int pna_tower_aggr_train_fwd_f32(const pna_tower_aggr_train_args* args, pna_stream_t stream);
+int pna_tower_aggr_train_bwd_f32(const pna_tower_aggr_train_args* args, pna_stream_t stream);
 
 /* ---- The two ENDS of the molecule nets: the sum of embedding tables and the per-graph readout, one call each way ----------------
  * replaces: ogb's AtomEncoder as nets/HIV_graph_classification/pna_net.py:42 calls it (a sum of nine nn.Embedding lookups), the single

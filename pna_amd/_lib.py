@@ -390,6 +390,14 @@ class PnaTowerDropArgs(_Args):
     ]
 
 
+class PnaTowerAggrTrainArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32), ("base", ctypes.c_void_p), ("edge", ctypes.c_void_p),
+        ("drop", ctypes.c_void_p), ("n_aggr", ctypes.c_int32), ("aggr", ctypes.c_int32 * PNA_MAX_AGGR), ("_pad0", ctypes.c_int32),
+        ("row_mean", ctypes.c_void_p), ("pos_t", ctypes.c_void_p),
+    ]
+
+
 class PnaEmbedSumArgs(_Args):
     _fields_ = [
         ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
@@ -653,6 +661,11 @@ def lib():
             fn.restype = ctypes.c_int
         for fn in (L.pna_tower_drop_train_fwd_f32, L.pna_tower_drop_train_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaTowerDropArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_tower_aggr_train_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 7 + [ctypes.POINTER(ctypes.c_int32)]
+        L.pna_tower_aggr_train_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_tower_aggr_train_fwd_f32, L.pna_tower_aggr_train_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaTowerAggrTrainArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         L.pna_dropout_mask_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                            ctypes.c_void_p]

@@ -831,32 +831,41 @@ class _TowerTrainPlan(_GraphScratchPlan):
     """What one call of the three tower training Functions needs besides the layer's tensors: the transposed graph's arrays and the
     call's workspace.  Nothing here depends on weight values.  edge_dim > 0: the plan of a layer with edge features
     (pna_tower_edge_train_*_f32) -- its larger workspace, the int32 edge ids and the transposed edges' CSR positions (both kept on the
-    graph), x_edge in the saved state."""
+    graph), x_edge in the saved state.  aggr: the plan of pna_tower_aggr_train_*_f32 -- the layer's aggregator codes in its order (A of
+    them: a, the posttrans weight's gradient and the workspace are sized by A; None = mean max min std, A = 4); its backward is the
+    per-edge one, so it holds pos_t also without edge features, and the saved state ends with row_mean (V, T Fi)."""
 
-    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev, edge_dim=0):
+    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev, edge_dim=0, aggr=None):
         V, E = graph.num_nodes, int(graph.csr.col.numel())
         self.V, self.E, self.T, self.Fi, self.Fo, self.S, self.div, self.dev = V, E, T, Fi, Fo, S, bool(divide_input), dev
         self.edge_dim = int(edge_dim)
+        self.aggr = None if aggr is None else tuple(int(c) for c in aggr)
+        self.A = 4 if aggr is None else len(self.aggr)
         self.col_t, self.rank_t, self.items_t = _transposed_whole_rows(graph)
         if self.edge_dim:
-            nbytes = _lib.lib().pna_tower_edge_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div), self.edge_dim)
             self.eid = graph.edge_ids32()
+        if self.aggr is not None:
+            nbytes = _lib.lib().pna_tower_aggr_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div), self.edge_dim, self.A,
+                                                                     (ctypes.c_int32 * self.A)(*self.aggr))
+        elif self.edge_dim:
+            nbytes = _lib.lib().pna_tower_edge_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div), self.edge_dim)
+        else:
+            nbytes = _lib.lib().pna_tower_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div))
+        if self.edge_dim or self.aggr is not None:                # the per-edge backward
             gT = graph._pna_amd_transposed
             self.pos_t = getattr(gT, "_pna_amd_pos_t", None)      # position of every transposed edge in the forward CSR
             if self.pos_t is None:
                 self.pos_t = gT._pna_amd_pos_t = gT.csr.eid.to(torch.int32).contiguous()
-        else:
-            nbytes = _lib.lib().pna_tower_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div))
         if nbytes < 0:
             raise RuntimeError("TowerLayerSmallTrainFn: shape outside pna_tower_train_*_f32 (the layer checks it before taking this path)")
         self.take_workspace(graph, nbytes)
 
     def new_saved(self):
-        """The state one forward leaves for its backward -- x_cat (V, 2 T Fi) | a (V, T 4 Fi) | z (V, C) | p (V, C) | save_mean,
-        save_invstd [C] in one buffer, argmax | argmin (V, T Fi) in another.  Per CALL, not per plan: two layers of one shape on one
-        graph are both alive until their backwards."""
+        """The state one forward leaves for its backward -- x_cat (V, 2 T Fi) | a (V, T A Fi) | z (V, C) | p (V, C) | save_mean,
+        save_invstd [C] [| x_edge (E, T Fi)] [| row_mean (V, T Fi)] in one buffer, argmax | argmin (V, T Fi) in another.  Per CALL, not
+        per plan: two layers of one shape on one graph are both alive until their backwards."""
         V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
-        fbuf = torch.empty(V * 6 * TFi + 2 * V * C + 2 * C + (self.E * TFi if self.edge_dim else 0), dtype=torch.float32, device=self.dev)
+        fbuf = torch.empty(self._float_end() + (V * TFi if self.aggr is not None else 0), dtype=torch.float32, device=self.dev)
         ibuf = torch.empty(2, V, TFi, dtype=torch.int32, device=self.dev)
         return fbuf, ibuf
 
@@ -864,18 +873,47 @@ class _TowerTrainPlan(_GraphScratchPlan):
         """(x_cat, a, z, p, stats (2, C), argmax, argmin) of a saved state."""
         fbuf, ibuf = saved
         V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
-        cuts = [V * 2 * TFi, V * 4 * TFi, V * C, V * C, 2 * C]
+        cuts = [V * 2 * TFi, V * self.A * TFi, V * C, V * C, 2 * C]
         parts, o = [], 0
         for n in cuts:
             parts.append(fbuf[o:o + n])
             o += n
-        return (parts[0].view(V, 2 * TFi), parts[1].view(V, 4 * TFi), parts[2].view(V, C), parts[3].view(V, C), parts[4].view(2, C), ibuf[0], ibuf[1])
+        return (parts[0].view(V, 2 * TFi), parts[1].view(V, self.A * TFi), parts[2].view(V, C), parts[3].view(V, C), parts[4].view(2, C), ibuf[0], ibuf[1])
 
     def x_edge(self, saved):
         """The (E, T Fi) x_edge of an edge plan's saved state (behind the pieces views() returns)."""
         V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
-        o = V * 6 * TFi + 2 * V * C + 2 * C
+        o = V * (2 + self.A) * TFi + 2 * V * C + 2 * C
         return saved[0][o:o + self.E * TFi].view(self.E, TFi)
+
+    def _float_end(self):
+        """Where the pieces views() and x_edge() return end in the float buffer of a saved state."""
+        V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
+        return V * (2 + self.A) * TFi + 2 * V * C + 2 * C + (self.E * TFi if self.edge_dim else 0)
+
+    def row_mean(self, saved):
+        """The (V, T Fi) row_mean of an aggregator-list plan's saved state (the last piece)."""
+        o, n = self._float_end(), self.V * self.T * self.Fi
+        return saved[0][o:o + n].view(self.V, self.T * self.Fi)
+
+    def aggr_args(self, base, edge, key, saved, backward=False):
+        """The pna_tower_aggr_train_args around `base`, `edge` (or None) and the mask key (p, seed, offset) (or None)."""
+        r = _lib.PnaTowerAggrTrainArgs()
+        r.base = ctypes.cast(ctypes.pointer(base), ctypes.c_void_p)
+        drop = None
+        if edge is not None:
+            r.edge = ctypes.cast(ctypes.pointer(edge), ctypes.c_void_p)
+        if key is not None:
+            drop = _tower_drop_args(base, edge, key)
+            r.drop = ctypes.cast(ctypes.pointer(drop), ctypes.c_void_p)
+        r.n_aggr = self.A
+        for i, c in enumerate(self.aggr):
+            r.aggr[i] = c
+        r.row_mean = self.row_mean(saved).data_ptr()
+        if backward and edge is None and self.E:
+            r.pos_t = _lib.dev_ptr(self.pos_t, torch.int32, "pos_t")
+        r._keep = (base, edge, drop)
+        return r
 
     def edge_args(self, base, e, saved, grad_e=None, backward=False):
         """The pna_tower_edge_train_args around `base` (args() of this plan, set_backward() applied for a backward)."""
@@ -960,10 +998,13 @@ def _tower_drop_args(base, edge, key):
     return d
 
 
-def _tower_train_call(which, base, edge, key, dev):
-    """One of the three C entry pairs, `which` = "fwd" or "bwd": with a mask key pna_tower_drop_train_*_f32, else with an edge block
+def _tower_train_call(which, base, edge, key, dev, aggr=None):
+    """One of the four C entry pairs, `which` = "fwd" or "bwd": with an aggregator-list block (_TowerTrainPlan.aggr_args, which holds the
+    edge block and the mask key) pna_tower_aggr_train_*_f32, else with a mask key pna_tower_drop_train_*_f32, else with an edge block
     pna_tower_edge_train_*_f32, else pna_tower_train_*_f32."""
-    if key is not None:
+    if aggr is not None:
+        name, block = f"pna_tower_aggr_train_{which}_f32", aggr
+    elif key is not None:
         name, block = f"pna_tower_drop_train_{which}_f32", _tower_drop_args(base, edge, key)
     elif edge is not None:
         name, block = f"pna_tower_edge_train_{which}_f32", edge
@@ -972,20 +1013,22 @@ def _tower_train_call(which, base, edge, key, dev):
     _lib.check(getattr(_lib.lib(), name)(ctypes.byref(block), _lib.stream_ptr(dev)), name)
 
 
-def _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, key, params):
-    """The forward of the three tower training Functions.  e None or a layer without edge features: no edge block; key None: no dropout."""
+def _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, key, params, aggr=None):
+    """The forward of the four tower training Functions.  e None or a layer without edge features: no edge block; key None: no dropout;
+    aggr None: mean max min std through the three older entry pairs, else the layer's aggregator codes."""
     T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
     dev = h.device
     x = h if h.stride(1) == 1 else h.contiguous()
     ed = layer.towers[0].edge_dim if e is not None else 0
     ef = None if not ed else (e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous())
-    plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed)
+    plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed, aggr=aggr)
     out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
     saved = plan.new_saved()
     slope = layer.mixing_network.activation.negative_slope
     a = plan.args(graph, x, snorm, scales, _tower_train_tensors(layer, params), params[6 * T], params[6 * T + 1], slope, layer.residual, saved)
     a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
-    _tower_train_call("fwd", a, plan.edge_args(a, ef, saved) if ed else None, key, dev)
+    q = plan.edge_args(a, ef, saved) if ed else None
+    _tower_train_call("fwd", a, q, key, dev, plan.aggr_args(a, q, key, saved) if aggr is not None else None)
     ctx.plan, ctx.graph, ctx.layer, ctx.scales, ctx.snorm, ctx.state, ctx.slope, ctx.key = plan, graph, layer, scales, snorm, saved, slope, key
     ctx.save_for_backward(x, *([ef] if ed else []), *params)
     return out
@@ -1007,7 +1050,7 @@ def _tower_train_backward(ctx, go, lead):
     g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if (ed and need[1]) else None
     # one buffer per kind of parameter: (T, ...) blocks the towers' gradients are views of
     g_wpre = torch.empty(T, Fi, 2 * Fi + ed, dtype=torch.float32, device=dev)
-    g_wpost = torch.empty(T, Fo, (1 + 4 * S) * Fi, dtype=torch.float32, device=dev)
+    g_wpost = torch.empty(T, Fo, (1 + plan.A * S) * Fi, dtype=torch.float32, device=dev)
     g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
     g_vec = torch.empty(3, T, Fo, dtype=torch.float32, device=dev)       # grad_b_post | grad_gamma | grad_beta
     g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad_w_mix | grad_b_mix
@@ -1017,7 +1060,8 @@ def _tower_train_backward(ctx, go, lead):
     grads = [(g_wpre[t], g_bpre[t], g_wpost[t], g_vec[0, t], g_vec[1, t] if has_affine else None, g_vec[2, t] if has_affine else None)
              for t in range(T)]
     plan.set_backward(a, go, g_h, grads, g_mix[:C], g_mix[C])
-    _tower_train_call("bwd", a, plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True) if ed else None, ctx.key, dev)
+    q = plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True) if ed else None
+    _tower_train_call("bwd", a, q, ctx.key, dev, plan.aggr_args(a, q, ctx.key, ctx.state, backward=True) if plan.aggr is not None else None)
     res = [g_h if need[0] else None, g_e] + [None] * (lead - 2)
     for t in range(T):
         res += grads[t]
@@ -1069,6 +1113,21 @@ class TowerLayerDropSmallTrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go):
         return _tower_train_backward(ctx, go, 7)
+
+
+class TowerLayerAggrSmallTrainFn(torch.autograd.Function):
+    """The three Functions above for a PNALayer whose towers aggregate with any 1-4 distinct aggregators out of mean sum max min std var
+    (models/dgl/aggregators.py:6-26, 50-51), through pna_tower_aggr_train_fwd_f32 / pna_tower_aggr_train_bwd_f32.  `e` is None for a layer
+    without edge features, `key` = (p, seed, offset) or None for towers without dropout, `aggr` the tuple of aggregator codes in the
+    layer's order.  A tower's posttrans weight is (Fo, (1 + len(aggr) n_scaler) Fi)."""
+
+    @staticmethod
+    def forward(ctx, h, e, layer, graph, scales, snorm, key, aggr, *params):
+        return _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, key, params, aggr=aggr)
+
+    @staticmethod
+    def backward(ctx, go):
+        return _tower_train_backward(ctx, go, 8)
 
 
 def _tower_train_inputs(layer, snorm_n):
@@ -1550,3 +1609,16 @@ def set2set(x, lstm, steps):
     """`steps` rounds of Set2Set on x (B, N, D) with `lstm` (an nn.LSTM(2D, D): one layer, one direction, bias) through Set2SetFn.  Reads
     nothing on the host and waits for nothing: capturable."""
     return Set2SetFn.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, int(steps))
+
+
+def tower_layer_aggr_small_train(layer, graph, h, e, snorm_n, scales):
+    """The three wrappers above for a layer with another list of aggregators, through TowerLayerAggrSmallTrainFn; with tower dropout the
+    mask's key is drawn as tower_layer_drop_small_train draws it."""
+    from . import functional as PF
+    snorm, *params = _tower_train_inputs(layer, snorm_n)
+    p, key = float(layer.towers[0].dropout), None
+    if p > 0:
+        seed, offset = PF.tower_dropout_key(h.device, h.shape[0] * layer.out_dim)
+        key = (p, seed, offset)
+    aggr = tuple(_lib.AGG_CODES[n] for n in layer.towers[0].aggregators)
+    return TowerLayerAggrSmallTrainFn.apply(h, e if layer.edge_features else None, layer, graph, tuple(scales), snorm, key, aggr, *params)

@@ -19,6 +19,12 @@
 // Dropout inside the towers (pna_tower_drop_train_*_f32, pna_dropout_mask_f32): the two mixing kernels have a DROP instantiation that
 // applies a Philox4x32-10 mask (pna_philox.h) between the BatchNorms' output and the mixing Linear; the backward regenerates it from
 // the call's (seed, offset).  Every other launch is shared with the calls without dropout.
+//
+// Any list of aggregators (pna_tower_aggr_train_*_f32: 1-4 distinct ones out of mean | sum | max | min | std | var in the layer's order,
+// models/dgl/aggregators.py:6-26, 50-51 under pna_layer.py:55-76, 130-145 -- the MPNN rows of realworld_benchmark/README.md:54, 91-100
+// and every aggregator ablation): KArgs carries the block index of each aggregator inside a tower's aggregate, -1 when it is not listed,
+// read under wavefront-uniform branches.  The three entry pairs above fill it with {mean, max, min, std} and run the same kernels in the
+// same arithmetic sequence.  That route's backward is always the per-edge one (k_tt_edge_dm + k_tt_edge_pull), with or without x_edge.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -47,11 +53,14 @@ constexpr int kMaxED = 64;       // edge_dim of the route with edge features: th
 struct KArgs {
   const int32_t* rowptr; const int32_t* col;
   int V, T, Fi, Fo, S, C, TFi, div, residual;
+  int K;                                                    // A Fi: the width of one tower's aggregate, A listed aggregators
+  int b_mean, b_sum, b_max, b_min, b_std, b_var;            // the aggregator's block inside a tower's aggregate, -1 = not listed
+  float* rowmean;                                           // saved (V, T Fi) E[m0] where std / var is listed without mean, else NULL
   const float* h; long ldh;
   const float* snorm;                                       // [V] or NULL (graph norm off)
   const float* scale[3];
   const float* w_pre[kMaxT]; const float* b_pre[kMaxT];     // (Fi, 2 Fi) = [W_a | W_b], [Fi]
-  const float* w_post[kMaxT]; const float* b_post[kMaxT];   // (Fo, (1 + 4 S) Fi) = [W_h | W_s0 | ..], [Fo]
+  const float* w_post[kMaxT]; const float* b_post[kMaxT];   // (Fo, (1 + A S) Fi) = [W_h | W_s0 | ..], [Fo]
   const float* gamma[kMaxT]; const float* beta[kMaxT];
   float* rmean[kMaxT]; float* rvar[kMaxT];
   const float* w_mix; const float* b_mix;                   // (C, C), [C]
@@ -62,7 +71,7 @@ struct KArgs {
   float* part; int n_part;                                  // [tiles][2][C] column sums of a 16-row tile
   float* cm;                                                // backward [2][C]: mean g, mean g xhat
   float* gp; float* hcat; float* ghc; float* gz;            // backward (V, C) each
-  float* gagg;                                              // backward (V, T 4 Fi): [G_mean | G_max | G_min | G_std] per tower
+  float* gagg;                                              // backward (V, T K): the listed blocks' gradients per tower, a's layout
   float* gxs; float* gxd;                                   // backward (V, T Fi): the gradient of x_src, x_dst
   float* gh;                                                // backward (V, in_dim)
   float* ggamma[kMaxT]; float* gbeta[kMaxT];
@@ -78,6 +87,15 @@ struct KArgs {
 };
 
 __device__ __forceinline__ float leaky(float p, float slope) { return p > 0.f ? p : p * slope; }
+
+// var of one feature of one destination row (models/dgl/aggregators.py:22-26): pna_dev::row_stats' radicand before the + 1e-5, op by op
+__device__ __forceinline__ float row_var(float s, float q, int deg) {
+  if (deg <= 0) return 0.f;
+  const float D = (float)deg, invD = 1.0f / D;
+  const float mean = pna_dev::div_rn(s, D, invD), msq = pna_dev::div_rn(q, D, invD);
+  const float var = msq - mean * mean;
+  return var < 0.f ? 0.f : var;
+}
 
 // ---- forward, launch 1: x_cat = [x_src | x_dst], x_src,t = W_a,t h_t, x_dst,t = W_b,t h_t + b_t, of 16 rows ----------------------
 __global__ __launch_bounds__(kThreads) void k_tt_project(const KArgs g) {
@@ -179,9 +197,9 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int Fi = g.Fi, Fo = g.Fo, T = g.T, TFi = g.TFi, C = g.C, K = 4 * Fi, Q = quads(K), P = pitch_of(Q), QH = quads(Fi), PH = pitch_of(QH);
+  const int Fi = g.Fi, Fo = g.Fo, T = g.T, TFi = g.TFi, C = g.C, K = g.K, Q = quads(K), P = pitch_of(Q), QH = quads(Fi), PH = pitch_of(QH);
   const int NT = (Fo + 15) / 16, PZ = C + 1;
-  float* const A = lds;                                     // [16][P]  one tower's aggregate [mean | max | min | std]
+  float* const A = lds;                                     // [16][P]  one tower's aggregate, the listed blocks ([mean | max | min | std])
   float* const H = A + kRows * P;                           // [16][PH] the tower's input slice
   float* const Z = H + kRows * PH;                          // [16][PZ] the rows' z, all towers
   float* const SC = Z + kRows * PZ;                         // [4][16]  scale_0..2 and the graph-norm factor of the tile's rows
@@ -256,11 +274,17 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
           pna_dev::row_stats(s[j], q[j], mx[j], mn[j], end - beg, mean, omx, omn, sd);     // mean | max | min of the shifted messages
           pna_dev::row_stats(s0[j], q0[j], mx[j], mn[j], end - beg, m0, x0, n0, sd);       // std of x_src alone
           float* const al = A + r * P + c;
-          al[0] = mean; al[Fi] = omx; al[2 * Fi] = omn; al[3 * Fi] = sd;
           float* const ag = g.a + (size_t)row * T * K + (size_t)t * K + c;
-          ag[0] = mean; ag[Fi] = omx; ag[2 * Fi] = omn; ag[3 * Fi] = sd;
-          g.amx[(size_t)row * TFi + t * Fi + c] = ax[j];
-          g.amn[(size_t)row * TFi + t * Fi + c] = an[j];
+          if (g.b_mean >= 0) { al[g.b_mean * Fi] = mean; ag[g.b_mean * Fi] = mean; }            // (every branch on the list is wavefront-uniform)
+          if (g.b_max >= 0) { al[g.b_max * Fi] = omx; ag[g.b_max * Fi] = omx; g.amx[(size_t)row * TFi + t * Fi + c] = ax[j]; }
+          if (g.b_min >= 0) { al[g.b_min * Fi] = omn; ag[g.b_min * Fi] = omn; g.amn[(size_t)row * TFi + t * Fi + c] = an[j]; }
+          if (g.b_std >= 0) { al[g.b_std * Fi] = sd; ag[g.b_std * Fi] = sd; }
+          if (g.b_sum >= 0) { al[g.b_sum * Fi] = s[j]; ag[g.b_sum * Fi] = s[j]; }               // the fold's own sum (0 without in-edges)
+          if (g.b_var >= 0) {
+            const float vr = row_var(s0[j], q0[j], end - beg);
+            al[g.b_var * Fi] = vr; ag[g.b_var * Fi] = vr;
+          }
+          if (g.rowmean) g.rowmean[(size_t)row * TFi + t * Fi + c] = m0;
         }
       }
     }
@@ -269,7 +293,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
     for (int nt = wave; nt < NT; nt += kWaves) {
       const int n = nt * 16 + li;
       const bool nok = n < Fo;
-      const float* const wrow = g.w_post[t] + (size_t)min(n, Fo - 1) * (1 + 4 * S) * Fi;
+      const float* const wrow = g.w_post[t] + (size_t)min(n, Fo - 1) * (Fi + S * K);
       f4 acch = {0.f, 0.f, 0.f, 0.f}, acc[S];
 #pragma unroll
       for (int s = 0; s < S; ++s) acc[s] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -546,13 +570,13 @@ __global__ __launch_bounds__(256) void k_tt_bwd_finalize(const KArgs g) {
 }
 
 // ---- backward, launch 3: gz = n[v] gamma invstd (g - mean g - xhat mean(g xhat)) (stored) and, per tower, G = sum_s scale_s (gz_t W_s)
-// of 16 rows into gagg's [G_mean | G_max | G_min | G_std] ----
+// of 16 rows into gagg's blocks, a's layout ([G_mean | G_max | G_min | G_std]) ----
 template <int S>
 __global__ __launch_bounds__(kThreads) void k_tt_rows_bwd(const KArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int Fi = g.Fi, Fo = g.Fo, T = g.T, C = g.C, K = 4 * Fi, QN = quads(Fo), PN = pitch_of(QN), NTJ = (K + 15) / 16;
+  const int Fi = g.Fi, Fo = g.Fo, T = g.T, C = g.C, K = g.K, QN = quads(Fo), PN = pitch_of(QN), NTJ = (K + 15) / 16;
   float* const GZ = lds;                                    // [T][16][PN] gz, a padded block per tower
   float* const SC = GZ + T * kRows * PN;                    // [4][16]
   const int r0 = blockIdx.x * kRows;
@@ -579,14 +603,14 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_bwd(const KArgs g) {
     GZ[i] = val;
   }
   __syncthreads();
-  // G tile (16 rows x 16 columns of the tower's 4 Fi) per wavefront: A = gz_t (K = Fo), B[k = n][j] = W_post,t[n][Fi + s 4Fi + j]
+  // G tile (16 rows x 16 columns of the tower's K) per wavefront: A = gz_t (K = Fo), B[k = n][j] = W_post,t[n][Fi + s K + j]
   for (int u = wave; u < T * NTJ; u += kWaves) {
     const int t = u / NTJ, jt = u - t * NTJ;
     const int j = jt * 16 + li;
     const bool jok = j < K;
     const int jj = min(j, K - 1);
     const float* const w = g.w_post[t] + Fi + jj;
-    const long ldw = (long)(1 + 4 * S) * Fi;
+    const long ldw = (long)Fi + (long)S * K;
     f4 acc[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) acc[s] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -650,7 +674,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_grad_h(const KArgs g) {
     if (wave < NTI) {
       const float* const wpost = g.w_post[t] + ii;          // W_h,t[k][i]: row k of the posttrans weight, column i
       const float* const wpre = g.w_pre[t];
-      const long ldpost = (long)(1 + 4 * g.S) * Fi;
+      const long ldpost = (long)Fi + (long)g.S * g.K;
       for (int qd = 0; qd < Q; ++qd) {
         const int k = 16 * qd + 4 * lg;
         const f4 a = *reinterpret_cast<const f4*>(A + li * P + k);
@@ -684,22 +708,29 @@ __global__ __launch_bounds__(kThreads) void k_tt_grad_h(const KArgs g) {
   }
 }
 
-// ---- backward with edge features, after the rows kernel: the message gradient per edge, destination row by destination row over the
-// FORWARD CSR (a wavefront owns rows wave, wave + 8; a lane owns columns lane and lane + 64 of a tower):
-//   dm[k] = G_mean[v] / D + [std^2 - 1e-5 > 0] G_std[v] / (std[v] D) ((x_src[u] + x_edge[k]) - (mean[v] - x_dst[v]))
+// ---- backward, after the rows kernel (the routes with edge features and the one with an aggregator list): the message gradient per
+// edge, destination row by destination row over the FORWARD CSR (a wavefront owns rows wave, wave + 8; a lane owns columns lane and
+// lane + 64 of a tower).  Only the listed terms appear; m0[k] = x_src[u] [+ x_edge[k]] (EDGE), mean0 = the saved row mean of m0 where
+// there is one, else mean[v] - x_dst[v]:
+//   dm[k] = (G_mean[v] / D + G_sum[v]) + ([std^2 - 1e-5 > 0] G_std[v] / (std[v] D) + [var > 0] 2 G_var[v] / D) (m0[k] - mean0)
 //           + [k = argmax[v]] G_max[v] + [k = argmin[v]] G_min[v]
-// gx_dst[v] = G_mean + G_max + G_min (the variance term sums to zero over a row; 0 for a row without in-edges), and the CSR-ordered
-// copy of e that the W_e weight gradient reads ----
+// gx_dst[v] = G_mean + G_max + G_min + D G_sum (the variance terms sum to zero over a row; 0 for a row without in-edges), and with EDGE
+// the CSR-ordered copy of e that the W_e weight gradient reads.  With {mean, max, min, std} the operations and their order are those
+// of the route with edge features before the list existed ----
+template <bool EDGE>
 __global__ __launch_bounds__(kThreads) void k_tt_edge_dm(const KArgs g) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int Fi = g.Fi, T = g.T, TFi = g.TFi, K = 4 * Fi, ED = g.ED;
+  const int Fi = g.Fi, T = g.T, TFi = g.TFi, K = g.K, ED = g.ED;
+  const bool spread = g.b_std >= 0 || g.b_var >= 0;         // whether any term reads the messages themselves
   const int r0 = blockIdx.x * kRows;
   const int nrows = min(kRows, g.V - r0);
   for (int r = wave; r < nrows; r += kWaves) {
     const int row = r0 + r;
     const int beg = g.rowptr[row], end = g.rowptr[row + 1], D = end - beg;
-    if (lane < ED)
-      for (int k = beg; k < end; ++k) g.ecsr[(size_t)k * ED + lane] = g.e[(size_t)g.eid[k] * g.ld_e + lane];
+    if constexpr (EDGE) {
+      if (lane < ED)
+        for (int k = beg; k < end; ++k) g.ecsr[(size_t)k * ED + lane] = g.e[(size_t)g.eid[k] * g.ld_e + lane];
+    }
     const float fD = (float)D, invD = D > 0 ? 1.0f / fD : 0.f;
     for (int t = 0; t < T; ++t) {
       const float* const xs = g.xcat + t * Fi;
@@ -707,28 +738,45 @@ __global__ __launch_bounds__(kThreads) void k_tt_edge_dm(const KArgs g) {
       for (int j = 0; j < 2; ++j) {
         const int c = lane + 64 * j, cc = min(c, Fi - 1);   // (lanes past the last column redo it; not stored)
         const bool ok = c < Fi;
-        if (j == 1 && Fi <= 64) continue;                   // (wavefront-uniform)
-        const size_t oa = (size_t)row * T * K + (size_t)t * K + cc;
-        const float Gm = g.gagg[oa], Gx = g.gagg[oa + Fi], Gn = g.gagg[oa + 2 * Fi], Gs = g.gagg[oa + 3 * Fi];
-        const float mean = g.a[oa], sd = g.a[oa + 3 * Fi];
+        if (j == 1 && Fi <= 64) continue;                   // (wavefront-uniform, like every branch on the list below)
+        const size_t oa = (size_t)row * T * K + (size_t)t * K + cc, oc = (size_t)row * TFi + t * Fi + cc;
+        float Gm = 0.f, Gx = 0.f, Gn = 0.f, Gs = 0.f, mean = 0.f, sd = 0.f;
+        int ax = -1, an = -1;
+        if (g.b_mean >= 0) { Gm = g.gagg[oa + g.b_mean * Fi]; mean = g.a[oa + g.b_mean * Fi]; }
+        if (g.b_max >= 0) { Gx = g.gagg[oa + g.b_max * Fi]; ax = g.amx[oc]; }
+        if (g.b_min >= 0) { Gn = g.gagg[oa + g.b_min * Fi]; an = g.amn[oc]; }
+        if (g.b_std >= 0) { Gs = g.gagg[oa + g.b_std * Fi]; sd = g.a[oa + g.b_std * Fi]; }
         const float xd = xs[(size_t)row * 2 * TFi + TFi + cc];
-        const int ax = g.amx[(size_t)row * TFi + t * Fi + cc], an = g.amn[(size_t)row * TFi + t * Fi + cc];
-        const float r1 = Gm * invD;
-        const float r2 = (D > 0 && sd * sd - 1e-5f > 0.f) ? Gs / (sd * fD) : 0.f;
-        const float sh = mean - xd;                         // the mean of x_src[u] + x_edge[k]
-        if (ok) g.gxd[(size_t)row * TFi + t * Fi + c] = D > 0 ? (Gm + Gx) + Gn : 0.f;
+        float r1 = Gm * invD;
+        float r2 = (D > 0 && sd * sd - 1e-5f > 0.f) ? Gs / (sd * fD) : 0.f;
+        float gd = (Gm + Gx) + Gn;
+        if (g.b_sum >= 0) {
+          const float Gu = g.gagg[oa + g.b_sum * Fi];
+          r1 = r1 + Gu;
+          gd = gd + fD * Gu;
+        }
+        if (g.b_var >= 0) {
+          const float Gv = g.gagg[oa + g.b_var * Fi], vr = g.a[oa + g.b_var * Fi];
+          r2 = r2 + ((D > 0 && vr > 0.f) ? (2.0f * Gv) / fD : 0.f);
+        }
+        const float sh = g.rowmean ? g.rowmean[oc] : mean - xd;     // the mean of m0 over the row
+        if (ok) g.gxd[oc] = D > 0 ? gd : 0.f;
         for (int e = beg; e < end; e += kEU) {
-          float m0[kEU];
+          float m0[kEU] = {0.f, 0.f, 0.f, 0.f};
+          if (spread) {
 #pragma unroll
-          for (int u = 0; u < kEU; ++u) {
-            const int k = min(e + u, end - 1);
-            m0[u] = xs[(size_t)g.col[k] * 2 * TFi + cc] + g.xedge[(size_t)k * TFi + t * Fi + cc];
+            for (int u = 0; u < kEU; ++u) {
+              const int k = min(e + u, end - 1);
+              m0[u] = xs[(size_t)g.col[k] * 2 * TFi + cc];
+              if constexpr (EDGE) m0[u] = m0[u] + g.xedge[(size_t)k * TFi + t * Fi + cc];
+            }
           }
 #pragma unroll
           for (int u = 0; u < kEU; ++u)
             if (e + u < end) {                              // (wavefront-uniform)
               const int k = e + u;
-              float d = r1 + r2 * (m0[u] - sh);
+              float d = r1;
+              if (spread) d = r1 + r2 * (m0[u] - sh);
               d = d + (k == ax ? Gx : 0.f);
               d = d + (k == an ? Gn : 0.f);
               if (ok) g.dm[(size_t)k * TFi + t * Fi + c] = d;
@@ -848,8 +896,34 @@ bool in_scope(int64_t V, int64_t E, int T, int Fi, int Fo, int S, int div) {
 bool dw_takes(int N, int S, int K, int Kh) { return N <= 128 && S * N <= 240 && K + Kh + 1 <= 384; }      // (every N of this file is <= 128)
 int64_t dw_bytes_of(int64_t V, int N, int S, int K, int Kh) { return dw_takes(N, S, K, Kh) ? (int64_t)240 * 384 * 4 * ((V + 255) / 256) : 0; }
 
-// ED == 0: the route without edge features.  ED > 0: no packed rows (its pull reads dm), + dm (E, T Fi) and the CSR-ordered copy of e
-Layout layout_of(int64_t V, int T, int Fi, int Fo, int S, int64_t E = 0, int ED = 0) {
+// The aggregator list of a call: how many, each one's block inside a tower's aggregate (-1 = not listed; indexed by PNA_AGG_MEAN ..
+// PNA_AGG_VAR), and what pna_tower_aggr_train_args carries beside the three older blocks.  general: the call came through
+// pna_tower_aggr_train_*_f32 -- its backward is the per-edge one whether there are edge features or not
+struct Aggr {
+  int A, b[6];
+  bool general;
+  float* row_mean;
+  const int32_t* pos_t;
+};
+const Aggr kStandard = {4, {0, -1, 1, 2, 3, -1}, false, nullptr, nullptr};      // mean | max | min | std
+
+// the list of a pna_tower_aggr_train call: 1..4 distinct codes out of PNA_AGG_MEAN .. PNA_AGG_VAR
+bool read_list(int n_aggr, const int32_t* aggr, Aggr& ag) {
+  if (n_aggr < 1 || n_aggr > 4 || !aggr) return false;
+  ag.A = n_aggr;
+  for (int i = 0; i < 6; ++i) ag.b[i] = -1;
+  for (int i = 0; i < n_aggr; ++i) {
+    if (aggr[i] < PNA_AGG_MEAN || aggr[i] > PNA_AGG_VAR || ag.b[aggr[i]] >= 0) return false;
+    ag.b[aggr[i]] = i;
+  }
+  ag.general = true; ag.row_mean = nullptr; ag.pos_t = nullptr;
+  return true;
+}
+bool needs_row_mean(const Aggr& ag) { return (ag.b[PNA_AGG_STD] >= 0 || ag.b[PNA_AGG_VAR] >= 0) && ag.b[PNA_AGG_MEAN] < 0; }
+
+// ED == 0: the route without edge features.  ED > 0: no packed rows (its pull reads dm), + dm (E, T Fi) and the CSR-ordered copy of e.
+// A: the listed aggregators; per_edge: the backward forms dm also without edge features (no packed rows either way)
+Layout layout_of(int64_t V, int T, int Fi, int Fo, int S, int64_t E = 0, int ED = 0, int A = 4, bool per_edge = false) {
   Layout l;
   const int64_t C = (int64_t)T * Fo, TFi = (int64_t)T * Fi;
   l.n_tile = (int)((V + kRows - 1) / kRows);
@@ -862,13 +936,13 @@ Layout layout_of(int64_t V, int T, int Fi, int Fo, int S, int64_t E = 0, int ED 
   l.ghc = l.hcat + up64(V * C);
   l.gz = l.ghc + up64(V * C);
   l.gagg = l.gz + up64(V * C);
-  l.gxs = l.gagg + up64(V * 4 * TFi);
+  l.gxs = l.gagg + up64(V * A * TFi);
   l.gxd = l.gxs + up64(V * TFi);
   l.packed = l.gxd + up64(V * TFi);
-  l.dm = l.packed + (ED > 0 ? 0 : up64(V * l.pitch));
-  l.ecsr = l.dm + (ED > 0 ? up64(E * TFi) : 0);
+  l.dm = l.packed + ((ED > 0 || per_edge) ? 0 : up64(V * l.pitch));
+  l.ecsr = l.dm + ((ED > 0 || per_edge) ? up64(E * TFi) : 0);
   l.dw = l.ecsr + (ED > 0 ? up64(E * ED) : 0);
-  int64_t b = dw_bytes_of(V, Fo, S, 4 * Fi, Fi);
+  int64_t b = dw_bytes_of(V, Fo, S, A * Fi, Fi);
   const int64_t b1 = dw_bytes_of(V, Fi, 1, Fi, 0), b2 = dw_bytes_of(V, (int)C, 1, (int)C, 0), b3 = ED > 0 ? dw_bytes_of(E, Fi, 1, ED, 0) : 0;
   b = b > b1 ? b : b1;
   b = b > b2 ? b : b2;
@@ -877,15 +951,17 @@ Layout layout_of(int64_t V, int T, int Fi, int Fo, int S, int64_t E = 0, int ED 
   return l;
 }
 
-// q != NULL: the call with edge features (pna_tower_edge_train_*): its own checks, the wider pretrans weight, the larger workspace
-int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const char* who, const pna_tower_edge_train_args* q = nullptr) {
+// q != NULL: the call with edge features (pna_tower_edge_train_*): its own checks, the wider pretrans weight, the larger workspace.
+// ag: the aggregator list (the three older entry pairs: kStandard)
+int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const char* who, const pna_tower_edge_train_args* q = nullptr,
+         const Aggr& ag = kStandard) {
   if (!p) return pna_set_error(PNA_E_INVALID, who);
   if (int rc_ss = pna_check_struct_size(bwd ? "pna_tower_train_bwd_f32" : "pna_tower_train_fwd_f32", p->struct_size, sizeof(*p))) return rc_ss;
   const int T = p->n_tower, Fi = p->Fi, Fo = p->Fo, S = p->n_scaler;
   if (!in_scope(p->V, p->E, T, Fi, Fo, S, p->divide_input)) return pna_set_error(PNA_E_INVALID, who);
   const int in_dim = p->divide_input ? T * Fi : Fi, C = T * Fo;
   if (p->residual && in_dim != C) return pna_set_error(PNA_E_INVALID, who);
-  if (!p->rowptr || (p->E > 0 && !p->col) || !p->h || p->ldh < in_dim || !p->w_mix || !p->x_cat || !p->a || !p->argmax || !p->argmin || !p->z || !p->p ||
+  if (!p->rowptr || (p->E > 0 && !p->col) || !p->h || p->ldh < in_dim || !p->w_mix || !p->x_cat || !p->a || (ag.b[PNA_AGG_MAX] >= 0 && !p->argmax) || (ag.b[PNA_AGG_MIN] >= 0 && !p->argmin) || !p->z || !p->p ||
       !p->save_mean || !p->save_invstd || !p->workspace || ((uintptr_t)p->workspace & 255))
     return pna_set_error(PNA_E_INVALID, who);
   for (int t = 0; t < T; ++t)
@@ -896,7 +972,8 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
   if (bwd) {
     if (!p->grad_out || p->ld_go < C || !p->grad_h || !p->grad_w_mix || !p->grad_b_mix || !p->items_t || p->n_items_t != p->V)
       return pna_set_error(PNA_E_INVALID, who);
-    if (!q && (!p->col_t || !p->rank_t)) return pna_set_error(PNA_E_INVALID, who);      // (the edge route's pull reads pos_t instead)
+    if (!q && !ag.general && (!p->col_t || !p->rank_t)) return pna_set_error(PNA_E_INVALID, who);      // (the per-edge pull reads pos_t instead)
+    if (!q && ag.general && p->E > 0 && !ag.pos_t) return pna_set_error(PNA_E_INVALID, who);
     for (int t = 0; t < T; ++t)
       if (!p->grad_w_pre[t] || !p->grad_b_pre[t] || !p->grad_w_post[t] || !p->grad_b_post[t] || (p->gamma[t] && (!p->grad_gamma[t] || !p->grad_beta[t])))
         return pna_set_error(PNA_E_INVALID, who);
@@ -907,12 +984,17 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
     if (p->E > 0 && (!q->e || q->ld_e < ED || !q->eid || !q->x_edge || (bwd && !q->pos_t))) return pna_set_error(PNA_E_INVALID, who);
     if (bwd && q->grad_e && q->ld_ge < ED) return pna_set_error(PNA_E_INVALID, who);
   }
-  l = layout_of(p->V, T, Fi, Fo, S, p->E, ED);
+  if (ag.general && needs_row_mean(ag) && !ag.row_mean) return pna_set_error(PNA_E_INVALID, who);
+  l = layout_of(p->V, T, Fi, Fo, S, p->E, ED, ag.A, ag.general);
   if (p->workspace_bytes < l.total * 4) return pna_set_error(PNA_E_INVALID, who);
   memset(&g, 0, sizeof(g));
   float* const ws = (float*)p->workspace;
   g.rowptr = p->rowptr; g.col = p->col; g.V = p->V; g.T = T; g.Fi = Fi; g.Fo = Fo; g.S = S; g.C = C; g.TFi = T * Fi;
   g.div = p->divide_input; g.residual = p->residual != 0;
+  g.K = ag.A * Fi;
+  g.b_mean = ag.b[PNA_AGG_MEAN]; g.b_sum = ag.b[PNA_AGG_SUM]; g.b_max = ag.b[PNA_AGG_MAX]; g.b_min = ag.b[PNA_AGG_MIN];
+  g.b_std = ag.b[PNA_AGG_STD]; g.b_var = ag.b[PNA_AGG_VAR];
+  g.rowmean = needs_row_mean(ag) ? ag.row_mean : nullptr;
   g.h = p->h; g.ldh = (long)p->ldh; g.snorm = p->snorm_n;
   for (int s = 0; s < 3; ++s) g.scale[s] = s < S ? p->row_scale[s] : nullptr;
   for (int t = 0; t < T; ++t) {
@@ -930,6 +1012,8 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
   if (q) {
     g.e = q->e; g.ld_e = (long)q->ld_e; g.eid = q->eid; g.xedge = q->x_edge; g.pos_t = q->pos_t; g.items_t = p->items_t;
     g.dm = ws + l.dm; g.ecsr = ws + l.ecsr; g.ge = q->grad_e; g.ld_ge = (long)q->ld_ge;
+  } else if (ag.general) {
+    g.pos_t = ag.pos_t; g.items_t = p->items_t; g.dm = ws + l.dm;
   }
   return PNA_OK;
 }
@@ -968,7 +1052,7 @@ int launch_fwd(const KArgs& g, const Layout& l, hipStream_t st, const char* fail
   hipLaunchKernelGGL(k_tt_project, grid, block, (size_t)kRows * (in_dim + 1) * sizeof(float), st, g);                   // <= 33 KB
   if (EDGE && g.E > 0)
     hipLaunchKernelGGL(k_tt_edge_project, dim3((unsigned)((g.E + kRows - 1) / kRows)), block, (size_t)kRows * pitch_of(quads(g.ED)) * sizeof(float), st, g);
-  const size_t lds = ((size_t)kRows * pitch_of(quads(4 * Fi)) + (size_t)kRows * pitch_of(quads(Fi)) + (size_t)kRows * (C + 1) + 4 * kRows) * sizeof(float);   // <= 50 KB
+  const size_t lds = ((size_t)kRows * pitch_of(quads(g.K)) + (size_t)kRows * pitch_of(quads(Fi)) + (size_t)kRows * (C + 1) + 4 * kRows) * sizeof(float);   // <= 50 KB
   if (g.S == 1) hipLaunchKernelGGL((k_tt_rows_fwd<1, EDGE>), grid, block, lds, st, g);
   else if (g.S == 2) hipLaunchKernelGGL((k_tt_rows_fwd<2, EDGE>), grid, block, lds, st, g);
   else hipLaunchKernelGGL((k_tt_rows_fwd<3, EDGE>), grid, block, lds, st, g);
@@ -978,11 +1062,12 @@ int launch_fwd(const KArgs& g, const Layout& l, hipStream_t st, const char* fail
   return PNA_OK;
 }
 
-// q != NULL: the backward with edge features -- the per-edge message gradient and its pull instead of rowprep + the ranked pull
+// q != NULL: the backward with edge features -- the per-edge message gradient and its pull instead of rowprep + the ranked pull;
+// per_edge: the same without edge features (the call with an aggregator list)
 int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, pna_stream_t stream, const pna_tower_edge_train_args* q, const char* failed,
-               bool drop = false) {
+               bool drop = false, bool per_edge = false) {
   hipStream_t st = (hipStream_t)stream;
-  const int T = g.T, Fi = g.Fi, Fo = g.Fo, S = g.S, C = g.C, TFi = g.TFi, K = 4 * Fi;
+  const int T = g.T, Fi = g.Fi, Fo = g.Fo, S = g.S, C = g.C, TFi = g.TFi, K = g.K;
   const dim3 grid((unsigned)l.n_tile), block(kThreads);
   // 1. the mixing network, 2. the column sums, 3. gz and the aggregate's gradient
   const size_t lds_mix = ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float);
@@ -998,10 +1083,14 @@ int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, p
   int rc2;
   if (q) {
     // 4. the message gradient per edge (and gx_dst, the CSR-ordered e), then its pull per source row: gx_src; grad_e when wanted
-    hipLaunchKernelGGL(k_tt_edge_dm, grid, block, 0, st, g);
+    hipLaunchKernelGGL(k_tt_edge_dm<true>, grid, block, 0, st, g);
     hipLaunchKernelGGL(k_tt_edge_pull, grid, block, 0, st, g);
     if (g.ge && g.E > 0)
       hipLaunchKernelGGL(k_tt_edge_grad_e, dim3((unsigned)((g.E + kRows - 1) / kRows)), block, (size_t)kRows * pitch_of(quads(Fi)) * sizeof(float), st, g);
+  } else if (per_edge) {
+    // 4. the same two launches on the messages without an x_edge term: no copy of e, no grad_e
+    hipLaunchKernelGGL(k_tt_edge_dm<false>, grid, block, 0, st, g);
+    hipLaunchKernelGGL(k_tt_edge_pull, grid, block, 0, st, g);
   } else {
     // 4. rowprep + ranked pull over the transposed graph, all towers: gx_src; rowprep's grad_dst is gx_dst
     pna_segreduce_bwd_args b;
@@ -1035,7 +1124,7 @@ int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, p
   const int64_t ldwp = (int64_t)g.ldw_pre;
   for (int t = 0; t < T; ++t) {
     const float* const ht = p->h + (g.div ? t * Fi : 0);
-    rc2 = weight_grad(g.gz + t * Fo, C, Fo, p->a + (size_t)t * K, (int64_t)T * K, K, ht, p->ldh, Fi, S, p->row_scale, p->V, p->grad_w_post[t], (int64_t)(1 + 4 * S) * Fi,
+    rc2 = weight_grad(g.gz + t * Fo, C, Fo, p->a + (size_t)t * K, (int64_t)T * K, K, ht, p->ldh, Fi, S, p->row_scale, p->V, p->grad_w_post[t], (int64_t)Fi + (int64_t)S * K,
                       p->grad_b_post[t], dws, l.dw_bytes, st);
     if (rc2 != PNA_OK) return rc2;
     rc2 = weight_grad(g.gxs + t * Fi, TFi, Fi, ht, p->ldh, Fi, nullptr, 0, 0, 1, nullptr, p->V, p->grad_w_pre[t], ldwp, nullptr, dws, l.dw_bytes, st);
@@ -1080,6 +1169,36 @@ int fill_drop(const pna_tower_drop_args* d, KArgs& g, Layout& l, bool bwd) {
   const int rc = fill(d->base, g, l, bwd, who, d->edge);
   if (rc != PNA_OK) return rc;
   g.drop = pna_philox::make_mask(d->p, d->seed, d->offset);
+  return PNA_OK;
+}
+
+// pna_tower_aggr_train_*: the list and the consistency of the blocks, then the base route's checks under that list
+int fill_aggr(const pna_tower_aggr_train_args* r, KArgs& g, Layout& l, bool bwd) {
+  static const char* const needs =
+      ": needs 1 <= n_aggr <= 4 distinct codes PNA_AGG_MEAN .. PNA_AGG_VAR in aggr; a base inside pna_tower_train_*_f32's scope whose a is (V, n_tower n_aggr Fi) "
+      "and whose w_post / grad_w_post are (Fo, (1 + n_aggr n_scaler) Fi), argmax where max is listed, argmin where min is listed; edge == NULL, or an edge "
+      "pna_tower_edge_train_*_f32 accepts with edge->base == base; drop == NULL, or 0 <= p < 1 with drop->base == base and drop->edge == edge; row_mean "
+      "(V, n_tower Fi) where std or var is listed and mean is not; in the backward with E > 0 and edge == NULL pos_t; a 256-byte aligned workspace of "
+      "pna_tower_aggr_train_workspace_bytes(V, E, n_tower, Fi, Fo, n_scaler, divide_input, edge_dim, n_aggr, aggr) bytes";
+  static const std::string fwd_msg = std::string("pna_tower_aggr_train_fwd_f32") + needs, bwd_msg = std::string("pna_tower_aggr_train_bwd_f32") + needs;
+  const char* const who = bwd ? bwd_msg.c_str() : fwd_msg.c_str();
+  const char* const fn = bwd ? "pna_tower_aggr_train_bwd_f32" : "pna_tower_aggr_train_fwd_f32";
+  if (!r) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(fn, r->struct_size, sizeof(*r))) return rc_ss;
+  Aggr ag;
+  if (!read_list(r->n_aggr, r->aggr, ag) || !r->base) return pna_set_error(PNA_E_INVALID, who);
+  if (r->edge) {
+    if (int rc_ss = pna_check_struct_size(fn, r->edge->struct_size, sizeof(*r->edge))) return rc_ss;
+    if (r->edge->base != r->base) return pna_set_error(PNA_E_INVALID, who);
+  }
+  if (r->drop) {
+    if (int rc_ss = pna_check_struct_size(fn, r->drop->struct_size, sizeof(*r->drop))) return rc_ss;
+    if (r->drop->base != r->base || r->drop->edge != r->edge || !(r->drop->p >= 0.f && r->drop->p < 1.f)) return pna_set_error(PNA_E_INVALID, who);
+  }
+  ag.row_mean = r->row_mean; ag.pos_t = r->pos_t;
+  const int rc = fill(r->base, g, l, bwd, who, r->edge, ag);
+  if (rc != PNA_OK) return rc;
+  if (r->drop) g.drop = pna_philox::make_mask(r->drop->p, r->drop->seed, r->drop->offset);
   return PNA_OK;
 }
 
@@ -1165,6 +1284,32 @@ extern "C" int pna_tower_drop_train_bwd_f32(const pna_tower_drop_args* d, pna_st
   const int rc = fill_drop(d, g, l, true);
   if (rc != PNA_OK) return rc;
   return launch_bwd(d->base, g, l, stream, d->edge, "pna_tower_drop_train_bwd_f32: launch failed", true);
+}
+
+extern "C" int64_t pna_tower_aggr_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input,
+                                                        int32_t edge_dim, int32_t n_aggr, const int32_t* aggr) {
+  Aggr ag;
+  if (!in_scope(V, E, n_tower, Fi, Fo, n_scaler, divide_input) || edge_dim < 0 || edge_dim > kMaxED || !read_list(n_aggr, aggr, ag)) return -1;
+  return layout_of(V, n_tower, Fi, Fo, n_scaler, E, edge_dim, ag.A, true).total * 4;
+}
+
+extern "C" int pna_tower_aggr_train_fwd_f32(const pna_tower_aggr_train_args* r, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill_aggr(r, g, l, false);
+  if (rc != PNA_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const char* const failed = "pna_tower_aggr_train_fwd_f32: launch failed";
+  if (r->edge) return r->drop ? launch_fwd<true, true>(g, l, st, failed) : launch_fwd<true, false>(g, l, st, failed);
+  return r->drop ? launch_fwd<false, true>(g, l, st, failed) : launch_fwd<false, false>(g, l, st, failed);
+}
+
+extern "C" int pna_tower_aggr_train_bwd_f32(const pna_tower_aggr_train_args* r, pna_stream_t stream) {
+  KArgs g;
+  Layout l;
+  const int rc = fill_aggr(r, g, l, true);
+  if (rc != PNA_OK) return rc;
+  return launch_bwd(r->base, g, l, stream, r->edge, "pna_tower_aggr_train_bwd_f32: launch failed", r->drop != nullptr, true);
 }
 
 extern "C" int pna_dropout_mask_f32(float* out, int64_t ld, int64_t V, int32_t C, float p, uint64_t seed, uint64_t offset, pna_stream_t stream) {

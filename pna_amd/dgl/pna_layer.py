@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import _lib
 from .. import functional as PF
 from .. import ops
 from ..graph import Graph
@@ -406,10 +407,25 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
             return False
         return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())     # (the query needs a device)
 
-    def _small_tower_train_clauses(self, graph, h, snorm_n, rows, edge, e, drop=False):
+    def _small_tower_aggr_train_path(self, graph, h, e, snorm_n=None):
+        """Whether this call is served by pna_tower_aggr_train_fwd_f32 / _bwd_f32 (autograd.TowerLayerAggrSmallTrainFn): the clauses of
+        _small_tower_train_path with the knob PNA_AMD_SMALL_TOWER_TRAIN_AGGR_ROWS in place of the other three and, instead of mean max min
+        std, 1-4 distinct aggregators out of mean sum max min std var in any order, equal across the towers and NOT that list in that
+        order (the other three routes serve it: the four stay disjoint).  Edge features are allowed either way (the clauses of
+        _small_tower_train_edge_path apply when the layer has them); the towers' dropout is 0 everywhere or one 0 < p < 1, and in the
+        second case the route is not taken while the stream is being captured (the mask's key is drawn on the host)."""
+        if not self._small_tower_train_clauses(graph, h, snorm_n, PF.SMALL_TOWER_TRAIN_AGGR_ROWS, bool(self.edge_features), e, drop=None, any_list=True):
+            return False
+        if self.towers[0].dropout == 0:
+            return True
+        return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())     # (the query needs a device)
+
+    def _small_tower_train_clauses(self, graph, h, snorm_n, rows, edge, e, drop=False, any_list=False):
         """The clauses of the one-call training routes: `rows` the route's knob, `edge` whether it is the route with edge features
         (required of the layer and every tower) or the one without (excluded), `e` the edge route's features, `drop` whether the towers'
-        dropout has to be active (one p in (0, 1) for all towers) or absent."""
+        dropout has to be active (one p in (0, 1) for all towers) or absent, None = either (0 everywhere, or one p in (0, 1)).  any_list:
+        the route of pna_tower_aggr_train_* -- 1-4 distinct aggregators out of functional.TOWER_TRAIN_AGGREGATORS other than
+        ("mean", "max", "min", "std") where the default requires exactly that list."""
         V = h.shape[0]
         if not (rows > 0 and 0 < V <= rows):
             return False
@@ -418,12 +434,26 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
         if not (self.training and bool(self.edge_features) == edge and h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and type(graph) is Graph
                 and graph.num_nodes == V and V >= 2 and h.shape[1] == self.in_dim):
             return False
-        if not (tuple(t0.aggregators) == ("mean", "max", "min", "std") and 1 <= len(t0.scalers) <= 3
-                and PF.small_tower_train_fits(len(towers), self.input_tower, self.output_tower, len(t0.scalers))):
+        names = tuple(t0.aggregators)
+        if any_list:
+            if not (1 <= len(names) <= 4 and len(set(names)) == len(names) and all(n in PF.TOWER_TRAIN_AGGREGATORS for n in names)
+                    and names != ("mean", "max", "min", "std") and 1 <= len(t0.scalers) <= 3):
+                return False
+            if not PF.small_tower_aggr_train_fits(len(towers), self.input_tower, self.output_tower, len(t0.scalers), 0, [_lib.AGG_CODES[n] for n in names]):
+                return False
+            post_shape = (self.output_tower, (1 + len(names) * len(t0.scalers)) * self.input_tower)
+            if any(len(t.posttrans.fully_connected) != 1 or tuple(t.posttrans.fully_connected[0].linear.weight.shape) != post_shape for t in towers):
+                return False
+        elif not (names == ("mean", "max", "min", "std") and 1 <= len(t0.scalers) <= 3
+                  and PF.small_tower_train_fits(len(towers), self.input_tower, self.output_tower, len(t0.scalers))):
             return False
         if edge:
             Fi, ed = self.input_tower, t0.edge_dim
-            if not (PF.small_tower_train_edge_fits(len(towers), Fi, self.output_tower, len(t0.scalers), ed) and all(t.edge_dim == ed for t in towers)):
+            if any_list:
+                fits = ed >= 1 and PF.small_tower_aggr_train_fits(len(towers), Fi, self.output_tower, len(t0.scalers), ed, [_lib.AGG_CODES[n] for n in names])
+            else:
+                fits = PF.small_tower_train_edge_fits(len(towers), Fi, self.output_tower, len(t0.scalers), ed)
+            if not (fits and all(t.edge_dim == ed for t in towers)):
                 return False
             if any(len(t.pretrans.fully_connected) != 1 or tuple(t.pretrans.fully_connected[0].linear.weight.shape) != (Fi, 2 * Fi + ed) for t in towers):
                 return False
@@ -431,7 +461,10 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
                 return False
         for t in towers:
             bn = t.batchnorm_h
-            drop_ok = (0 < t.dropout < 1 and t.dropout == t0.dropout) if drop else t.dropout == 0
+            if drop is None:
+                drop_ok = 0 <= t.dropout < 1 and t.dropout == t0.dropout
+            else:
+                drop_ok = (0 < t.dropout < 1 and t.dropout == t0.dropout) if drop else t.dropout == 0
             if not (t.training and bn.training and t.batch_norm and bool(t.edge_features) == edge and drop_ok and t.graph_norm == t0.graph_norm
                     and tuple(t.aggregators) == tuple(t0.aggregators) and tuple(t.scalers) == tuple(t0.scalers)
                     and len(t.pretrans.fully_connected) == 1 and len(t.posttrans.fully_connected) == 1):
@@ -520,6 +553,12 @@ class PNALayer(PF.DropsCachesOnConversion, nn.Module):
             from .. import autograd as AG
             t0 = self.towers[0]
             return AG.tower_layer_drop_small_train(self, graph, h, e, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
+        if PF.SMALL_TOWER_TRAIN_AGGR_ROWS > 0 and self._small_tower_aggr_train_path(graph, h, e, snorm_n):
+            # the same for any other list of 1-4 aggregators out of mean sum max min std var, with or without edge features and tower
+            # dropout (autograd.TowerLayerAggrSmallTrainFn)
+            from .. import autograd as AG
+            t0 = self.towers[0]
+            return AG.tower_layer_aggr_small_train(self, graph, h, e, snorm_n, _row_scales(graph, t0.scalers, t0.avg_d, h.device))
         h_cat = _towers_forward(list(self.towers), graph, h, e, snorm_n, self.divide_input)
         mix = self.mixing_network
         if (h_cat.shape[1] >= 4 and isinstance(mix.activation, nn.LeakyReLU) and mix.b_norm is None and (mix.dropout is None or not self.training)

@@ -1223,6 +1223,26 @@ def small_tower_train_edge_fits(T, Fi, Fo, S=3, edge_dim=0):
 SMALL_TOWER_TRAIN_DROPOUT_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_DROPOUT_ROWS", "0"))
 
 
+# PNALayer TRAINING batches whose towers aggregate with ANY 1-4 distinct aggregators out of mean sum max min std var -- except the list
+# mean max min std in that order, which the three knobs above serve -- up to this many nodes take the one-call route
+# (autograd.TowerLayerAggrSmallTrainFn: pna_tower_aggr_train_fwd_f32 / _bwd_f32), with or without edge features and tower dropout.  A knob
+# of its own: the three above keep their meaning and their scope.  0 = off, the default
+SMALL_TOWER_TRAIN_AGGR_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_AGGR_ROWS", "0"))
+
+TOWER_TRAIN_AGGREGATORS = ("mean", "sum", "max", "min", "std", "var")
+
+
+def small_tower_aggr_train_fits(T, Fi, Fo, S, edge_dim, codes):
+    """Whether towers, widths, scalers, edge_dim (0 = no edge features) and the list of aggregator codes are inside
+    pna_tower_aggr_train_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, two rows without edges)
+    codes = [int(c) for c in codes]
+    if not all(-2 ** 31 <= c < 2 ** 31 for c in codes):
+        return False
+    arr = (ctypes.c_int32 * max(len(codes), 1))(*codes)
+    return _lib.lib().pna_tower_aggr_train_workspace_bytes(2, 0, T, Fi, Fo, S, 0, edge_dim, len(codes), arr) >= 0
+
+
 def tower_dropout_key(device, n):
     """(seed, offset) of one dropout mask over n elements, taken from the device's default torch generator, which then moves past the
     4 ceil(n / 4) words the mask may use: torch.manual_seed makes a run reproducible and torch's own random ops behind the call draw
