@@ -418,6 +418,16 @@ def M_rows(t):
     return t.shape[0]
 
 
+def _rows(t):
+    """t as rows the one-call routes take: unit column stride and a row pitch of at least the width, anything else copied once (an
+    expanded tensor has pitch 0, and every C entry refuses a pitch below the width).  A tensor that qualifies comes back as it is, no
+    copy; so does one of at most one row with unit column stride, whose pitch nothing reads.  The copy is a clone in row-major strides:
+    `contiguous()` returns a tensor of width 1 with column stride != 1 as it is."""
+    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 DAGG_GROUPED = os.environ.get("PNA_AMD_DAGG_GROUPED", "1") != "0"     # 0: d agg = gy W^T as the three-block bf16 x 3 contraction (rounds 3-5)
 PULL_EDGE_ROWS = os.environ.get("PNA_AMD_PULL_EDGE_ROWS", "1") != "0"   # 0: the ranked pull of rounds 3-5 (R1 | R2 | G_max | G_min | ranks per out-edge)
 PULL_PACKED = os.environ.get("PNA_AMD_PULL_PACKED", "1") != "0"   # 0: table, aggregate gradient and ranks as three separate rows (round 3)
@@ -443,7 +453,7 @@ class SimpleLayerPlanFn(torch.autograd.Function):
         F, N = layer.in_dim, layer.out_dim
         K = 4 * F
         aggs = list(layer.aggregators)
-        x = h if h.stride(1) == 1 else h.contiguous()
+        x = _rows(h)
         csr = graph.csr
         dev = h.device
         agg = torch.empty(plan.rows, DG.agg_pitch(K), dtype=torch.float32, device=dev)[:, :K]
@@ -470,7 +480,7 @@ class SimpleLayerPlanFn(torch.autograd.Function):
         x, weight, agg, amx, amn = ctx.saved_tensors
         graph, plan, scales, aggs, F, N = ctx.graph, ctx.plan, ctx.scales, ctx.aggs, ctx.F, ctx.N
         K, S = 4 * F, len(scales)
-        gy = gy if gy.stride(1) == 1 else gy.contiguous()
+        gy = _rows(gy)
         g_w = g_b = g_h = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_b:
@@ -543,6 +553,7 @@ class PosttransFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, agg, K, weight, bias, row_scales, h_self, degree_graph=None):
         w = weight if weight.stride(-1) == 1 else weight.contiguous()
+        agg, h_self = _rows(agg), None if h_self is None else _rows(h_self)
         y = ops.posttrans(agg, K, w, row_scales, bias, h_self)
         ctx.K, ctx.row_scales = K, row_scales
         ctx.degree_graph = degree_graph                   # the graph whose DEGREE scalers row_scales are (or None): see backward
@@ -555,6 +566,7 @@ class PosttransFn(torch.autograd.Function):
         agg, weight, h_self = ctx.saved_tensors
         K, scales = ctx.K, ctx.row_scales
         S = len(scales)
+        gy = _rows(gy)                                    # (the weight-gradient kernels take a row pitch: an expand has none)
         Kh = 0 if h_self is None else h_self.shape[1]
         a = agg[:, :K]
         # G = [scale_0 (.) gy | scale_1 (.) gy | ...]  (M, S*N): one operand for both big products, so that each is ONE
@@ -645,9 +657,10 @@ def bn_relu_residual(bn, y, residual=None, relu=True):
 class BnTailFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, residual, running_mean, running_var, momentum, eps, relu):
+        y = _rows(y)
         M, N = y.shape
         dev = y.device
-        res = None if residual is None else (residual if residual.stride(1) == 1 else residual.contiguous())
+        res = None if residual is None else _rows(residual)
         out = torch.empty(M, N, dtype=torch.float32, device=dev)
         stats = torch.empty(2, N, dtype=torch.float32, device=dev)
         ws = torch.empty(_lib.lib().pna_bn_tail_workspace_bytes(M, N) // 4, dtype=torch.float32, device=dev)
@@ -672,7 +685,7 @@ class BnTailFn(torch.autograd.Function):
         y, gamma, beta, stats = ctx.saved_tensors
         M, N = y.shape
         dev = y.device
-        go = go if go.stride(1) == 1 else go.contiguous()
+        go = _rows(go)
         gy = torch.empty(M, N, dtype=torch.float32, device=dev)
         gwb = torch.empty(2, N, dtype=torch.float32, device=dev)
         ws = torch.empty(_lib.lib().pna_bn_tail_workspace_bytes(M, N) // 4, dtype=torch.float32, device=dev)
@@ -781,7 +794,7 @@ class SimpleLayerSmallTrainFn(torch.autograd.Function):
         bn = layer.batchnorm_h
         F, N, S = layer.in_dim, layer.out_dim, len(scales)
         dev = h.device
-        x = h if h.stride(1) == 1 else h.contiguous()
+        x = _rows(h)
         w = weight if weight.is_contiguous() else weight.contiguous()
         plan = _SmallTrainPlan(graph, F, N, S, dev)
         out = torch.empty(plan.V, N, dtype=torch.float32, device=dev)
@@ -799,7 +812,7 @@ class SimpleLayerSmallTrainFn(torch.autograd.Function):
         plan, layer = ctx.plan, ctx.layer
         F, N, S = plan.F, plan.N, plan.S
         dev = x.device
-        go = go if go.stride(1) == 1 else go.contiguous()
+        go = _rows(go)
         g_h = torch.empty(plan.V, F, dtype=torch.float32, device=dev)
         g_w = torch.empty(N, S * 4 * F, dtype=torch.float32, device=dev)
         g_vec = torch.empty(3, N, dtype=torch.float32, device=dev)          # grad_b | grad_gamma | grad_beta
@@ -1013,14 +1026,22 @@ def _tower_train_call(which, base, edge, key, dev, aggr=None):
     _lib.check(getattr(_lib.lib(), name)(ctypes.byref(block), _lib.stream_ptr(dev)), name)
 
 
+def _row_major(params):
+    """The tower calls take every parameter as a bare pointer to row-major storage, without a pitch: one that is stored otherwise (a weight
+    re-stored as p.data.t().contiguous().t()) goes in as a contiguous copy, and autograd hands the copy's gradient to the parameter; a
+    row-major one is passed as it is."""
+    return tuple(None if p is None else p.contiguous() for p in params)
+
+
 def _tower_train_forward(ctx, h, e, layer, graph, scales, snorm, key, params, aggr=None):
     """The forward of the four tower training Functions.  e None or a layer without edge features: no edge block; key None: no dropout;
     aggr None: mean max min std through the three older entry pairs, else the layer's aggregator codes."""
     T, Fi, Fo, S = len(layer.towers), layer.input_tower, layer.output_tower, len(scales)
     dev = h.device
-    x = h if h.stride(1) == 1 else h.contiguous()
+    x = _rows(h)
     ed = layer.towers[0].edge_dim if e is not None else 0
-    ef = None if not ed else (e if (e.shape[0] == 0 or e.stride(1) == 1) else e.contiguous())
+    ef = None if not ed else _rows(e)
+    params = _row_major(params)
     plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed, aggr=aggr)
     out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
     saved = plan.new_saved()
@@ -1044,7 +1065,7 @@ def _tower_train_backward(ctx, go, lead):
     ef = params.pop(0) if ed else None
     C = T * Fo
     dev = x.device
-    go = go if go.stride(1) == 1 else go.contiguous()
+    go = _rows(go)
     need = ctx.needs_input_grad
     g_h = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
     g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if (ed and need[1]) else None
@@ -1205,9 +1226,9 @@ class EmbedSumFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, idx, *tables):
-        if idx.dim() == 2 and idx.stride(1) != 1:
-            idx = idx.contiguous()
-        tables = tuple(w if w.stride(1) == 1 else w.contiguous() for w in tables)
+        if idx.dim() == 2:
+            idx = _rows(idx)
+        tables = tuple(_rows(w) for w in tables)
         dev = tables[0].device
         out = torch.empty(idx.shape[0], tables[0].shape[1], dtype=torch.float32, device=dev)
         a = _embed_args(idx, tables)
@@ -1220,7 +1241,7 @@ class EmbedSumFn(torch.autograd.Function):
     def backward(ctx, go):
         idx, *tables = ctx.saved_tensors
         dev = go.device
-        go = go if go.stride(1) == 1 else go.contiguous()
+        go = _rows(go)
         a = _embed_args(idx, tables)
         F = tables[0].shape[1]
         rows = [w.shape[0] for w in tables]
@@ -1256,7 +1277,7 @@ class ReadoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, offsets, op):
-        h = h if h.stride(1) == 1 else h.contiguous()
+        h = _rows(h)
         V, F = h.shape
         G = offsets.numel() - 1
         dev = h.device
@@ -1274,7 +1295,7 @@ class ReadoutFn(torch.autograd.Function):
     def backward(ctx, go):
         G, V, F = ctx.shape
         dev = go.device
-        go = go if go.stride(1) == 1 else go.contiguous()
+        go = _rows(go)
         gh = torch.empty(V, F, dtype=torch.float32, device=dev)
         a = _readout_args(ctx.offsets, G, V, F, ctx.op)
         a.argmax = _lib.dev_ptr(ctx.arg, torch.int32, "argmax")
@@ -1291,11 +1312,6 @@ def readout(h, offsets, op):
 
 # ---- the GRU update between two message-passing steps: nn.GRU over a length-1 sequence as a cell over rows (pna_gru.hip) -------------
 _gru_ws = {}        # device -> the backward's reusable workspace; nothing is keyed per module: a shared GRU has several calls alive
-
-
-def _gru_rows(t):
-    """t as rows the calls take: unit column stride and a row pitch of at least the width (an expanded tensor has pitch 0)."""
-    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
 
 
 def _gru_saved(V, H, dev):
@@ -1322,7 +1338,7 @@ class GruCellFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, w_ih, w_hh, b_ih, b_hh, keep):
-        x, h, w_ih, w_hh = _gru_rows(x), _gru_rows(h), _gru_rows(w_ih), _gru_rows(w_hh)
+        x, h, w_ih, w_hh = _rows(x), _rows(h), _rows(w_ih), _rows(w_hh)
         b_ih, b_hh = b_ih.contiguous(), b_hh.contiguous()
         dev, V, H = x.device, x.shape[0], w_hh.shape[1]
         out = torch.empty(V, H, dtype=torch.float32, device=dev)
@@ -1342,7 +1358,7 @@ class GruCellFn(torch.autograd.Function):
         x, h, w_ih, w_hh, saved = ctx.saved_tensors
         dev, V, H = go.device, x.shape[0], w_hh.shape[1]
         I, Hc, IN = x.shape[1], h.shape[1], w_ih.shape[1]
-        go = _gru_rows(go)                                     # (the cotangent of out.sum(0) is an expand: strides (0, 1))
+        go = _rows(go)                                     # (the cotangent of out.sum(0) is an expand: strides (0, 1))
         need = ctx.needs_input_grad
         a = _gru_args(x, h, w_ih, w_hh)
         a.saved = _lib.dev_ptr(saved, torch.float32, "saved")
@@ -1398,8 +1414,8 @@ class MlpHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, acts, *params):
-        x = _gru_rows(x)
-        ws = [_gru_rows(w) for w in params[0::2]]
+        x = _rows(x)
+        ws = [_rows(w) for w in params[0::2]]
         bs = [None if b is None else b.contiguous() for b in params[1::2]]
         dev, V = x.device, x.shape[0]
         y = torch.empty(V, ws[-1].shape[0], dtype=torch.float32, device=dev)
@@ -1418,7 +1434,7 @@ class MlpHeadFn(torch.autograd.Function):
         ws, kept = rest[:L], list(rest[L:])
         bs = [kept.pop(0) if has else None for has in ctx.has_bias]
         dev, V = go.device, x.shape[0]
-        go = _gru_rows(go)                                     # (the cotangent of y.sum() is an expand: strides (0, 0))
+        go = _rows(go)                                     # (the cotangent of y.sum() is an expand: strides (0, 0))
         need = ctx.needs_input_grad
         a = _mlp_head_args(x, ctx.acts, ws, bs)
         a.grad_out, a.ld_go = _lib.dev_ptr(go, torch.float32, "grad_out"), go.stride(0)

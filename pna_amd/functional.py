@@ -17,7 +17,9 @@ def _unit_stride(t):
         return None
     if t.dtype != torch.float32:
         raise TypeError(f"pna_amd computes in fp32 like the reference; got {t.dtype}")
-    return t if t.stride(-1) == 1 else t.contiguous()
+    if t.stride(-1) == 1 and not (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t
+    return t.contiguous()      # (also a broadcast row, strides (0, 1): the kernels take a row pitch of at least the width)
 
 
 def aggregate(graph, x, F, aggregators, *, n_tower=1, dst_term=None, edge_term=None, row_scales=(None,),

@@ -79,7 +79,7 @@ class GRU(nn.Module):
         if PF.GRU_ROWS > 0 and self._one_call_path(x, y):
             from . import autograd as AG
             return AG.gru_cell(x, y, self.gru)
-        return self.gru(x.unsqueeze(0), y.unsqueeze(0))[1].squeeze()
+        return self.gru(x.unsqueeze(0), y.unsqueeze(0).contiguous())[1].squeeze()      # (MIOpen refuses a hidden state that is not contiguous)
 
 
 def gru_one_call_path(gru, x, y):

@@ -13,6 +13,7 @@ from pna_amd import _lib, autograd as AG, ops
 from pna_amd import functional as PF
 from pna_amd.dgl.pna_layer import PNASimpleLayer, _row_scales
 from pna_amd.graph import Graph
+from tower_train_run import pitched_input, pitched_output
 
 pytestmark = pytest.mark.gpu
 
@@ -22,20 +23,29 @@ CASES = ["simple_train_f20", "simple_train_f75", "narrow", "wide", "hand_res", "
 
 
 class _Run:
-    """One forward + backward through the two C calls on a case's inputs: every output as a tensor."""
+    """One forward + backward through the two C calls on a case's inputs: every output as a tensor.  pitches: None = every operand
+    contiguous; a dict {"h" / "out" / "go": row pitch} (the operands whose pitch the ABI carries: grad_h has none) = that operand is a
+    tower_train_run.pitched_input / pitched_output view (`buffers` keeps the outputs' whole buffers)."""
 
-    def __init__(self, name, dev, repeat=1):
+    def __init__(self, name, dev, repeat=1, pitches=None):
         meta, a, sd, ref = C.case(name)
         self.meta, self.arrays, self.sd, self.ref = meta, a, sd, ref
         V, F, N = meta["N"], meta["F"], meta["out_dim"]
         scalers = meta["scalers"].split()
         S = len(scalers)
         self.g = g = Graph(a["src"], a["dst"], V).to(dev)
+        pitches = dict(pitches or {})
+        assert set(pitches) <= {"h", "out", "go"}, pitches
+        self.pitches, self.buffers = pitches, {}
         self.h = h = a["h"].to(dev)
+        if "h" in pitches:
+            self.h = h = pitched_input(h, pitches["h"])
         self.w, self.b = sd[C.W_KEY].to(dev).contiguous(), sd[C.B_KEY].to(dev)
         self.scales = _row_scales(g, scalers, {"log": a["avg_log"]}, dev)
         self.plan = plan = AG._SmallTrainPlan(g, F, N, S, dev)
         go = a["R"].to(dev)
+        if "go" in pitches:
+            go = pitched_input(go, pitches["go"])
         self.history = []
         for _ in range(repeat):
             bn = types.SimpleNamespace(weight=sd["batchnorm_h.weight"].to(dev), bias=sd["batchnorm_h.bias"].to(dev), eps=1e-5, momentum=0.1,
@@ -44,21 +54,23 @@ class _Run:
             fbuf, ibuf = saved = plan.new_saved()
             plan.ws.fill_(float("nan"))                         # (the workspace needs no initialisation)
             out = torch.empty(V, N, device=dev)
+            if "out" in pitches:
+                out, self.buffers["out"] = pitched_output(V, N, pitches["out"], dev)
             args = plan.args(g, h, self.w, self.b, bn, self.scales, meta["residual"], saved)
-            args.out, args.ld_out = out.data_ptr(), N
+            args.out, args.ld_out = out.data_ptr(), out.stride(0)
             self.args = args
             _lib.check(_lib.lib().pna_simple_train_fwd_f32(ctypes.byref(args), _lib.stream_ptr(dev)), "fwd")
             gh, gw, gv = torch.empty(V, F, device=dev), torch.empty(N, S * 4 * F, device=dev), torch.empty(3, N, device=dev)
             plan.ws.fill_(float("nan"))                         # (the backward reads nothing the forward left there)
             args.momentum = -1.0
-            args.grad_out, args.ld_go = go.data_ptr(), N
+            args.grad_out, args.ld_go = go.data_ptr(), go.stride(0)
             args.col_t, args.rank_t, args.items_t = plan.col_t.data_ptr(), plan.rank_t.data_ptr(), plan.items_t.data_ptr()
             args.n_items_t = plan.items_t.shape[0]
             args.grad_h, args.grad_w, args.grad_b, args.grad_gamma, args.grad_beta = (gh.data_ptr(), gw.data_ptr(), gv[0].data_ptr(),
                                                                                       gv[1].data_ptr(), gv[2].data_ptr())
             _lib.check(_lib.lib().pna_simple_train_bwd_f32(ctypes.byref(args), _lib.stream_ptr(dev)), "bwd")
             torch.cuda.synchronize(dev)
-            self.bn, self.out, self.gh, self.gw, self.gv = bn, out, gh, gw, gv
+            self.bn, self.out, self.gh, self.gw, self.gv, self.go = bn, out, gh, gw, gv, go
             self.a = fbuf[:V * 4 * F].view(V, 4 * F)
             self.z = fbuf[V * 4 * F:V * 4 * F + V * N].view(V, N)
             self.stats = fbuf[V * 4 * F + V * N:].view(2, N)

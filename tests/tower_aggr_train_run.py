@@ -9,6 +9,7 @@ from pna_amd import _lib, autograd as AG
 from pna_amd.dgl.pna_layer import _row_scales
 from pna_amd.graph import Graph
 from tower_aggr_train_cases import SLOPE, codes_of
+from tower_train_run import OPERANDS, pitched_input, pitched_output
 
 NAN = float("nan")
 
@@ -19,9 +20,11 @@ class Run:
     pna_tower_edge_train_* with edge features, else pna_tower_train_*.  `repeat` calls on the same plan, each from the case's running
     statistics: `history` holds every call's outputs by name.  The workspace, the saved state, grad_e and the gradient buffers are
     NaN-filled before the call that writes them: none needs an initialisation.  tweak(which, base, edge, block): changes the argument
-    blocks just before a call (the refusal tests); expect: the return code both calls must give."""
+    blocks just before a call (the refusal tests); expect: the return code both calls must give.  pitches: None = every operand contiguous;
+    a dict {operand of tower_train_run.OPERANDS: row pitch} = that operand is a tower_train_run.pitched_input / pitched_output view
+    (`buffers` keeps the outputs' whole buffers)."""
 
-    def __init__(self, case, dev, *, old=False, repeat=1, tweak=None, expect=0):
+    def __init__(self, case, dev, *, old=False, repeat=1, tweak=None, expect=0, pitches=None):
         meta, a, sd, ref, key = case
         self.meta, self.arrays, self.sd, self.ref, self.key = meta, a, sd, ref, key
         V, T, div, ed = meta["N"], meta["towers"], meta["divide_input"], meta["edge_dim"]
@@ -33,11 +36,20 @@ class Run:
         self.T, self.Fi, self.Fo, self.S, self.ed, self.A, self.codes = T, Fi, Fo, S, ed, A, codes
         self.g = g = Graph(a["src"], a["dst"], V).to(dev)
         h, e = a["h"].to(dev), a["e"].to(dev)
+        pitches = dict(pitches or {})
+        assert set(pitches) <= set(OPERANDS), pitches
+        self.pitches, self.buffers = pitches, {}
+        if "h" in pitches:
+            h = pitched_input(h, pitches["h"])
+        if "e" in pitches and ed:
+            e = pitched_input(e, pitches["e"])
         sn = a["snorm_n"].reshape(-1).to(dev).contiguous()
         scales = _row_scales(g, scalers, {"log": a["avg_log"]}, dev)
         dsd = {k: v.to(dev) for k, v in sd.items()}
         self.plan = plan = AG._TowerTrainPlan(g, T, Fi, Fo, S, div, dev, edge_dim=ed, aggr=None if old else codes)
         go = a["R"].to(dev)
+        if "go" in pitches:
+            go = pitched_input(go, pitches["go"])
         L, st = _lib.lib(), _lib.stream_ptr(dev)
         names = [(f"towers.{t}.pretrans.fully_connected.0.linear.", f"towers.{t}.posttrans.fully_connected.0.linear.", f"towers.{t}.batchnorm_h.")
                  for t in range(T)]
@@ -71,11 +83,15 @@ class Run:
             saved[1].fill_(-7)
             plan.ws.fill_(NAN)                                  # (the workspace needs no initialisation)
             out = torch.full((V, Cc), NAN, device=dev)
+            if "out" in pitches:
+                out, self.buffers["out"] = pitched_output(V, Cc, pitches["out"], dev)
             args = plan.args(g, h, sn, scales, towers, dsd["mixing_network.linear.weight"], dsd["mixing_network.linear.bias"], SLOPE, meta["residual"], saved)
-            args.out, args.ld_out = out.data_ptr(), Cc
+            args.out, args.ld_out = out.data_ptr(), out.stride(0)
             call("fwd", args, plan.edge_args(args, e, saved) if ed else None, saved)
             gh = torch.full((V, meta["in_dim"]), NAN, device=dev)
             ge = torch.full((e.shape[0], ed), NAN, device=dev) if ed else None
+            if ed and "ge" in pitches:
+                ge, self.buffers["ge"] = pitched_output(e.shape[0], ed, pitches["ge"], dev)
             grads, named = [], {}
             for pre, post, bn in names:
                 gt = (torch.empty(Fi, 2 * Fi + ed, device=dev), torch.empty(Fi, device=dev), torch.empty(Fo, (1 + A * S) * Fi, device=dev),
@@ -89,7 +105,7 @@ class Run:
             plan.ws.fill_(NAN)                                  # (the backward reads nothing the forward left there)
             plan.set_backward(args, go, gh, grads, gmw, gmb)
             qb = plan.edge_args(args, e, saved, grad_e=ge, backward=True) if ed else None
-            self.keep = (towers, grads, go, ge, args, qb)
+            self.keep, self.saved = (towers, grads, go, ge, args, qb), saved
             call("bwd", args, qb, saved)
             self.out, self.gh, self.ge, self.grads, self.running = out, gh, ge, named, running
             self.x_cat, self.a, self.z, self.p, self.stats, self.amx, self.amn = plan.views(saved)
