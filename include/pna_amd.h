@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PNA_ABI_VERSION 23 /* 23, additive: + pna_tower_aggr_train_fwd_f32 / pna_tower_aggr_train_bwd_f32 / pna_tower_aggr_train_workspace_bytes /
+#define PNA_ABI_VERSION 23 /* 23, additive: + pna_pyg_conv_train_fwd_f32 / pna_pyg_conv_train_bwd_f32 / pna_pyg_conv_train_workspace_bytes /
+                                  pna_pyg_conv_train_args (PNAConv's training forward and backward, one call each, on the kernels of the
+                                  tower training routes without BatchNorm and with the PyG statistics); no existing struct or entry point changed.
+                                  23, additive: + pna_tower_aggr_train_fwd_f32 / pna_tower_aggr_train_bwd_f32 / pna_tower_aggr_train_workspace_bytes /
                                   pna_tower_aggr_train_args (the one-call tower training routes for any 1-4 distinct aggregators out of mean,
                                   sum, max, min, std, var, with or without edge features and dropout); no existing struct or entry point changed.
                                   23, additive: + pna_batch_plan_i32 / pna_batch_plan_limits / pna_batch_plan_workspace_bytes / pna_batch_plan_args (every
@@ -1699,6 +1702,57 @@ int64_t pna_tower_aggr_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tow
                                              int32_t edge_dim /* 0 = none */, int32_t n_aggr, const int32_t* aggr);   /* -1 outside the scope */
 int pna_tower_aggr_train_fwd_f32(const pna_tower_aggr_train_args* args, pna_stream_t stream);
 int pna_tower_aggr_train_bwd_f32(const pna_tower_aggr_train_args* args, pna_stream_t stream);
+
+/* ---- PNAConv (the PyG formulation) TRAINING on molecule batches: forward and backward as ONE call each ----------------------------
+ * replaces: models/pytorch_geometric/pna.py:120-159 (forward, message, aggregate and update of PNAConv with pre_layers == post_layers
+ * == 1: per tower pre_nn on [x_i | x_j | edge_encoder(edge_attr)], the aggregators of aggregators.py:6-32 and the scalers of
+ * scalers.py:7-29 on the result, post_nn on [x | aggregate], cat, lin) and what autograd derives from it in loss.backward().
+ *
+ * The kernels are those of pna_tower_aggr_train_*_f32 in two modes that only these entries switch on:
+ *   no BatchNorm    hcat = z (the forward launches no column-sum and no finalise kernel), gz = g_hcat; base->gamma / beta / running_* /
+ *                   save_mean / save_invstd / eps / momentum / grad_gamma / grad_beta are NOT read and may be NULL / 0;
+ *   PyG statistics  var = E[m0^2] - E[m0]^2 NOT clamped, its gradient 2 G_var / D (m0 - mean0) without the [var > 0] gate
+ *                   (aggregators.py:25-28); std = sqrt(relu(var) + 1e-5) (:31-32); a row without in-edges has std = sqrtf(1e-5f) with a
+ *                   zero gradient and 0 in every other block (the rules of PNA_AGG_STD_PYG and PNA_AGG_VAR_RAW; the list itself is
+ *                   written with PNA_AGG_MEAN .. PNA_AGG_VAR).
+ * lin is a plain Linear: the entries run the mixing launch with slope 1.0f (leaky(p) = p and go * slope = go exactly), whatever
+ * base->slope holds.  base->snorm_n must be NULL and base->residual 0 (the layer has neither).  drop must be NULL.
+ *
+ * The layer's tensors, read as the optimiser leaves them: w_pre[t] (Fi, (2 | 3) Fi) = [W_i | W_j | W_e] with x_i the DESTINATION
+ * (pna.py:145), b_pre[t] [Fi], and with edge features w_enc (Fi, edge_dim), b_enc [Fi] of edge_encoder.  base->w_pre / b_pre /
+ * grad_w_pre / grad_b_pre are NOT read: the forward's first launch PACKS, per tower, the tower call's image
+ *   [W_j,t | W_i,t | M_t] (Fi, 2 Fi + edge_dim), M_t = W_e,t W_enc, and the bias b_t + W_e,t b_enc
+ * into `packed` (saved: n_tower Fi (2 Fi + edge_dim + 1) floats, the T images first, then the T biases; the backward reads the
+ * forward's image), and the tower call runs as the edge route on e = edge_attr itself: no (E, Fi) encoded tensor exists, and the bound
+ * is edge_dim <= 64.  The backward's last launch UNPACKS the tower call's gW'_t = [gA | gB | gM_t], gb'_t (in the workspace):
+ *   grad_w_pre[t] = [gB | gA | gM_t W_enc^T + gb'_t b_enc^T], grad_b_pre[t] = gb'_t,
+ *   grad_w_enc = sum_t W_e,t^T gM_t, grad_b_enc = sum_t W_e,t^T gb'_t (both in tower order),
+ * and grad_e is the edge route's under M_t.  Every product of the pack and the unpack is a float64 FMA chain in index order (k, then
+ * for the sums over towers t outermost), rounded to fp32 once.  No float atomics: two calls give identical bits.
+ * Launches: forward 1 (pack) + 3 (4 with edge features); backward 5 (6 with edge features when grad_e is wanted) + 2 per weight gradient
+ * (3 n_tower + 1 of them, 4 n_tower + 1 with edge features) + 1 (unpack).
+ * Scope (PNA_E_INVALID outside it, the workspace query returns -1): that of pna_tower_aggr_train_*_f32 -- 1 <= n_tower <= 8,
+ * 4 <= Fi <= 128, n_tower Fi <= 512, n_tower Fo <= 128, 1-4 distinct aggregators, 1-3 scalers (base->row_scale, already with the
+ * deg == 0 rules of scalers.py:16-19, 26-29), edge_dim 0 (aggr->edge == NULL, w_enc == b_enc == NULL) or 1..64, V >= 2. */
+typedef struct pna_pyg_conv_train_args {
+  uint32_t struct_size;    /* sizeof(pna_pyg_conv_train_args) of the CALLER's header: a shorter struct is refused with PNA_E_INVALID */
+  uint32_t _abi_reserved;  /* 0 */
+  const pna_tower_aggr_train_args* aggr;   /* its base and edge members as above; the workspace has pna_pyg_conv_train_workspace_bytes(...) bytes */
+  const float* w_pre[PNA_MAX_TOWER];       /* first n_tower of each: (Fi, 2 Fi) or (Fi, 3 Fi), contiguous */
+  const float* b_pre[PNA_MAX_TOWER];       /* [Fi] */
+  const float* w_enc;                      /* (Fi, edge_dim) contiguous, or NULL without edge features */
+  const float* b_enc;                      /* [Fi], with w_enc */
+  float* packed;                           /* saved, n_tower Fi (2 Fi + edge_dim + 1) floats: forward writes, backward reads */
+  float* grad_w_pre[PNA_MAX_TOWER];        /* backward: the parameters' shapes, contiguous */
+  float* grad_b_pre[PNA_MAX_TOWER];
+  float* grad_w_enc;                       /* backward, with w_enc */
+  float* grad_b_enc;
+} pna_pyg_conv_train_args;
+
+int64_t pna_pyg_conv_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input,
+                                           int32_t edge_dim /* 0 = none */, int32_t n_aggr, const int32_t* aggr);   /* -1 outside the scope */
+int pna_pyg_conv_train_fwd_f32(const pna_pyg_conv_train_args* args, pna_stream_t stream);
+int pna_pyg_conv_train_bwd_f32(const pna_pyg_conv_train_args* args, pna_stream_t stream);
 
 /* ---- The two ENDS of the molecule nets: the sum of embedding tables and the per-graph readout, one call each way ----------------
  * replaces: ogb's AtomEncoder as nets/HIV_graph_classification/pna_net.py:42 calls it (a sum of nine nn.Embedding lookups), the single

@@ -398,6 +398,15 @@ class PnaTowerAggrTrainArgs(_Args):
     ]
 
 
+class PnaPygConvTrainArgs(_Args):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32), ("aggr", ctypes.c_void_p),
+        ("w_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("b_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("w_enc", ctypes.c_void_p),
+        ("b_enc", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("grad_w_pre", ctypes.c_void_p * PNA_MAX_TOWER),
+        ("grad_b_pre", ctypes.c_void_p * PNA_MAX_TOWER), ("grad_w_enc", ctypes.c_void_p), ("grad_b_enc", ctypes.c_void_p),
+    ]
+
+
 class PnaEmbedSumArgs(_Args):
     _fields_ = [
         ("struct_size", ctypes.c_uint32), ("_abi_reserved", ctypes.c_uint32),
@@ -666,6 +675,11 @@ def lib():
         L.pna_tower_aggr_train_workspace_bytes.restype = ctypes.c_int64
         for fn in (L.pna_tower_aggr_train_fwd_f32, L.pna_tower_aggr_train_bwd_f32):
             fn.argtypes = [ctypes.POINTER(PnaTowerAggrTrainArgs), ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+        L.pna_pyg_conv_train_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 7 + [ctypes.POINTER(ctypes.c_int32)]
+        L.pna_pyg_conv_train_workspace_bytes.restype = ctypes.c_int64
+        for fn in (L.pna_pyg_conv_train_fwd_f32, L.pna_pyg_conv_train_bwd_f32):
+            fn.argtypes = [ctypes.POINTER(PnaPygConvTrainArgs), ctypes.c_void_p]
             fn.restype = ctypes.c_int
         L.pna_dropout_mask_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                            ctypes.c_void_p]

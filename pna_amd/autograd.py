@@ -848,8 +848,9 @@ class _TowerTrainPlan(_GraphScratchPlan):
     them: a, the posttrans weight's gradient and the workspace are sized by A; None = mean max min std, A = 4); its backward is the
     per-edge one, so it holds pos_t also without edge features, and the saved state ends with row_mean (V, T Fi)."""
 
-    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev, edge_dim=0, aggr=None):
+    def __init__(self, graph, T, Fi, Fo, S, divide_input, dev, edge_dim=0, aggr=None, pyg=False):
         V, E = graph.num_nodes, int(graph.csr.col.numel())
+        self.pyg = bool(pyg)                                      # the plan of pna_pyg_conv_train_*_f32: its workspace, `packed` last in the saved state
         self.V, self.E, self.T, self.Fi, self.Fo, self.S, self.div, self.dev = V, E, T, Fi, Fo, S, bool(divide_input), dev
         self.edge_dim = int(edge_dim)
         self.aggr = None if aggr is None else tuple(int(c) for c in aggr)
@@ -857,7 +858,10 @@ class _TowerTrainPlan(_GraphScratchPlan):
         self.col_t, self.rank_t, self.items_t = _transposed_whole_rows(graph)
         if self.edge_dim:
             self.eid = graph.edge_ids32()
-        if self.aggr is not None:
+        if self.pyg:
+            nbytes = _lib.lib().pna_pyg_conv_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div), self.edge_dim, self.A,
+                                                                   (ctypes.c_int32 * self.A)(*self.aggr))
+        elif self.aggr is not None:
             nbytes = _lib.lib().pna_tower_aggr_train_workspace_bytes(V, E, T, Fi, Fo, S, int(self.div), self.edge_dim, self.A,
                                                                      (ctypes.c_int32 * self.A)(*self.aggr))
         elif self.edge_dim:
@@ -878,7 +882,8 @@ class _TowerTrainPlan(_GraphScratchPlan):
         save_invstd [C] [| x_edge (E, T Fi)] [| row_mean (V, T Fi)] in one buffer, argmax | argmin (V, T Fi) in another.  Per CALL, not
         per plan: two layers of one shape on one graph are both alive until their backwards."""
         V, TFi, C = self.V, self.T * self.Fi, self.T * self.Fo
-        fbuf = torch.empty(self._float_end() + (V * TFi if self.aggr is not None else 0), dtype=torch.float32, device=self.dev)
+        fbuf = torch.empty(self._float_end() + (V * TFi if self.aggr is not None else 0) + (self.packed_floats() if self.pyg else 0),
+                           dtype=torch.float32, device=self.dev)
         ibuf = torch.empty(2, V, TFi, dtype=torch.int32, device=self.dev)
         return fbuf, ibuf
 
@@ -908,6 +913,15 @@ class _TowerTrainPlan(_GraphScratchPlan):
         """The (V, T Fi) row_mean of an aggregator-list plan's saved state (the last piece)."""
         o, n = self._float_end(), self.V * self.T * self.Fi
         return saved[0][o:o + n].view(self.V, self.T * self.Fi)
+
+    def packed_floats(self):
+        """The floats of a PyG plan's packed pretrans image: per tower (Fi, 2 Fi + edge_dim) and a bias."""
+        return self.T * self.Fi * (2 * self.Fi + self.edge_dim + 1)
+
+    def packed(self, saved):
+        """The packed image of a PyG plan's saved state (the last piece, behind row_mean)."""
+        o = self._float_end() + self.V * self.T * self.Fi
+        return saved[0][o:o + self.packed_floats()]
 
     def aggr_args(self, base, edge, key, saved, backward=False):
         """The pna_tower_aggr_train_args around `base`, `edge` (or None) and the mask key (p, seed, offset) (or None)."""
@@ -1638,3 +1652,111 @@ def tower_layer_aggr_small_train(layer, graph, h, e, snorm_n, scales):
         key = (p, seed, offset)
     aggr = tuple(_lib.AGG_CODES[n] for n in layer.towers[0].aggregators)
     return TowerLayerAggrSmallTrainFn.apply(h, e if layer.edge_features else None, layer, graph, tuple(scales), snorm, key, aggr, *params)
+
+
+def _pyg_conv_args(plan, r, pre, enc, saved, grads=None):
+    """The pna_pyg_conv_train_args around the list block `r`: the layer's own pretrans tensors `pre` = [(w_pre, b_pre)] per tower and
+    `enc` = (w_enc, b_enc) or None; grads = ([(grad_w_pre, grad_b_pre)], (grad_w_enc, grad_b_enc) or None) in a backward."""
+    y = _lib.PnaPygConvTrainArgs()
+    y.aggr = ctypes.cast(ctypes.pointer(r), ctypes.c_void_p)
+    for t, (w, b) in enumerate(pre):
+        y.w_pre[t], y.b_pre[t] = w.data_ptr(), b.data_ptr()
+    if enc is not None:
+        y.w_enc, y.b_enc = _lib.dev_ptr(enc[0], torch.float32, "w_enc"), _lib.dev_ptr(enc[1], torch.float32, "b_enc")
+    y.packed = plan.packed(saved).data_ptr()
+    if grads is not None:
+        for t, (gw, gb) in enumerate(grads[0]):
+            y.grad_w_pre[t], y.grad_b_pre[t] = gw.data_ptr(), gb.data_ptr()
+        if grads[1] is not None:
+            y.grad_w_enc, y.grad_b_enc = grads[1][0].data_ptr(), grads[1][1].data_ptr()
+    y._keep = r
+    return y
+
+
+def _pyg_conv_call(which, y, dev):
+    """pna_pyg_conv_train_fwd_f32 or pna_pyg_conv_train_bwd_f32 (`which` = "fwd" or "bwd") on the block `y`."""
+    name = f"pna_pyg_conv_train_{which}_f32"
+    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(y), _lib.stream_ptr(dev)), name)
+
+
+def _pyg_towers(params, T):
+    """Per tower (w_pre, b_pre, w_post, b_post, no BatchNorm: gamma, beta, running_mean, running_var None, eps 0, momentum < 0) for
+    _TowerTrainPlan.args out of PygConvFn's params."""
+    return [(*params[4 * t:4 * t + 4], None, None, None, None, 0.0, -1.0) for t in range(T)]
+
+
+class PygConvFn(torch.autograd.Function):
+    """pytorch_geometric.PNAConv with pre_layers == post_layers == 1 (models/pytorch_geometric/pna.py:120-159) on a molecule-sized batch
+    as ONE C call (pna_pyg_conv_train_fwd_f32) and its backward as one (pna_pyg_conv_train_bwd_f32): the kernels of the tower training
+    routes without BatchNorm and with the PyG statistics, behind a pack launch that turns the layer's [W_i | W_j | W_e] and its edge
+    encoder into the tower call's image (DESIGN.md 4.29).  `e` (E, edge_dim) in edge_index order, None for a layer without edge_dim;
+    `aggr` the aggregator codes in the layer's order; `params`: per tower w_pre, b_pre, w_post, b_post, then lin's weight and bias, then
+    with edge features the encoder's weight and bias.  A call under no_grad is the forward alone."""
+
+    @staticmethod
+    def forward(ctx, x, e, layer, graph, scales, aggr, *params):
+        T, Fi, Fo, S = layer.towers, layer.F_in, layer.F_out, len(scales)
+        dev = x.device
+        x = _rows(x)
+        ed = int(layer.edge_dim) if e is not None else 0
+        ef = _rows(e) if ed else None
+        params = _row_major(params)
+        plan = _TowerTrainPlan(graph, T, Fi, Fo, S, layer.divide_input, dev, edge_dim=ed, aggr=aggr, pyg=True)
+        out = torch.empty(plan.V, T * Fo, dtype=torch.float32, device=dev)
+        saved = plan.new_saved()
+        a = plan.args(graph, x, None, scales, _pyg_towers(params, T), params[4 * T], params[4 * T + 1], 1.0, False, saved)
+        a.out, a.ld_out = _lib.dev_ptr(out, torch.float32, "out"), out.stride(0)
+        q = plan.edge_args(a, ef, saved) if ed else None
+        r = plan.aggr_args(a, q, None, saved)
+        y = _pyg_conv_args(plan, r, [params[4 * t:4 * t + 2] for t in range(T)], params[4 * T + 2:4 * T + 4] if ed else None, saved)
+        _pyg_conv_call("fwd", y, dev)
+        ctx.plan, ctx.graph, ctx.scales, ctx.state = plan, graph, scales, saved
+        ctx.save_for_backward(x, *([ef] if ed else []), *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, *params = ctx.saved_tensors
+        plan = ctx.plan
+        T, Fi, Fo, S, ed = plan.T, plan.Fi, plan.Fo, plan.S, plan.edge_dim
+        ef = params.pop(0) if ed else None
+        C = T * Fo
+        dev = x.device
+        go = _rows(go)
+        need = ctx.needs_input_grad
+        g_x = torch.empty(plan.V, x.shape[1], dtype=torch.float32, device=dev)
+        g_e = torch.empty(plan.E, ed, dtype=torch.float32, device=dev) if (ed and need[1]) else None
+        g_wpre = torch.empty(T, Fi, (3 if ed else 2) * Fi, dtype=torch.float32, device=dev)
+        g_wpost = torch.empty(T, Fo, (1 + plan.A * S) * Fi, dtype=torch.float32, device=dev)
+        g_bpre = torch.empty(T, Fi, dtype=torch.float32, device=dev)
+        g_bpost = torch.empty(T, Fo, dtype=torch.float32, device=dev)
+        g_mix = torch.empty(C + 1, C, dtype=torch.float32, device=dev)       # grad of lin's weight | bias
+        g_enc = torch.empty(Fi, ed + 1, dtype=torch.float32, device=dev).view(-1) if ed else None
+        enc_grads = (g_enc[:Fi * ed].view(Fi, ed), g_enc[Fi * ed:]) if ed else None
+        mix_w, mix_b = params[4 * T], params[4 * T + 1]
+        a = plan.args(ctx.graph, x, None, ctx.scales, _pyg_towers(params, T), mix_w, mix_b, 1.0, False, ctx.state)
+        plan.set_backward(a, go, g_x, [(g_wpre[t], g_bpre[t], g_wpost[t], g_bpost[t], None, None) for t in range(T)], g_mix[:C], g_mix[C])
+        q = plan.edge_args(a, ef, ctx.state, grad_e=g_e, backward=True) if ed else None
+        r = plan.aggr_args(a, q, None, ctx.state, backward=True)
+        y = _pyg_conv_args(plan, r, [params[4 * t:4 * t + 2] for t in range(T)], params[4 * T + 2:4 * T + 4] if ed else None, ctx.state,
+                           grads=([(g_wpre[t], g_bpre[t]) for t in range(T)], enc_grads))
+        _pyg_conv_call("bwd", y, dev)
+        res = [g_x, g_e, None, None, None, None]
+        for t in range(T):
+            res += [g_wpre[t], g_bpre[t], g_wpost[t], g_bpost[t]]
+        res += [g_mix[:C], g_mix[C]]
+        if ed:
+            res += list(enc_grads)
+        return tuple(r_ if (r_ is None or need[i]) else None for i, r_ in enumerate(res))
+
+
+def pyg_conv_one_call(layer, graph, x, edge_attr, scales):
+    """lin(cat_t post_nn_t([x_t | scalers(aggregators(pre_nn_t([x_i | x_j | enc(e)])))])) of a PNAConv through PygConvFn."""
+    params = []
+    for pre, post in zip(layer.pre_nns, layer.post_nns):
+        params += [pre[0].weight, pre[0].bias, post[0].weight, post[0].bias]
+    params += [layer.lin.weight, layer.lin.bias]
+    if layer.edge_dim is not None:
+        params += [layer.edge_encoder.weight, layer.edge_encoder.bias]
+    aggr = tuple(_lib.AGG_CODES[n] for n in layer.aggregator_names)
+    return PygConvFn.apply(x, edge_attr if layer.edge_dim is not None else None, layer, graph, tuple(scales), aggr, *params)

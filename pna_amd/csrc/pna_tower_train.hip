@@ -25,6 +25,12 @@
 // and every aggregator ablation): KArgs carries the block index of each aggregator inside a tower's aggregate, -1 when it is not listed,
 // read under wavefront-uniform branches.  The three entry pairs above fill it with {mean, max, min, std} and run the same kernels in the
 // same arithmetic sequence.  That route's backward is always the per-edge one (k_tt_edge_dm + k_tt_edge_pull), with or without x_edge.
+//
+// PNAConv, the PyG formulation (pna_pyg_conv_train_*_f32: models/pytorch_geometric/pna.py:120-159): the same kernels in two modes of
+// KArgs -- nobn (no BatchNorm: hcat = z, gz = g_hcat, no column sums, no finalise launches) and pyg (aggregators.py:25-32: var not
+// clamped and not gated, std of a row without in-edges sqrt(1e-5)) -- behind k_pyg_pack, which turns the layer's [W_i | W_j | W_e] and its
+// edge encoder into the tower call's [W_a | W_b | W_e W_enc], and in front of k_pyg_unpack, which turns that image's gradient back.
+// Every other entry runs with both modes 0: the same branches taken, the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -84,17 +90,20 @@ struct KArgs {
   float* dm; float* ecsr;                                   // backward (E, T Fi) message gradient, (E, ED) copy of e, both in CSR order
   float* ge; long ld_ge;                                    // backward (E, ld_ge), original edge order, or NULL
   pna_philox::Mask drop;                                    // pna_tower_drop_train_*: the dropout between the BatchNorms and the mixing Linear
+  int nobn;                                                 // pna_pyg_conv_train_*: no BatchNorm at all -- hcat = z, gz = g_hcat [snorm]; no column sums
+  int pyg;                                                  // the PyG statistics: var not clamped (no gate in its gradient), std of a row without in-edges sqrt(1e-5)
 };
 
 __device__ __forceinline__ float leaky(float p, float slope) { return p > 0.f ? p : p * slope; }
 
 // var of one feature of one destination row (models/dgl/aggregators.py:22-26): pna_dev::row_stats' radicand before the + 1e-5, op by op
-__device__ __forceinline__ float row_var(float s, float q, int deg) {
+// raw (models/pytorch_geometric/aggregators.py:25-28): the same difference, NOT clamped
+__device__ __forceinline__ float row_var(float s, float q, int deg, bool raw) {
   if (deg <= 0) return 0.f;
   const float D = (float)deg, invD = 1.0f / D;
   const float mean = pna_dev::div_rn(s, D, invD), msq = pna_dev::div_rn(q, D, invD);
   const float var = msq - mean * mean;
-  return var < 0.f ? 0.f : var;
+  return (var < 0.f && !raw) ? 0.f : var;
 }
 
 // ---- forward, launch 1: x_cat = [x_src | x_dst], x_src,t = W_a,t h_t, x_dst,t = W_b,t h_t + b_t, of 16 rows ----------------------
@@ -273,6 +282,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
           float mean, omx, omn, sd, m0, x0, n0;
           pna_dev::row_stats(s[j], q[j], mx[j], mn[j], end - beg, mean, omx, omn, sd);     // mean | max | min of the shifted messages
           pna_dev::row_stats(s0[j], q0[j], mx[j], mn[j], end - beg, m0, x0, n0, sd);       // std of x_src alone
+          if (g.pyg && end == beg) sd = sqrtf(1e-5f);       // (models/pytorch_geometric/aggregators.py:31-32 on an empty segment)
           float* const al = A + r * P + c;
           float* const ag = g.a + (size_t)row * T * K + (size_t)t * K + c;
           if (g.b_mean >= 0) { al[g.b_mean * Fi] = mean; ag[g.b_mean * Fi] = mean; }            // (every branch on the list is wavefront-uniform)
@@ -281,7 +291,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
           if (g.b_std >= 0) { al[g.b_std * Fi] = sd; ag[g.b_std * Fi] = sd; }
           if (g.b_sum >= 0) { al[g.b_sum * Fi] = s[j]; ag[g.b_sum * Fi] = s[j]; }               // the fold's own sum (0 without in-edges)
           if (g.b_var >= 0) {
-            const float vr = row_var(s0[j], q0[j], end - beg);
+            const float vr = row_var(s0[j], q0[j], end - beg, g.pyg != 0);
             al[g.b_var * Fi] = vr; ag[g.b_var * Fi] = vr;
           }
           if (g.rowmean) g.rowmean[(size_t)row * TFi + t * Fi + c] = m0;
@@ -341,6 +351,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_fwd(const KArgs g) {
     __syncthreads();
   }
   // ---- the tile's BatchNorm column sums, shifted by the tile's first row (the finalize pass re-bases them in float64) ----
+  if (g.nobn) return;                                       // (uniform: no BatchNorm, nobody reads the sums)
   for (int c = tid; c < C; c += kThreads) {
     const float kc = Z[c];
     float s0 = 0.f, s1 = 0.f;
@@ -416,9 +427,13 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_fwd(const KArgs g) {
       const int r = i / P, c = i - r * P;
       float v = 0.f;
       if (c < C && r < nrows) {
-        float cm, ci, ca, cb;
-        bn_consts(g, c, cm, ci, ca, cb);
-        v = bn_affine(g.z[(size_t)(r0 + r) * C + c], cm, ca, cb);
+        if (g.nobn) {
+          v = g.z[(size_t)(r0 + r) * C + c];
+        } else {
+          float cm, ci, ca, cb;
+          bn_consts(g, c, cm, ci, ca, cb);
+          v = bn_affine(g.z[(size_t)(r0 + r) * C + c], cm, ca, cb);
+        }
       }
       HC[i] = v;
     }
@@ -481,9 +496,13 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_bwd(const KArgs g) {
       v = p > 0.f ? go : go * g.slope;
       g.gp[row * C + c] = v;
       if constexpr (!DROP) {
-        float cm, ci, ca, cb;
-        bn_consts(g, c, cm, ci, ca, cb);
-        g.hcat[row * C + c] = bn_affine(g.z[row * C + c], cm, ca, cb);
+        if (g.nobn) {
+          g.hcat[row * C + c] = g.z[row * C + c];
+        } else {
+          float cm, ci, ca, cb;
+          bn_consts(g, c, cm, ci, ca, cb);
+          g.hcat[row * C + c] = bn_affine(g.z[row * C + c], cm, ca, cb);
+        }
       }
     }
     GP[i] = v;
@@ -532,6 +551,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_mix_bwd(const KArgs g) {
       }
     }
   }
+  if (g.nobn) return;                                       // (uniform: no mean terms, no grad_gamma / grad_beta)
   __syncthreads();
   for (int c = tid; c < C; c += kThreads) {
     const float cm = g.mean[c], ci = g.invstd[c];
@@ -593,10 +613,14 @@ __global__ __launch_bounds__(kThreads) void k_tt_rows_bwd(const KArgs g) {
     if (n < Fo && r < nrows) {
       const int c = t * Fo + n;
       const size_t row = (size_t)(r0 + r);
-      float cm, ci, ca, cb;
-      bn_consts(g, c, cm, ci, ca, cb);
-      // pna_bn_tail's backward apply, op by op; the graph-norm factor last
-      val = ca * ((g.ghc[row * C + c] - g.cm[c]) - ((g.z[row * C + c] - cm) * ci) * g.cm[C + c]);
+      if (g.nobn) {
+        val = g.ghc[row * C + c];
+      } else {
+        float cm, ci, ca, cb;
+        bn_consts(g, c, cm, ci, ca, cb);
+        // pna_bn_tail's backward apply, op by op; the graph-norm factor last
+        val = ca * ((g.ghc[row * C + c] - g.cm[c]) - ((g.z[row * C + c] - cm) * ci) * g.cm[C + c]);
+      }
       if (g.snorm) val = val * SC[3 * kRows + r];
       g.gz[row * C + c] = val;
     }
@@ -757,7 +781,7 @@ __global__ __launch_bounds__(kThreads) void k_tt_edge_dm(const KArgs g) {
         }
         if (g.b_var >= 0) {
           const float Gv = g.gagg[oa + g.b_var * Fi], vr = g.a[oa + g.b_var * Fi];
-          r2 = r2 + ((D > 0 && vr > 0.f) ? (2.0f * Gv) / fD : 0.f);
+          r2 = r2 + ((D > 0 && (g.pyg || vr > 0.f)) ? (2.0f * Gv) / fD : 0.f);
         }
         const float sh = g.rowmean ? g.rowmean[oc] : mean - xd;     // the mean of m0 over the row
         if (ok) g.gxd[oc] = D > 0 ? gd : 0.f;
@@ -904,8 +928,9 @@ struct Aggr {
   bool general;
   float* row_mean;
   const int32_t* pos_t;
+  bool pyg;                     // pna_pyg_conv_train_*: no BatchNorm and the PyG statistics
 };
-const Aggr kStandard = {4, {0, -1, 1, 2, 3, -1}, false, nullptr, nullptr};      // mean | max | min | std
+const Aggr kStandard = {4, {0, -1, 1, 2, 3, -1}, false, nullptr, nullptr, false};      // mean | max | min | std
 
 // the list of a pna_tower_aggr_train call: 1..4 distinct codes out of PNA_AGG_MEAN .. PNA_AGG_VAR
 bool read_list(int n_aggr, const int32_t* aggr, Aggr& ag) {
@@ -916,7 +941,7 @@ bool read_list(int n_aggr, const int32_t* aggr, Aggr& ag) {
     if (aggr[i] < PNA_AGG_MEAN || aggr[i] > PNA_AGG_VAR || ag.b[aggr[i]] >= 0) return false;
     ag.b[aggr[i]] = i;
   }
-  ag.general = true; ag.row_mean = nullptr; ag.pos_t = nullptr;
+  ag.general = true; ag.row_mean = nullptr; ag.pos_t = nullptr; ag.pyg = false;
   return true;
 }
 bool needs_row_mean(const Aggr& ag) { return (ag.b[PNA_AGG_STD] >= 0 || ag.b[PNA_AGG_VAR] >= 0) && ag.b[PNA_AGG_MEAN] < 0; }
@@ -962,7 +987,7 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
   const int in_dim = p->divide_input ? T * Fi : Fi, C = T * Fo;
   if (p->residual && in_dim != C) return pna_set_error(PNA_E_INVALID, who);
   if (!p->rowptr || (p->E > 0 && !p->col) || !p->h || p->ldh < in_dim || !p->w_mix || !p->x_cat || !p->a || (ag.b[PNA_AGG_MAX] >= 0 && !p->argmax) || (ag.b[PNA_AGG_MIN] >= 0 && !p->argmin) || !p->z || !p->p ||
-      !p->save_mean || !p->save_invstd || !p->workspace || ((uintptr_t)p->workspace & 255))
+      (!ag.pyg && (!p->save_mean || !p->save_invstd)) || !p->workspace || ((uintptr_t)p->workspace & 255))
     return pna_set_error(PNA_E_INVALID, who);
   for (int t = 0; t < T; ++t)
     if (!p->w_pre[t] || !p->b_pre[t] || !p->w_post[t] || !p->b_post[t] || (p->gamma[t] == nullptr) != (p->beta[t] == nullptr) ||
@@ -995,6 +1020,7 @@ int fill(const pna_tower_train_args* p, KArgs& g, Layout& l, bool bwd, const cha
   g.b_mean = ag.b[PNA_AGG_MEAN]; g.b_sum = ag.b[PNA_AGG_SUM]; g.b_max = ag.b[PNA_AGG_MAX]; g.b_min = ag.b[PNA_AGG_MIN];
   g.b_std = ag.b[PNA_AGG_STD]; g.b_var = ag.b[PNA_AGG_VAR];
   g.rowmean = needs_row_mean(ag) ? ag.row_mean : nullptr;
+  g.nobn = ag.pyg; g.pyg = ag.pyg;
   g.h = p->h; g.ldh = (long)p->ldh; g.snorm = p->snorm_n;
   for (int s = 0; s < 3; ++s) g.scale[s] = s < S ? p->row_scale[s] : nullptr;
   for (int t = 0; t < T; ++t) {
@@ -1056,7 +1082,7 @@ int launch_fwd(const KArgs& g, const Layout& l, hipStream_t st, const char* fail
   if (g.S == 1) hipLaunchKernelGGL((k_tt_rows_fwd<1, EDGE>), grid, block, lds, st, g);
   else if (g.S == 2) hipLaunchKernelGGL((k_tt_rows_fwd<2, EDGE>), grid, block, lds, st, g);
   else hipLaunchKernelGGL((k_tt_rows_fwd<3, EDGE>), grid, block, lds, st, g);
-  hipLaunchKernelGGL(k_tt_bn_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
+  if (!g.nobn) hipLaunchKernelGGL(k_tt_bn_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
   hipLaunchKernelGGL(k_tt_mix_fwd<DROP>, grid, block, (size_t)kRows * pitch_of(quads(C)) * sizeof(float), st, g);
   if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, failed);
   return PNA_OK;
@@ -1073,7 +1099,7 @@ int launch_bwd(const pna_tower_train_args* p, const KArgs& g, const Layout& l, p
   const size_t lds_mix = ((size_t)kRows * pitch_of(quads(C)) + (size_t)kRows * (C + 1)) * sizeof(float);
   if (drop) hipLaunchKernelGGL(k_tt_mix_bwd<true>, grid, block, lds_mix, st, g);
   else hipLaunchKernelGGL(k_tt_mix_bwd<false>, grid, block, lds_mix, st, g);
-  hipLaunchKernelGGL(k_tt_bwd_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
+  if (!g.nobn) hipLaunchKernelGGL(k_tt_bwd_finalize, dim3((unsigned)C), dim3(256), 0, st, g);
   const size_t lds = ((size_t)T * kRows * pitch_of(quads(Fo)) + 4 * kRows) * sizeof(float);
   if (S == 1) hipLaunchKernelGGL(k_tt_rows_bwd<1>, grid, block, lds, st, g);
   else if (S == 2) hipLaunchKernelGGL(k_tt_rows_bwd<2>, grid, block, lds, st, g);
@@ -1173,7 +1199,8 @@ int fill_drop(const pna_tower_drop_args* d, KArgs& g, Layout& l, bool bwd) {
 }
 
 // pna_tower_aggr_train_*: the list and the consistency of the blocks, then the base route's checks under that list
-int fill_aggr(const pna_tower_aggr_train_args* r, KArgs& g, Layout& l, bool bwd) {
+// who_pyg != NULL: the call came through pna_pyg_conv_train_*_f32 (its message; no BatchNorm, the PyG statistics)
+int fill_aggr(const pna_tower_aggr_train_args* r, KArgs& g, Layout& l, bool bwd, const char* who_pyg = nullptr) {
   static const char* const needs =
       ": needs 1 <= n_aggr <= 4 distinct codes PNA_AGG_MEAN .. PNA_AGG_VAR in aggr; a base inside pna_tower_train_*_f32's scope whose a is (V, n_tower n_aggr Fi) "
       "and whose w_post / grad_w_post are (Fo, (1 + n_aggr n_scaler) Fi), argmax where max is listed, argmin where min is listed; edge == NULL, or an edge "
@@ -1181,7 +1208,7 @@ int fill_aggr(const pna_tower_aggr_train_args* r, KArgs& g, Layout& l, bool bwd)
       "(V, n_tower Fi) where std or var is listed and mean is not; in the backward with E > 0 and edge == NULL pos_t; a 256-byte aligned workspace of "
       "pna_tower_aggr_train_workspace_bytes(V, E, n_tower, Fi, Fo, n_scaler, divide_input, edge_dim, n_aggr, aggr) bytes";
   static const std::string fwd_msg = std::string("pna_tower_aggr_train_fwd_f32") + needs, bwd_msg = std::string("pna_tower_aggr_train_bwd_f32") + needs;
-  const char* const who = bwd ? bwd_msg.c_str() : fwd_msg.c_str();
+  const char* const who = who_pyg ? who_pyg : (bwd ? bwd_msg.c_str() : fwd_msg.c_str());
   const char* const fn = bwd ? "pna_tower_aggr_train_bwd_f32" : "pna_tower_aggr_train_fwd_f32";
   if (!r) return pna_set_error(PNA_E_INVALID, who);
   if (int rc_ss = pna_check_struct_size(fn, r->struct_size, sizeof(*r))) return rc_ss;
@@ -1195,7 +1222,7 @@ int fill_aggr(const pna_tower_aggr_train_args* r, KArgs& g, Layout& l, bool bwd)
     if (int rc_ss = pna_check_struct_size(fn, r->drop->struct_size, sizeof(*r->drop))) return rc_ss;
     if (r->drop->base != r->base || r->drop->edge != r->edge || !(r->drop->p >= 0.f && r->drop->p < 1.f)) return pna_set_error(PNA_E_INVALID, who);
   }
-  ag.row_mean = r->row_mean; ag.pos_t = r->pos_t;
+  ag.row_mean = r->row_mean; ag.pos_t = r->pos_t; ag.pyg = who_pyg != nullptr;
   const int rc = fill(r->base, g, l, bwd, who, r->edge, ag);
   if (rc != PNA_OK) return rc;
   if (r->drop) g.drop = pna_philox::make_mask(r->drop->p, r->drop->seed, r->drop->offset);
@@ -1216,6 +1243,153 @@ __global__ __launch_bounds__(256) void k_dropout_mask(float* out, long ld, uint6
       out[v * (uint64_t)ld + (e - v * (uint64_t)C)] = w[i] >= m.thr ? m.scale : 0.f;
     }
   }
+}
+
+// ---- PNAConv (pna_pyg_conv_train_*): the layer's own tensors against the tower call's image ------------------------------------------
+struct PygK {
+  int T, Fi, ED;
+  const float* w_pre[kMaxT]; const float* b_pre[kMaxT];     // the layer's: (Fi, (2 | 3) Fi) = [W_i | W_j | W_e], [Fi]
+  const float* w_enc; const float* b_enc;                   // (Fi, ED), [Fi]
+  float* img;                                               // T images (Fi, 2 Fi + ED) = [W_j | W_i | M], then T biases [Fi]
+  const float* gimg;                                        // backward: the tower call's gradients in img's layout
+  float* gw_pre[kMaxT]; float* gb_pre[kMaxT]; float* gw_enc; float* gb_enc;
+};
+
+// forward, launch 0: one thread per element of the image.  M_t[f][d] = sum_k W_e,t[f][k] W_enc[k][d] and b_t[f] + sum_k W_e,t[f][k] b_enc[k]
+// in float64, k ascending, rounded once
+__global__ __launch_bounds__(256) void k_pyg_pack(const PygK g) {
+  const int Fi = g.Fi, ED = g.ED, ldw = 2 * Fi + ED, lds = (ED ? 3 : 2) * Fi, per = Fi * (ldw + 1);
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)g.T * per) return;
+  const int t = (int)(i / per), rem = (int)(i - (long)t * per), f = rem / (ldw + 1), c = rem - f * (ldw + 1);
+  const float* const w = g.w_pre[t] + (size_t)f * lds;
+  if (c < 2 * Fi) {
+    g.img[(size_t)t * Fi * ldw + (size_t)f * ldw + c] = c < Fi ? w[Fi + c] : w[c - Fi];
+    return;
+  }
+  double acc = c == ldw ? (double)g.b_pre[t][f] : 0.0;
+  if (ED) {
+    const int d = c - 2 * Fi;
+    for (int k = 0; k < Fi; ++k) acc = __builtin_fma((double)w[2 * Fi + k], (double)(c == ldw ? g.b_enc[k] : g.w_enc[(size_t)k * ED + d]), acc);
+  }
+  if (c == ldw) g.img[(size_t)g.T * Fi * ldw + (size_t)t * Fi + f] = (float)acc;
+  else g.img[(size_t)t * Fi * ldw + (size_t)f * ldw + c] = (float)acc;
+}
+
+// backward, last launch: one thread per element of grad_w_pre (T Fi lds), grad_b_pre (T Fi), grad_w_enc (Fi ED), grad_b_enc (Fi), in that
+// order.  Sums in float64: d ascending; for the encoder t outermost, then f ascending
+__global__ __launch_bounds__(256) void k_pyg_unpack(const PygK g) {
+  const int T = g.T, Fi = g.Fi, ED = g.ED, ldw = 2 * Fi + ED, lds = (ED ? 3 : 2) * Fi;
+  const long nA = (long)T * Fi * lds, nB = (long)T * Fi, nC = (long)Fi * ED, nD = ED ? Fi : 0;
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const float* const gbias = g.gimg + (size_t)T * Fi * ldw;
+  if (i < nA) {
+    const int t = (int)(i / ((long)Fi * lds)), rem = (int)(i - (long)t * Fi * lds), f = rem / lds, c = rem - f * lds;
+    const float* const gw = g.gimg + (size_t)t * Fi * ldw + (size_t)f * ldw;
+    float v;
+    if (c < Fi) v = gw[Fi + c];
+    else if (c < 2 * Fi) v = gw[c - Fi];
+    else {
+      const int k = c - 2 * Fi;
+      double acc = 0.0;
+      for (int d = 0; d < ED; ++d) acc = __builtin_fma((double)gw[2 * Fi + d], (double)g.w_enc[(size_t)k * ED + d], acc);
+      acc = __builtin_fma((double)gbias[(size_t)t * Fi + f], (double)g.b_enc[k], acc);
+      v = (float)acc;
+    }
+    g.gw_pre[t][(size_t)f * lds + c] = v;
+    return;
+  }
+  i -= nA;
+  if (i < nB) {
+    const int t = (int)(i / Fi), f = (int)(i - (long)t * Fi);
+    g.gb_pre[t][f] = gbias[i];
+    return;
+  }
+  i -= nB;
+  if (i < nC + nD) {
+    const bool bias = i >= nC;
+    const int k = bias ? (int)(i - nC) : (int)(i / ED), d = bias ? 0 : (int)(i - (long)k * ED);
+    double acc = 0.0;
+    for (int t = 0; t < T; ++t)
+      for (int f = 0; f < Fi; ++f) {
+        const float we = g.w_pre[t][(size_t)f * lds + 2 * Fi + k];
+        const float gv = bias ? gbias[(size_t)t * Fi + f] : g.gimg[(size_t)t * Fi * ldw + (size_t)f * ldw + 2 * Fi + d];
+        acc = __builtin_fma((double)we, (double)gv, acc);
+      }
+    if (bias) g.gb_enc[k] = (float)acc;
+    else g.gw_enc[(size_t)k * ED + d] = (float)acc;
+  }
+}
+
+int64_t pyg_img_floats(int T, int Fi, int ED) { return up64((int64_t)T * Fi * (2 * Fi + ED + 1)); }
+
+// The blocks of a pna_pyg_conv_train call as the shared implementation takes them: copies of the caller's base / edge / list blocks whose
+// pretrans pointers are the packed image (and, in the backward, its gradient in the workspace behind the tower call's own pieces)
+struct PygCall {
+  pna_tower_train_args base;
+  pna_tower_edge_train_args edge;
+  pna_tower_aggr_train_args aggr;
+  PygK k;
+};
+
+int fill_pyg(const pna_pyg_conv_train_args* y, PygCall& c, KArgs& g, Layout& l, bool bwd) {
+  static const char* const needs =
+      ": needs aggr (drop == NULL) with a base inside pna_tower_aggr_train_*_f32's scope, snorm_n == NULL, residual == 0; edge and w_enc / b_enc "
+      "together or not at all; every tower's w_pre (Fi, (2 | 3) Fi) and b_pre; packed of n_tower Fi (2 Fi + edge_dim + 1) floats; in the backward every "
+      "tower's grad_w_pre / grad_b_pre (grad_w_enc / grad_b_enc with w_enc); a 256-byte aligned workspace of "
+      "pna_pyg_conv_train_workspace_bytes(V, E, n_tower, Fi, Fo, n_scaler, divide_input, edge_dim, n_aggr, aggr) bytes";
+  static const std::string fwd_msg = std::string("pna_pyg_conv_train_fwd_f32") + needs, bwd_msg = std::string("pna_pyg_conv_train_bwd_f32") + needs;
+  const char* const who = bwd ? bwd_msg.c_str() : fwd_msg.c_str();
+  const char* const fn = bwd ? "pna_pyg_conv_train_bwd_f32" : "pna_pyg_conv_train_fwd_f32";
+  if (!y) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(fn, y->struct_size, sizeof(*y))) return rc_ss;
+  const pna_tower_aggr_train_args* const r = y->aggr;
+  if (!r) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(fn, r->struct_size, sizeof(*r))) return rc_ss;
+  if (!r->base || r->drop) return pna_set_error(PNA_E_INVALID, who);
+  if (int rc_ss = pna_check_struct_size(fn, r->base->struct_size, sizeof(*r->base))) return rc_ss;
+  if (r->edge) {
+    if (int rc_ss = pna_check_struct_size(fn, r->edge->struct_size, sizeof(*r->edge))) return rc_ss;
+    if (r->edge->base != r->base) return pna_set_error(PNA_E_INVALID, who);
+  }
+  const pna_tower_train_args* const p = r->base;
+  const int T = p->n_tower, Fi = p->Fi, ED = r->edge ? r->edge->edge_dim : 0;
+  Aggr ag;
+  if (!in_scope(p->V, p->E, T, Fi, p->Fo, p->n_scaler, p->divide_input) || (r->edge && (ED < 1 || ED > kMaxED)) || !read_list(r->n_aggr, r->aggr, ag))
+    return pna_set_error(PNA_E_INVALID, who);
+  if (p->snorm_n || p->residual || (y->w_enc == nullptr) != (r->edge == nullptr) || (y->w_enc == nullptr) != (y->b_enc == nullptr) || !y->packed ||
+      !p->workspace || ((uintptr_t)p->workspace & 255))
+    return pna_set_error(PNA_E_INVALID, who);
+  if (bwd && y->w_enc && (!y->grad_w_enc || !y->grad_b_enc)) return pna_set_error(PNA_E_INVALID, who);
+  for (int t = 0; t < T; ++t)
+    if (!y->w_pre[t] || !y->b_pre[t] || (bwd && (!y->grad_w_pre[t] || !y->grad_b_pre[t]))) return pna_set_error(PNA_E_INVALID, who);
+  const int64_t tower_floats = layout_of(p->V, T, Fi, p->Fo, p->n_scaler, p->E, ED, ag.A, true).total;
+  if (p->workspace_bytes < (tower_floats + pyg_img_floats(T, Fi, ED)) * 4) return pna_set_error(PNA_E_INVALID, who);
+  const int64_t ldw = 2 * (int64_t)Fi + ED;
+  float* const gimg = (float*)p->workspace + tower_floats;
+  c.base = *p;
+  c.base.slope = 1.0f;
+  memset(&c.k, 0, sizeof(c.k));
+  c.k.T = T; c.k.Fi = Fi; c.k.ED = ED; c.k.w_enc = y->w_enc; c.k.b_enc = y->b_enc; c.k.img = y->packed; c.k.gimg = gimg;
+  c.k.gw_enc = y->grad_w_enc; c.k.gb_enc = y->grad_b_enc;
+  for (int t = 0; t < T; ++t) {
+    c.k.w_pre[t] = y->w_pre[t]; c.k.b_pre[t] = y->b_pre[t]; c.k.gw_pre[t] = y->grad_w_pre[t]; c.k.gb_pre[t] = y->grad_b_pre[t];
+    c.base.w_pre[t] = y->packed + (size_t)t * Fi * ldw;
+    c.base.b_pre[t] = y->packed + (size_t)T * Fi * ldw + (size_t)t * Fi;
+    c.base.grad_w_pre[t] = gimg + (size_t)t * Fi * ldw;
+    c.base.grad_b_pre[t] = gimg + (size_t)T * Fi * ldw + (size_t)t * Fi;
+    c.base.gamma[t] = c.base.beta[t] = nullptr;
+    c.base.running_mean[t] = c.base.running_var[t] = nullptr;
+    c.base.grad_gamma[t] = c.base.grad_beta[t] = nullptr;
+  }
+  c.aggr = *r;
+  c.aggr.base = &c.base;
+  if (r->edge) {
+    c.edge = *r->edge;
+    c.edge.base = &c.base;
+    c.aggr.edge = &c.edge;
+  }
+  return fill_aggr(&c.aggr, g, l, bwd, who);
 }
 
 }  // namespace
@@ -1310,6 +1484,41 @@ extern "C" int pna_tower_aggr_train_bwd_f32(const pna_tower_aggr_train_args* r, 
   const int rc = fill_aggr(r, g, l, true);
   if (rc != PNA_OK) return rc;
   return launch_bwd(r->base, g, l, stream, r->edge, "pna_tower_aggr_train_bwd_f32: launch failed", r->drop != nullptr, true);
+}
+
+extern "C" int64_t pna_pyg_conv_train_workspace_bytes(int64_t V, int64_t E, int32_t n_tower, int32_t Fi, int32_t Fo, int32_t n_scaler, int32_t divide_input,
+                                                      int32_t edge_dim, int32_t n_aggr, const int32_t* aggr) {
+  Aggr ag;
+  if (!in_scope(V, E, n_tower, Fi, Fo, n_scaler, divide_input) || edge_dim < 0 || edge_dim > kMaxED || !read_list(n_aggr, aggr, ag)) return -1;
+  return (layout_of(V, n_tower, Fi, Fo, n_scaler, E, edge_dim, ag.A, true).total + pyg_img_floats(n_tower, Fi, edge_dim)) * 4;
+}
+
+extern "C" int pna_pyg_conv_train_fwd_f32(const pna_pyg_conv_train_args* y, pna_stream_t stream) {
+  PygCall c;
+  KArgs g;
+  Layout l;
+  const int rc = fill_pyg(y, c, g, l, false);
+  if (rc != PNA_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const char* const failed = "pna_pyg_conv_train_fwd_f32: launch failed";
+  const long n = (long)c.k.T * c.k.Fi * (2 * c.k.Fi + c.k.ED + 1);
+  hipLaunchKernelGGL(k_pyg_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c.k);
+  return c.k.ED ? launch_fwd<true, false>(g, l, st, failed) : launch_fwd<false, false>(g, l, st, failed);
+}
+
+extern "C" int pna_pyg_conv_train_bwd_f32(const pna_pyg_conv_train_args* y, pna_stream_t stream) {
+  PygCall c;
+  KArgs g;
+  Layout l;
+  int rc = fill_pyg(y, c, g, l, true);
+  if (rc != PNA_OK) return rc;
+  rc = launch_bwd(&c.base, g, l, stream, c.k.ED ? &c.edge : nullptr, "pna_pyg_conv_train_bwd_f32: launch failed", false, true);
+  if (rc != PNA_OK) return rc;
+  const int Fi = c.k.Fi, ED = c.k.ED;
+  const long n = (long)c.k.T * Fi * ((ED ? 3 : 2) * Fi + 1) + (long)Fi * ED + (ED ? Fi : 0);
+  hipLaunchKernelGGL(k_pyg_unpack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c.k);
+  if (hipGetLastError() != hipSuccess) return pna_set_error(PNA_E_LAUNCH, "pna_pyg_conv_train_bwd_f32: launch failed");
+  return PNA_OK;
 }
 
 extern "C" int pna_dropout_mask_f32(float* out, int64_t ld, int64_t V, int32_t C, float p, uint64_t seed, uint64_t offset, pna_stream_t stream) {

@@ -1233,6 +1233,19 @@ SMALL_TOWER_TRAIN_AGGR_ROWS = int(os.environ.get("PNA_AMD_SMALL_TOWER_TRAIN_AGGR
 
 TOWER_TRAIN_AGGREGATORS = ("mean", "sum", "max", "min", "std", "var")
 
+# pytorch_geometric.PNAConv calls (fp32, training or not) on batches up to this many nodes take the one-call route (autograd.PygConvFn:
+# pna_pyg_conv_train_fwd_f32 / _bwd_f32 -- the tower training kernels without BatchNorm and with the PyG statistics).  0 = off, the
+# default
+PYG_TRAIN_ROWS = int(os.environ.get("PNA_AMD_PYG_TRAIN_ROWS", "0"))
+
+
+def pyg_conv_train_fits(T, Fi, Fo, S, edge_dim, codes):
+    """Whether towers, widths, scalers, edge_dim (0 = no edge features) and the list of aggregator codes are inside
+    pna_pyg_conv_train_*_f32's scope, by the library's own check."""
+    # (the workspace query takes the whole shape: asked at the smallest batch of the scope, two rows without edges)
+    arr = (ctypes.c_int32 * max(len(codes), 1))(*[int(c) for c in codes])
+    return _lib.lib().pna_pyg_conv_train_workspace_bytes(2, 0, T, Fi, Fo, S, 0, edge_dim, len(codes), arr) >= 0
+
 
 def small_tower_aggr_train_fits(T, Fi, Fo, S, edge_dim, codes):
     """Whether towers, widths, scalers, edge_dim (0 = no edge features) and the list of aggregator codes are inside

@@ -28,7 +28,8 @@ import torch
 from torch import Tensor
 from torch.nn import Linear, ModuleList, ReLU, Sequential
 
-from .. import functional as PF, ops
+from .. import _lib, functional as PF, ops
+from .._cache import memo
 from ..graph import Graph
 from .aggregators import AGGREGATORS, _KERNEL_NAME, fix_empty_std
 from .scalers import SCALERS, row_factor
@@ -69,9 +70,14 @@ def _graph_of(edge_index: Tensor, num_nodes: int) -> Graph:
 
 
 def _row_factors(graph: Graph, scalers: List[str], avg_deg):
-    """Per-row multipliers of the scalers (None = identity) and the in-degree vector."""
-    deg = graph.in_degrees().to(torch.float32)
-    return [None if s == "identity" else row_factor(s, deg, avg_deg).contiguous() for s in scalers], deg
+    """Per-row multipliers of the scalers (None = identity) and the in-degree vector, kept on the graph per scaler list and avg_deg:
+    the layers 2..L of a net launch nothing for them."""
+    def build():
+        deg = graph.in_degrees().to(torch.float32)
+        return [None if s == "identity" else row_factor(s, deg, avg_deg).contiguous() for s in scalers], deg
+    # (topology only: built from the CSR's rowptr and the layer's three avg_deg numbers, no feature or weight tensor -- a derived array of
+    # the graph like its transposed CSR, under a tag of the graph's own)
+    return memo(graph, "_pyg_rows_and_degrees", [], (tuple(scalers), tuple(sorted(avg_deg.items()))), build)
 
 
 def _bf16_inference(module, x, edge_attr, reads_edges):
@@ -148,11 +154,40 @@ class PNAConv(PF.DropsCachesOnConversion, torch.nn.Module):
             return False
         return True
 
+    def _one_call_path(self, x, edge_attr=None):
+        """Whether a call is served by pna_pyg_conv_train_fwd_f32 / _bwd_f32 (autograd.PygConvFn: the forward as one C call, and when a
+        gradient is wanted the backward as another): the knob PNA_AMD_PYG_TRAIN_ROWS is on and covers the batch; fp32 x (V, in_channels)
+        on the GPU with V >= 2; pre_layers == post_layers == 1; every floating-point parameter fp32 on the GPU; 1-4 distinct aggregators,
+        1-3 scalers and widths functional.pyg_conv_train_fits accepts (1-8 towers, 4 <= F_in <= 128, towers F_in <= 512, out_channels <=
+        128, edge_dim absent or 1..64); edge_attr fp32 (E, edge_dim) on the GPU exactly when the layer has edge_dim.  forward() adds what
+        needs the graph: one row of edge_attr per edge and in-degrees below 65535.  Everything else takes the code it took before."""
+        rows = PF.PYG_TRAIN_ROWS
+        if not (rows > 0 and x.dim() == 2 and 2 <= x.shape[0] <= rows and x.is_cuda and x.dtype == torch.float32 and x.shape[1] == self.in_channels):
+            return False
+        if any(len(nn) != 1 for nn in self.pre_nns) or any(len(nn) != 1 for nn in self.post_nns):
+            return False
+        names, ed = self.aggregator_names, self.edge_dim
+        if not (1 <= len(names) <= 4 and len(set(names)) == len(names) and 1 <= len(self.scaler_names) <= 3 and (ed is None or 1 <= ed <= 64)):
+            return False
+        if (edge_attr is None) != (ed is None):
+            return False
+        if ed is not None and not (edge_attr.is_cuda and edge_attr.dtype == torch.float32 and edge_attr.dim() == 2 and edge_attr.shape[1] == ed):
+            return False
+        for p in self.parameters():
+            if p.dtype != torch.float32 or not p.is_cuda:
+                return False
+        return PF.pyg_conv_train_fits(self.towers, self.F_in, self.F_out, len(self.scaler_names), ed or 0, [_lib.AGG_CODES[n] for n in names])
+
     def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None) -> Tensor:
         V, T, Fi = x.shape[0], self.towers, self.F_in
         graph = _graph_of(edge_index, V)
         if self._bf16_path(x, edge_attr):
             return PF.pyg_conv_bf16(self, graph, x, edge_attr)
+        if (PF.PYG_TRAIN_ROWS > 0 and self._one_call_path(x, edge_attr) and graph.csr.max_degree < 65535
+                and (edge_attr is None or edge_attr.shape[0] == graph.csr.col.numel())):
+            # a molecule batch in fp32: the forward as one C call, the backward as another (autograd.PygConvFn)
+            from .. import autograd as AG
+            return AG.pyg_conv_one_call(self, graph, x, edge_attr, _row_factors(graph, self.scaler_names, self.avg_deg)[0])
         csr = graph.csr
         names = [_KERNEL_NAME[a] for a in self.aggregator_names]
         A, S = len(names), len(self.scaler_names)
